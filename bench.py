@@ -14,6 +14,11 @@ path ends with it): `value` includes it, `value_compute_only` and the not-overla
 
 --seconds 600 gives the per-GPU shard of BASELINE config 4 (64 ch x 10 min over 8 GPUs = 8 ch x 600 s each).
 
+A plain run does only what the headline needs: set up, the device warm-up, W warm-up steps, K timed steps, --dump-outputs DIR if given
+(what the last timed step computed, as .npy files; the inputs are seeded, so two builds compare output for output) and one JSON line.
+Every side measurement (the cold and median figures, per-kernel times and rooflines, PCIe, the other BASELINE configurations, the CPU
+baseline; at N > 1 the other gather legs, the slot check and config 4) runs with --full only; its fields are null without it.
+
 PyTorch here is plumbing only: device buffers, streams, events and torch.distributed.  The kernels are the HIP library
 flan_amd/libflanhip.so called through the C ABI (include/flanhip.h).
 """
@@ -69,7 +74,30 @@ def parse_args(argv=None):
     ap.add_argument("--no-config4", action="store_true", help="N > 1: skip the config 4 leg")
     ap.add_argument("--plan-only", action="store_true",
                     help="no GPU work: the ranks rendezvous over gloo, agree on the plan and rank 0 prints it (what tests/ use to cover the launcher on CPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every side measurement: the cold and event-timed medians, per-kernel times and rooflines, the PCIe-inclusive leg, the other "
+                         "BASELINE configurations, the CPU baseline and, at N > 1, the other gather legs, the slot check and config 4.  Without it a run sets up, "
+                         "warms up, times the K steps, writes --dump-outputs and prints the result line (those fields null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): the output audio and the PV; an "
+                         "array of more than %d values is written as a fixed sample of that many (numpy default_rng(%d), sorted flat indices)" % (1 << 22, 0))
     return ap.parse_args(argv)
+
+
+DUMP_MAX_VALUES = 1 << 22                    # per array: two arrays stay within 32 MiB
+DUMP_SEED = 0
+
+
+def dump_outputs(directory, arrays, torch):
+    """--dump-outputs: every (name, device tensor) as directory/name.npy in float32, whole when it has at most DUMP_MAX_VALUES values, else the values at
+    DUMP_MAX_VALUES flat indices drawn by numpy's default_rng(DUMP_SEED) and sorted (the same indices for the same shape, so runs compare value for value)"""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays:
+        if t.numel() > DUMP_MAX_VALUES:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, t.numel(), DUMP_MAX_VALUES))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(directory, name + ".npy"), t.float().cpu().numpy())
 
 
 def free_port():
@@ -177,7 +205,9 @@ class GatherLegs:
             self.fa.lib.flanhip_comm_destroy(self.comm)
             self.comm = None
 
-    def legs(self, audio, pv, ws, ch, n, W, HOP, DFT, steps, warmup, timed_region, unfused=False):
+    def legs(self, audio, pv, ws, ch, n, W, HOP, DFT, steps, warmup, timed_region, unfused=False, full=True, on_timed=None):
+        """the overlapped leg (the timed steps), then on_timed(the gathered buffer its last step wrote); with `full` also the slot check and the
+        compute-only, compute-then-gather and gather-alone legs"""
         fa, torch, dist, rank, world = self.fa, self.torch, self.dist, self.rank, self.world
         lib = fa.lib
         F = int(lib.flanhip_num_pv_frames(n, HOP))
@@ -241,6 +271,10 @@ class GatherLegs:
 
         res = {}
         res["overlapped_s"] = timed_region(step_overlapped, drain, steps, warmup)
+        if on_timed is not None:
+            on_timed(finals[(counter[0] - 1) & 1])
+        if not full:
+            return res
         # what arrived: every slot of both buffers against the sum its owner reports for its own slot
         ok = True
         for b in (0, 1):
@@ -406,10 +440,10 @@ def main():
 
     # device warm-up (not the W warm-up steps of the contract, which follow): a GPU that has been idle needs tens of milliseconds of
     # load before its clocks settle; without this a short run measures the ramp, not the kernels
-    # the cold figure first (what `--steps 5 --warmup 1 --preroll-ms 0` measures on a just-woken GPU): reported beside the steady-state value,
-    # never as it
+    # the cold figure first (what `--steps 5 --warmup 1 --preroll-ms 0` measures on a just-woken GPU, --full only): reported beside the
+    # steady-state value, never as it
     cold = None
-    if args.preroll_ms > 0 and not distributed:
+    if args.full and args.preroll_ms > 0 and not distributed:
         step()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -453,35 +487,44 @@ def main():
         dt = time.perf_counter() - t0
         return sharding.max_over_ranks(dist, dt, ctl_dev) if distributed else dt
 
+    def dump(final):
+        """--dump-outputs, straight after the timed steps: what their last step computed (rank 0: the gathered output at N > 1)"""
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, [("audio_out", final), ("pv", pv)], torch)
+
     elapsed_compute = None
     legs = None
     if use_gather:
         # the headline shape with the gather: the K timed steps of the contract are the overlapped ones
-        legs = gather.legs(audio, pv, ws, ch, n, WINDOW, HOP, DFT, args.steps, args.warmup, timed_region, unfused=args.unfused)
-        elapsed, elapsed_compute = legs["overlapped_s"], legs["compute_only_s"]
+        legs = gather.legs(audio, pv, ws, ch, n, WINDOW, HOP, DFT, args.steps, args.warmup, timed_region, unfused=args.unfused, full=args.full,
+                           on_timed=dump)
+        elapsed, elapsed_compute = legs["overlapped_s"], legs.get("compute_only_s")
     else:
         elapsed = timed_region(step, lambda: None)
+        dump(out)
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * frames_per_step * args.steps / elapsed
     value_compute_only = world * frames_per_step * args.steps / elapsed_compute if elapsed_compute else None
     # SURVEY 8(d): "hipEvent-timed, median of >= 20 runs" -- the same step, each one bracketed by events on the launch stream, reported
-    # beside the contract's barrier-to-barrier mean over K steps
-    n_med = max(20, min(args.steps, 200))
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_med)]
-    for e0, e1 in evs:
-        e0.record()
-        step()
-        e1.record()
-    torch.cuda.synchronize()
-    per = sorted(e0.elapsed_time(e1) for e0, e1 in evs)
-    step_ms_median = per[len(per) // 2]
+    # beside the contract's barrier-to-barrier mean over K steps (--full)
+    step_ms_median = None
+    if args.full:
+        n_med = max(20, min(args.steps, 200))
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_med)]
+        for e0, e1 in evs:
+            e0.record()
+            step()
+            e1.record()
+        torch.cuda.synchronize()
+        per = sorted(e0.elapsed_time(e1) for e0, e1 in evs)
+        step_ms_median = per[len(per) // 2]
 
     # per-kernel timing with events on the launch stream (rank 0 only), inside the same analyse -> synthesise sequence as the
     # timed region: events bracket k_analyze, the pre-pass (k_phase_sums unless fused, k_phase_scan), k_synthesize and
     # k_ola_fixup of every step (the `stages` argument of flanhip_synthesize_dev_stages selects which synthesis kernels a call launches)
     extra = {}
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         reps = max(5, args.steps)
         acc = [0.0, 0.0, 0.0, 0.0]
         for _ in range(reps):
@@ -580,7 +623,7 @@ def main():
                                   "frac_of_8TBs": round(frames_per_step * BYTES_ROUNDTRIP / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
 
     # ---- the gather legs for the record, and BASELINE config 4's shape (64 ch x 10 min over 8 GPUs = 8 ch x 600 s per rank) through the same steps ----
-    if use_gather:
+    if use_gather and args.full:
         t_compute, t_then, t_over = (legs[k] / args.steps for k in ("compute_only_s", "then_gather_s", "overlapped_s"))
         extra["allgather"] = {"nranks": gather.nranks, "api": gather.api, "api_error": gather.err, "ms_alone": round(legs["gather_alone_ms"], 3),
                               "bytes_per_rank": ch * F * HOP * 4, "slots_verified": legs["slots_verified"],
@@ -600,7 +643,7 @@ def main():
                 extra["config4"] = {"error": repr(e)}
 
     # the host-buffer C ABI (flanhip_analyze / flanhip_synthesize): upload, kernels, download -- for DESIGN.md, never the metric
-    if rank == 0 and world == 1 and not use_gather and not args.no_pcie and ( args.pcie or ( ch * n <= 8 * 60 * 48000 and DFT <= 4096 ) ):
+    if args.full and rank == 0 and world == 1 and not use_gather and not args.no_pcie and ( args.pcie or ( ch * n <= 8 * 60 * 48000 and DFT <= 4096 ) ):
         import numpy as np
         x_host = audio.cpu().numpy()
         fa.analyze(x_host[:1, :48000], SR, WINDOW, HOP, DFT)
@@ -616,7 +659,7 @@ def main():
         del pv_host, out_host
 
     # ---- the other BASELINE configurations, timed the same way (device resident, events, after the same warm-up) ----
-    if rank == 0 and world == 1 and not args.no_configs and not use_gather:
+    if args.full and rank == 0 and world == 1 and not args.no_configs and not use_gather:
         del pv, out, ws
         torch.cuda.empty_cache()
         try:
@@ -625,7 +668,7 @@ def main():
             extra["configs"] = {"error": repr(e)}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:        # the CPU leg is reported at N=1 only; the other ranks would idle behind it
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:        # the CPU leg is reported at N=1 only; the other ranks would idle behind it
         cores = os.cpu_count() or 1
         sample_s = min(args.seconds, 60.0)           # bounded: at most 8 x 60 s = 45 008 frames (~4 s on one core, the same again on all)
         v1, frames1, dt1 = cpu_baseline(ch, sample_s, 1, WINDOW, HOP, DFT)
@@ -653,8 +696,8 @@ def main():
         }
         if share_gpu:
             line["rehearsal"] = "FLAN_BENCH_SHARE_GPU=1: %d ranks on one GPU, gloo control plane, no RCCL gather" % world
-        line["ms_per_step_median"] = round(step_ms_median, 4)          # median of >= 20 event-timed steps; ms_per_step: the K steps between barriers
-        line["value_median"] = round(world * frames_per_step / (step_ms_median * 1e-3), 1) if world == 1 else None
+        line["ms_per_step_median"] = round(step_ms_median, 4) if step_ms_median else None      # median of >= 20 event-timed steps; ms_per_step: the K steps between barriers
+        line["value_median"] = round(world * frames_per_step / (step_ms_median * 1e-3), 1) if world == 1 and step_ms_median else None
         line["value_cold"] = cold["frames_per_s"] if cold else None       # a just-woken GPU, 5 steps after 1 (no clock pre-roll)
         ag = extra.get("allgather") or {}
         # N > 1: `value` is the step WITH the north star's output reassembly (the all-gather overlapped with the next batch's compute);
@@ -670,6 +713,7 @@ def main():
         line["rccl_nranks"] = ag.get("nranks")
         line["config4"] = extra.pop("config4", None)                       # N > 1: BASELINE config 4's shape per rank -- compute only, compute then all-gather, overlapped
         line["device_warmup"] = {"preroll_ms": args.preroll_ms, "preroll_steps": preroll_steps, "cold": cold}
+        line["full"] = args.full                                           # False: the side measurements above are null (bench.py --full takes them)
         line.update(extra)
         print(json.dumps(line), flush=True)
     if gather is not None:

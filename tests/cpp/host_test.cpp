@@ -21,6 +21,7 @@
 using namespace flan;
 
 static int failures = 0;
+static std::string g_flan_path = "flan_host_test.flan";          // where the .flan round trip writes: --flan-file=PATH (the test's own temporary directory)
 #define CHECK( cond ) do { if( !( cond ) ) { std::printf( "FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond ); ++failures; } } while( 0 )
 static bool close_to( double a, double b, double rel ) { return std::fabs( a - b ) <= rel * std::fabs( b ) + 1e-30; }
 
@@ -112,7 +113,7 @@ static void no_device_checks()
 	CHECK( p.bin_to_frequency( 1 ) == 6000.0f && p.frequency_to_bin( 12000.0f ) == 2.0f );
 	CHECK( close_to( p.time_to_frame( 1.0f ), 93.75, 1e-7 ) );
 	p.get_MF( 0, 1, 2 ) = MF{ 3.0f, 440.0f };
-	const std::string path = "/tmp/flan_host_test.flan";
+	const std::string path = g_flan_path;
 	CHECK( p.save( path ) );
 	PV q = PV::load_from_file( path );
 	CHECK( q.get_num_frames() == 3 && q.get_num_bins() == 5 && q.get_window_size() == 8 );
@@ -509,7 +510,13 @@ static void device_checks()
 
 int main( int argc, char ** argv )
 	{
-	const bool no_device = argc > 1 && std::string( argv[1] ) == "--no-device";
+	bool no_device = false;
+	for( int i = 1; i < argc; ++i )
+		{
+		const std::string a = argv[i];
+		if( a == "--no-device" ) no_device = true;
+		else if( a.rfind( "--flan-file=", 0 ) == 0 ) g_flan_path = a.substr( 12 );
+		}
 	if( no_device ) no_device_checks(); else device_checks();
 	std::printf( "\n%s (%d failures)\n", failures ? "FAILED" : "PASSED", failures );
 	return failures ? 1 : 0;

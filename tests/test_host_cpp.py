@@ -23,13 +23,13 @@ def _run(args):
     return subprocess.run([BIN] + args, capture_output=True, text=True, env=env, timeout=300)
 
 
-def test_host_surface_without_device():
+def test_host_surface_without_device(tmp_path):
     """no GPU: null objects and a loud error, never a CPU fallback"""
     import torch
     if torch.cuda.is_available():
         pytest.skip("a GPU is visible here; the no-device behaviour is checked in the CPU container")
     _build()
-    r = _run(["--no-device"])
+    r = _run(["--no-device", "--flan-file=%s" % (tmp_path / "host_test.flan")])
     print(r.stdout, r.stderr)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "PASSED" in r.stdout

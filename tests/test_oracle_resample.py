@@ -6,7 +6,8 @@ import pytest
 import oracle_lib as O
 
 r8b = O.load_r8b_ref()
-pytestmark = pytest.mark.skipif(r8b is None, reason="oracle/_ref/libr8bref.so not built (no /root/reference)")
+# only the comparisons with the real r8brain need it; the checker's own known answers and fixtures run everywhere
+needs_r8b = pytest.mark.skipif(r8b is None, reason="oracle/_ref/libr8bref.so not built (the reference sources were not available to build())")
 
 
 def ref_resample(x, src, dst):
@@ -25,6 +26,7 @@ def test_filter_is_the_1621_tap_design():
     assert np.allclose(h, h[::-1], rtol=0, atol=1e-18) and abs(h.sum() - 1.0) < 1e-12
 
 
+@needs_r8b
 @pytest.mark.parametrize("ch,n", [(2, 9600), (1, 20001), (2, 4801), (3, 1000), (1, 100)])
 def test_restatement_matches_r8brain(ch, n):
     rng = np.random.default_rng(ch * 1000 + n)
@@ -39,6 +41,7 @@ def test_restatement_matches_r8brain(ch, n):
     assert same >= 0.995
 
 
+@needs_r8b
 def test_impulse_and_channel_bleed():
     """an impulse at the end of channel 0 rings into the start of channel 1: the buffer is one stream"""
     x = np.zeros((2, 4000), np.float32)
@@ -53,6 +56,7 @@ RATES = [(144000.0, 48000.0, 1, 3), (72000.0, 48000.0, 2, 3), (32000.0, 48000.0,
          (16000.0, 48000.0, 3, 1), (96000.0, 48000.0, 1, 2), (44100.0, 88200.0, 2, 1), (88200.0, 44100.0, 1, 2)]
 
 
+@needs_r8b
 @pytest.mark.parametrize("src,dst,up,down", RATES)
 def test_single_step_ratios_match_r8brain(src, dst, up, down):
     """every ratio CDSPResampler serves with one block convolver (CDSPResampler.h:139-207): zero-stuff by `up`, the default
@@ -81,6 +85,7 @@ TWO_STAGE = [(44100.0, 48000.0), (48000.0, 44100.0), (96000.0, 44100.0), (22050.
              (32000.0, 44100.0), (44100.0, 12000.0), (48000.0, 22050.0), (11025.0, 8000.0)]
 
 
+@needs_r8b
 @pytest.mark.parametrize("src,dst", TWO_STAGE)
 def test_two_stage_ratios_match_r8brain(src, dst):
     """the ratios CDSPResampler serves with one block convolver and one whole-stepping CDSPFracInterpolator (CDSPResampler.h:214-316,
@@ -103,6 +108,7 @@ HB_CHAINS = [(48000.0, 192000.0), (44100.0, 176400.0), (48000.0, 384000.0), (160
              (96000.0, 16000.0), (192000.0, 24000.0), (192000.0, 44100.0), (384000.0, 48000.0), (384000.0, 16000.0), (768000.0, 48000.0)]
 
 
+@needs_r8b
 @pytest.mark.parametrize("src,dst", HB_CHAINS)
 def test_half_band_chains_match_r8brain(src, dst):
     """chains with CDSPHBUpsampler / CDSPHBDownsampler stages (CDSPResampler.h:174-212, :319-378): the restatement against the vendored
@@ -123,6 +129,7 @@ def test_half_band_chains_match_r8brain(src, dst):
 SPLINE = [(44100.0, 48001.0), (48000.0, 50854.3), (44100.0, 22000.0), (44100.0, 44056.0), (96000.0, 44101.0), (44100.0, 30000.5), (44100.0, 14000.3)]
 
 
+@needs_r8b
 @pytest.mark.parametrize("src,dst", SPLINE)
 def test_ratios_without_whole_stepping_match_r8brain(src, dst):
     """no small common divisor: CDSPFracInterpolator with the spline-interpolated bank (getFilterBank( -1, 3, 8, ... ): FilterFracs from the
@@ -145,6 +152,7 @@ GENERAL = [(1000.0, 64000.0), (96000.0, 1000.0), (500.0, 44100.0), (768000.0, 15
            (96000.0, 11026.0), (1000.0, 44100.0), (44100.0, 48000.0), (96000.0, 48000.0), (192000.0, 44100.0), (8000.0, 96000.0)]
 
 
+@needs_r8b
 @pytest.mark.parametrize("src,dst", GENERAL)
 def test_stage_list_matches_r8brain(src, dst):
     """the whole of CDSPResampler's constructor as a stage list (build_stages): upsampling with intermediate interpolation, half-band stages in

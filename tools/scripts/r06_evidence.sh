@@ -10,7 +10,7 @@ cd $R
 bash tools/scripts/profile_bench.sh > $O/profile_bench.log 2>&1
 for f in prof_kt.json sq_summary.txt inst_classes.txt hbm_summary.txt kernel_stats.csv; do cp gpurun_out/$f $O/ 2>/dev/null; done
 echo "headline profile done" > $O/progress.txt
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err
 echo "bench done" >> $O/progress.txt
 bash tools/scripts/timeline_config3.sh > $O/config3_timeline.txt 2>&1
 echo "config 3 done" >> $O/progress.txt
