@@ -123,6 +123,14 @@ _SIGS = {
     "flanhip_noise_dev": (C.c_int, [_vp, _i64, _i64, C.c_uint32, _vp]),
     "flanhip_sqdiff_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     "flanhip_copy_dev": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "flanhip_spv_analyze": (C.c_int, [_vp, _i64, _i64, _f32, _i32, _vp, _vp]),
+    "flanhip_spv_analyze_dev": (C.c_int, [_vp, _i64, _i64, _f32, _i32, _vp, _vp]),
+    "flanhip_spv_synthesize_workspace_bytes": (C.c_size_t, [_i64, _i64, _i32, _f32]),
+    "flanhip_spv_synthesize": (C.c_int, [_vp, _i64, _i64, _i32, _f32, _vp, _vp]),
+    "flanhip_spv_synthesize_dev": (C.c_int, [_vp, _i64, _i64, _i32, _f32, _vp, _vp, _vp]),
+    "flanhip_spv_modify_frequency_const_dev": (C.c_int, [_vp, _i64, _i64, _i32, _f32, _i32, _vp, _vp]),
+    "flanhip_spv_twiddles": (C.c_int, [_i32, _vp]),
+    "flanhip_spv_debug_chain_length": (None, [_i32]),
 }
 
 EXPORTS = sorted(_SIGS)
@@ -606,3 +614,63 @@ def synthesize_workspace_bytes(ch, F, bins, sample_rate, analysis_rate, window):
 def synthesize_dev(d_pv, ch, F, bins, sample_rate, analysis_rate, window, d_out, d_ws, d_nan=None, stream=None):
     check(lib.flanhip_synthesize_dev(_dp(d_pv), ch, F, bins, sample_rate, analysis_rate, window, _dp(d_out), _dp(d_ws),
                                      _dp(d_nan), _vp(stream or 0)))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the sliding-DFT vocoder (Audio::convert_to_SPV / SPV::convert_to_audio): one spectrum per input sample
+# ---------------------------------------------------------------------------------------------------------------
+
+def spv_analyze(audio, sample_rate, num_bins=1024):
+    """Audio::convert_to_SPV.  audio float32 [ch][n] -> float32 [ch][n][num_bins][2] (m, f)."""
+    audio = np.ascontiguousarray(audio, np.float32)
+    ch, n = audio.shape
+    out = np.empty((ch, n, num_bins, 2), np.float32)
+    check(lib.flanhip_spv_analyze(_ptr(audio), ch, n, sample_rate, num_bins, _ptr(out), None))
+    return out
+
+
+def spv_synthesize(spv, sample_rate):
+    """SPV::convert_to_audio.  spv float32 [ch][n][bins][2] -> float32 [ch][n]."""
+    spv = np.ascontiguousarray(spv, np.float32)
+    ch, n, bins, _ = spv.shape
+    out = np.empty((ch, n), np.float32)
+    check(lib.flanhip_spv_synthesize(_ptr(spv), ch, n, bins, sample_rate, _ptr(out), None))
+    return out
+
+
+def spv_twiddles(num_bins):
+    """The analysis' twiddle table, float32 [2 num_bins][2] (re, im), computed on the host."""
+    out = np.empty((2 * num_bins, 2), np.float32)
+    check(lib.flanhip_spv_twiddles(num_bins, _ptr(out)))
+    return out
+
+
+def spv_analyze_dev(d_audio, ch, n, sample_rate, num_bins, d_out, stream=None):
+    check(lib.flanhip_spv_analyze_dev(_dp(d_audio), ch, n, sample_rate, num_bins, _dp(d_out), _vp(stream or 0)))
+
+
+def spv_synthesize_workspace_bytes(ch, n, num_bins, sample_rate):
+    return int(lib.flanhip_spv_synthesize_workspace_bytes(ch, n, num_bins, sample_rate))
+
+
+def spv_synthesize_dev(d_spv, ch, n, num_bins, sample_rate, d_out, d_ws, stream=None):
+    check(lib.flanhip_spv_synthesize_dev(_dp(d_spv), ch, n, num_bins, sample_rate, _dp(d_out), _dp(d_ws), _vp(stream or 0)))
+
+
+def spv_modify_frequency_const_dev(d_spv, ch, n, num_bins, value, multiply, d_out, stream=None):
+    check(lib.flanhip_spv_modify_frequency_const_dev(_dp(d_spv), ch, n, num_bins, value, int(bool(multiply)), _dp(d_out), _vp(stream or 0)))
+
+
+class spv_chain_length:
+    """with fa.spv_chain_length(100): ...   -- frames per chain of this thread's SPV launches, back to the library's choice afterwards"""
+
+    def __init__(self, frames):
+        self.frames = int(frames)
+
+    def __enter__(self):
+        lib.flanhip_spv_debug_chain_length(self.frames)
+        return self
+
+    def __exit__(self, *exc):
+        lib.flanhip_spv_debug_chain_length(0)
+        return False

@@ -9,6 +9,7 @@
 namespace flan {
 
 class PV;
+class SPV;
 
 class Audio : public AudioBuffer
 	{
@@ -35,6 +36,11 @@ public:
 	PV convert_to_ms_PV( Frame window_size = 2048, Frame hop = 128, Frame dft_size = 4096, flan_CANCEL_ARG ) const;
 	Audio convert_to_mid_side() const;                                           // AudioConversions.cpp:32-51
 	Audio convert_to_left_right() const;                                         // :53-56
+	/** The sliding-DFT vocoder (Conversions/AudioSPV.cpp:27-102): one spectrum of dft_size bins per input sample, on the device
+	 *  (flanhip_spv_analyze_dev).  dft_size < 2 returns a null SPV (the reference reads bin 1 of every frame). */
+	SPV convert_to_SPV( Bin dft_size = 1024, flan_CANCEL_ARG ) const;
+	/** AudioSPV.cpp:104-108: convert_to_mid_side().convert_to_SPV( dft_size ) */
+	SPV convert_to_ms_SPV( Bin dft_size = 1024, flan_CANCEL_ARG ) const;
 	/** r8brain-equivalent sample-rate conversion (AudioConversions.cpp:14-30). */
 	Audio resample( FrameRate new_sample_rate ) const;
 

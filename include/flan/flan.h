@@ -4,5 +4,7 @@
 #include "flan/Function.h"
 #include "flan/AudioBuffer.h"
 #include "flan/PVBuffer.h"
+#include "flan/SPVBuffer.h"
 #include "flan/Audio.h"
 #include "flan/PV.h"
+#include "flan/SPV.h"

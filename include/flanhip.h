@@ -394,6 +394,41 @@ int flanhip_smear_time_dev(const flanhip_MF * d_pv, int64_t num_channels, int64_
 /* ---- Audio::convert_to_mid_side / convert_to_left_right (Audio/AudioConversions.cpp:32-56), stereo only ------ */
 int flanhip_mid_side_dev(const float * d_in, int64_t num_audio_frames, float * d_out, void * stream);
 
+/* ---- Audio::convert_to_SPV / SPV::convert_to_audio: the sliding-DFT vocoder (Conversions/AudioSPV.cpp, SPV/SPVBuffer.cpp) --- */
+/* N = num_bins (the reference's dft_size), L = 2 N.  audio: float[ch][n]; spv: flanhip_MF[ch][n][N] -- one spectrum per input sample,
+ * so 8 n N bytes per channel (1 s of 48 kHz at N = 1024: 393 MB).  The analysis rate of an SPV is its sample rate and bin b sits at
+ * b sr / N (SPVBuffer.cpp).  Analysis (AudioSPV.cpp:27-108): L-point sliding DFT of the trailing window, frequency-domain Hann 3-tap
+ * (with the reference's edge rule at bins 0 and N-1), phase_vocoder with the phases of the previous SAMPLE.  The GPU seeds each chain
+ * of frames from a direct sum over the window before it, so the spectra follow the exact transform more closely than
+ * the reference's fp32 running sum over the whole channel; they are not bit-identical to it.  Synthesis (AudioSPV.cpp:110-145):
+ * inverse_phase_vocoder per bin, sample = 2 sum_b (-1)^b m cos( phase ).
+ * Differences from the reference, on purpose: indices are 64-bit, so the twiddle index (f b) mod L is the intended one past
+ * f b >= 2^31 (the reference's int32 product turns negative there, about 44.7 s at 48 kHz and N = 1024, and indexes out of its
+ * table); N < 2 is FLANHIP_ERR_UNSUPPORTED (the reference reads bin 1 of a one-bin frame).  N up to 2^24.
+ * `cancel` is polled before the upload and before the launch.  Unlike the STFT kernels, the SPV kernels do not poll it: once launched they
+ * run to the end, and a flag raised meanwhile makes the call return FLANHIP_ERR_CANCELLED after the stream has drained. */
+int flanhip_spv_analyze(const float * audio, int64_t num_channels, int64_t num_audio_frames, float sample_rate, int num_bins,
+                        flanhip_MF * out, volatile int * cancel);
+int flanhip_spv_analyze_dev(const float * d_audio, int64_t num_channels, int64_t num_audio_frames, float sample_rate, int num_bins,
+                            flanhip_MF * d_out, void * stream);
+/* bytes of device workspace flanhip_spv_synthesize_dev needs (pure host arithmetic; 0 for arguments it refuses).  Sized for the
+ * calling thread's flanhip_spv_debug_chain_length setting: size and launch under the same one. */
+size_t flanhip_spv_synthesize_workspace_bytes(int64_t num_channels, int64_t num_frames, int num_bins, float sample_rate);
+/* spv: flanhip_MF[ch][n][N]; out: float[ch][n] */
+int flanhip_spv_synthesize(const flanhip_MF * spv, int64_t num_channels, int64_t num_frames, int num_bins, float sample_rate,
+                           float * out, volatile int * cancel);
+int flanhip_spv_synthesize_dev(const flanhip_MF * d_spv, int64_t num_channels, int64_t num_frames, int num_bins, float sample_rate,
+                               float * d_out, void * d_workspace, void * stream);
+/* SPV::modify_frequency / repitch (SPV/SPV.cpp:21-44) with a constant Function: f = value (multiply 0) or f = f * value (multiply 1),
+ * m unchanged.  d_out may be d_spv. */
+int flanhip_spv_modify_frequency_const_dev(const flanhip_MF * d_spv, int64_t num_channels, int64_t num_frames, int num_bins, float value,
+                                           int multiply, flanhip_MF * d_out, void * stream);
+/* the twiddle table T[i] = polar( 1.0f, omega i ), omega = -pi2 / L as a float (AudioSPV.cpp:13-22): float[2 L] (re, im).  No device. */
+int flanhip_spv_twiddles(int num_bins, float * out);
+/* test hook: frames per chain of the calling thread's SPV launches (0: the library's choice).  Results do not depend on the cut beyond
+ * rounding. */
+void flanhip_spv_debug_chain_length(int frames);
+
 /* ---- Audio::resample (Audio/AudioConversions.cpp:14-30, r8brain CDSPResampler with default parameters) --------- */
 /* AudioConversions.cpp:22: out frames = Frame( float(num_frames) * ( dst_rate / src_rate ) ) */
 int64_t flanhip_resample_out_frames(int64_t num_frames, float src_rate, float dst_rate);
