@@ -131,6 +131,11 @@ _SIGS = {
     "flanhip_spv_modify_frequency_const_dev": (C.c_int, [_vp, _i64, _i64, _i32, _f32, _i32, _vp, _vp]),
     "flanhip_spv_twiddles": (C.c_int, [_i32, _vp]),
     "flanhip_spv_debug_chain_length": (None, [_i32]),
+    "flanhip_convolve_out_frames": (_i64, [_i64, _i64]),
+    "flanhip_convolve_workspace_bytes": (C.c_size_t, [_i64, _i64, _i64, _i64]),
+    "flanhip_convolve": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _f32, _i32, _vp, _vp]),
+    "flanhip_convolve_dev": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _f32, _i32, _vp, _vp, _vp]),
+    "flanhip_convolve_debug_partition": (None, [_i32]),
 }
 
 EXPORTS = sorted(_SIGS)
@@ -673,4 +678,56 @@ class spv_chain_length:
 
     def __exit__(self, *exc):
         lib.flanhip_spv_debug_chain_length(0)
+        return False
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Audio::convolve: partitioned FFT convolution (the IR at the audio's sample rate)
+# ---------------------------------------------------------------------------------------------------------------
+
+def convolve_out_frames(n, m):
+    return int(lib.flanhip_convolve_out_frames(n, m))
+
+
+def convolve_partition(n, m):
+    """The partition the library takes for an n-frame input and an m-frame IR (flanhip.h): the smallest of 512 ... 4096 with
+    ceil(m / P) <= 32, else 4096.  (A forced partition, convolve_partition_forced, overrides it.)"""
+    P = 512
+    while P < 4096 and -(-m // P) > 32:
+        P *= 2
+    return P
+
+
+def convolve(audio, ir, sample_rate, normalize=True):
+    """Audio::convolve with both at one rate.  audio float32 [ch][n], ir float32 [ir_ch][m] -> float32 [ch][n + m]."""
+    audio = np.ascontiguousarray(audio, np.float32)
+    ir = np.ascontiguousarray(ir, np.float32)
+    ch, n = audio.shape
+    irch, m = ir.shape
+    out = np.empty((ch, n + m), np.float32)
+    check(lib.flanhip_convolve(_ptr(audio), ch, n, _ptr(ir), irch, m, sample_rate, int(bool(normalize)), _ptr(out), None))
+    return out
+
+
+def convolve_workspace_bytes(ch, n, ir_ch, m):
+    return int(lib.flanhip_convolve_workspace_bytes(ch, n, ir_ch, m))
+
+
+def convolve_dev(d_audio, ch, n, d_ir, ir_ch, m, sample_rate, normalize, d_out, d_ws, stream=None):
+    check(lib.flanhip_convolve_dev(_dp(d_audio), ch, n, _dp(d_ir), ir_ch, m, sample_rate, int(bool(normalize)), _dp(d_out), _dp(d_ws),
+                                   _vp(stream or 0)))
+
+
+class convolve_partition_forced:
+    """with fa.convolve_partition_forced(1024): ...   -- the partition of this thread's convolutions, back to the library's choice afterwards"""
+
+    def __init__(self, samples):
+        self.samples = int(samples)
+
+    def __enter__(self):
+        lib.flanhip_convolve_debug_partition(self.samples)
+        return self
+
+    def __exit__(self, *exc):
+        lib.flanhip_convolve_debug_partition(0)
         return False

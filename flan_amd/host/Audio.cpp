@@ -1,5 +1,6 @@
 // Audio.cpp -- construction and conversions of flan::Audio over the C ABI
-// (reference: src/flan/Audio/AudioConstructors.cpp, Conversions/AudioPV.cpp:12-84, Audio/AudioConversions.cpp:14-56).
+// (reference: src/flan/Audio/AudioConstructors.cpp, Conversions/AudioPV.cpp:12-84, Audio/AudioConversions.cpp:14-56,
+// Audio/AudioCombination.cpp:299-352).
 #include "flan/Audio.h"
 
 #include <iostream>
@@ -122,6 +123,36 @@ Audio Audio::resample( FrameRate new_sample_rate ) const
 	if( !detail::report( flanhip_resample_dev( d_in, get_num_channels(), get_num_frames(), get_sample_rate(), new_sample_rate,
 			static_cast<float*>( block->ptr ), nullptr ), "resample" ) ) return Audio::create_null();
 	if( !detail::report( flanhip_stream_synchronize( nullptr ), "resample" ) ) return Audio::create_null();
+	return AudioBuffer::adopt_device( f, std::move( block ) );
+	}
+
+Audio Audio::convolve( const Audio & ir, bool normalize ) const
+	{
+	if( is_null() ) return Audio::create_null();                // AudioCombination.cpp:304-305
+	if( ir.is_null() ) return Audio::create_null();
+	// :307-308: an IR of another rate is resampled to this one first (all its channels as one stream, Audio::resample)
+	const Audio resampled = get_sample_rate() == ir.get_sample_rate() ? Audio() : ir.resample( get_sample_rate() );
+	const Audio & h = get_sample_rate() == ir.get_sample_rate() ? ir : resampled;
+	if( h.is_null() ) return Audio::create_null();
+	AudioBuffer::Format f = get_format();                        // :310-313
+	f.num_frames = Frame( flanhip_convolve_out_frames( get_num_frames(), h.get_num_frames() ) );
+	const size_t ws_bytes = flanhip_convolve_workspace_bytes( get_num_channels(), get_num_frames(), h.get_num_channels(), h.get_num_frames() );
+	if( f.num_frames <= 0 || ws_bytes == 0 )
+		{
+		std::cerr << "flan: convolve refused the shape: " << get_num_channels() << " x " << get_num_frames() << " with "
+		          << h.get_num_channels() << " x " << h.get_num_frames() << std::endl;
+		return Audio::create_null();
+		}
+	const float * d_x = device_data();
+	const float * d_h = h.device_data();
+	if( !d_x || !d_h ) return Audio::create_null();
+	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( f.num_channels ) * size_t( f.num_frames ) );
+	auto ws = detail::DeviceBlock::allocate( ws_bytes );
+	if( !block || !ws ) return Audio::create_null();
+	const int rc = flanhip_convolve_dev( d_x, get_num_channels(), get_num_frames(), d_h, h.get_num_channels(), h.get_num_frames(),
+		get_sample_rate(), normalize ? 1 : 0, static_cast<float*>( block->ptr ), ws->ptr, nullptr );
+	if( !detail::report( rc, "convolve" ) ) return Audio::create_null();
+	if( !detail::report( flanhip_stream_synchronize( nullptr ), "convolve" ) ) return Audio::create_null();   // the workspace goes back idle
 	return AudioBuffer::adopt_device( f, std::move( block ) );
 	}
 

@@ -43,6 +43,12 @@ public:
 	SPV convert_to_ms_SPV( Bin dft_size = 1024, flan_CANCEL_ARG ) const;
 	/** r8brain-equivalent sample-rate conversion (AudioConversions.cpp:14-30). */
 	Audio resample( FrameRate new_sample_rate ) const;
+	/** Convolution with an impulse response (Audio/AudioCombination.cpp:299-352), on the device (flanhip_convolve_dev).
+	 *  A null *this or ir gives a null Audio; an ir of another sample rate is first ir.resample( get_sample_rate() ).  The result has
+	 *  this Audio's channels and sample rate and n + m frames; IR channels are used cyclically (channel c takes ir channel c % ir channels).
+	 *  normalize: the result times 1.0f / get_max_sample_magnitude(), so an all-zero result becomes NaN everywhere (0 * inf), as in the
+	 *  reference.  The result stays device-resident until read. */
+	Audio convolve( const Audio & ir, bool normalize = true ) const;
 
 	// the older camelCase spellings BASELINE.json's north_star uses
 	PV convertToPV( Frame window_size = 2048, Frame hop = 128, Frame dft_size = 4096, flan_CANCEL_ARG ) const;

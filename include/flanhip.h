@@ -429,6 +429,34 @@ int flanhip_spv_twiddles(int num_bins, float * out);
  * rounding. */
 void flanhip_spv_debug_chain_length(int frames);
 
+/* ---- Audio::convolve: partitioned FFT convolution (Audio/AudioCombination.cpp:299-352) --------------------------------------- */
+/* audio: float[ch][n]; ir: float[ir_ch][m], at the audio's sample rate (resampling an IR of another rate is the C++ layer's job,
+ * Audio::convolve); out: float[ch][n + m] (n + m frames, as the reference's; the last one is 0 up to round-off).
+ * out[c][t] = sum_k audio[c][t-k] ir[c % ir_ch][k]: IR channels are used cyclically.  Uniformly partitioned overlap-save with
+ * partition P: K = ceil( m / P ) IR spectra, J = ceil( (n + m) / P ) input and output spectra, each a 2P-point fp32
+ * FFT on the device; the library takes the smallest P of 512, 1024, 2048, 4096 with K <= 32, else 4096.  Numerics: fp32 throughout,
+ * within about 5e-7 rms (relative) of the exact convolution, not bit-identical to FFTW's D = 2 pow2( max( n, m ) ) transform;
+ * deterministic (no floating-point atomics: two calls agree bit for bit).
+ * normalize != 0: out *= 1.0f / max |out|, the max over frames [0, end) with end = clamp( Frame( float(N) / sr * sr ), 0, N - 1 ),
+ * N = n + m (AudioBuffer::get_max_sample_magnitude() with default arguments, in fp32), the reciprocal and product in fp32 like the
+ * reference's modify_volume_in_place.  sample_rate serves only this range.  If that max is 0 the gain is +inf, as in the reference:
+ * every sample becomes NaN (0 * inf) or +-inf.
+ * Workspace: 8 (P+1) (2 ch J + min( ch, ir_ch ) K) + 8192 bytes (the X and Y spectra, the IR spectra of the IR channels used, and
+ * 64 partial maxima of normalize, 128 bytes apart).
+ * Non-positive sizes, null pointers, a non-positive sample rate and (for _dev) a null workspace are FLANHIP_ERR_INVALID_ARG.
+ * `cancel` is polled before the upload and before the launch; the kernels run to the end once launched. */
+int64_t flanhip_convolve_out_frames(int64_t num_frames, int64_t ir_frames);           /* n + m; 0 for non-positive sizes */
+/* bytes of device workspace flanhip_convolve_dev needs (pure host arithmetic; 0 for arguments it refuses).  Sized for the calling
+ * thread's flanhip_convolve_debug_partition setting: size and launch under the same one. */
+size_t  flanhip_convolve_workspace_bytes(int64_t num_channels, int64_t num_frames, int64_t ir_channels, int64_t ir_frames);
+int flanhip_convolve(const float * audio, int64_t num_channels, int64_t num_frames, const float * ir, int64_t ir_channels, int64_t ir_frames,
+                     float sample_rate, int normalize, float * out, volatile int * cancel);
+int flanhip_convolve_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, const float * d_ir, int64_t ir_channels,
+                         int64_t ir_frames, float sample_rate, int normalize, float * d_out, void * d_workspace, void * stream);
+/* test hook: the partition P of the calling thread's convolutions (0: the library's choice).  A P other than a power of two from 128 to
+ * 4096 makes the calls FLANHIP_ERR_UNSUPPORTED (workspace 0).  Results do not depend on P beyond rounding. */
+void flanhip_convolve_debug_partition(int samples);
+
 /* ---- Audio::resample (Audio/AudioConversions.cpp:14-30, r8brain CDSPResampler with default parameters) --------- */
 /* AudioConversions.cpp:22: out frames = Frame( float(num_frames) * ( dst_rate / src_rate ) ) */
 int64_t flanhip_resample_out_frames(int64_t num_frames, float src_rate, float dst_rate);
