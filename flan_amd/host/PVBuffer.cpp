@@ -10,20 +10,17 @@
 #include <iostream>
 #include <utility>
 
-#include "device_block.h"
-
 namespace flan {
 
-PVBuffer::PVBuffer() : format(), buffer() {}
-PVBuffer::PVBuffer( const Format & other ) : format( other ), buffer( count() ) {}
-PVBuffer::PVBuffer( const std::string & filename ) : format(), buffer() { load( filename ); }
+PVBuffer::PVBuffer() : format() {}
+PVBuffer::PVBuffer( const Format & other ) : format( other ), mirror( "PV", false, std::vector<MF>( count() ) ) {}
+PVBuffer::PVBuffer( const std::string & filename ) : format() { load( filename ); }
 
 PVBuffer PVBuffer::adopt_device( const Format & f, std::shared_ptr<detail::DeviceBlock> block )
 	{
 	PVBuffer out;
 	out.format = f;
-	out.dev = std::move( block );
-	out.host_valid = false;
+	out.mirror.adopt( std::move( block ) );
 	return out;
 	}
 
@@ -31,15 +28,11 @@ PVBuffer PVBuffer::copy() const
 	{
 	PVBuffer out;
 	out.format = format;
-	out.buffer = get_buffer();
+	out.mirror = mirror.copy( count() );
 	return out;
 	}
 
-bool PVBuffer::is_null() const
-	{
-	auto held = lock.hold();
-	return count() == 0 || ( host_valid && buffer.empty() && !dev ) || format.sample_rate == 0;
-	}
+bool PVBuffer::is_null() const { return count() == 0 || mirror.holds_nothing() || format.sample_rate == 0; }
 
 bool PVBuffer::is_nan_or_inf() const
 	{
@@ -48,70 +41,10 @@ bool PVBuffer::is_nan_or_inf() const
 	return false;
 	}
 
-void PVBuffer::clear_buffer()
-	{
-	auto held = lock.hold();
-	buffer.assign( count(), MF{ 0.0f, 0.0f } );
-	host_valid = true;
-	dev.reset();
-	synth_ws.reset();
-	}
-
-const std::vector<MF> & PVBuffer::get_buffer() const
-	{
-	// const methods may run concurrently on one object (they are pure reads in the reference): the first one brings the data over
-	// under the object's lock, the others wait for it; once host_valid is set no const method touches the vector again
-	auto held = lock.hold();
-	if( !host_valid )
-		{
-		if( buffer.capacity() < count() )                // fresh memory: let every worker fault its share of the pages in, not this thread alone
-			{
-			buffer.reserve( count() );
-			detail::touch_pages( buffer.data(), sizeof( MF ) * count() );
-			}
-		buffer.resize( count() );
-		if( dev && count() && !detail::download_to_host( buffer.data(), dev->ptr, sizeof( MF ) * count() ) )
-			std::cerr << "flan: download of PV failed: " << flanhip_last_error() << std::endl;
-		host_valid = true;
-		}
-	return buffer;
-	}
-
-std::vector<MF> & PVBuffer::get_buffer()
-	{
-	std::as_const( *this ).get_buffer();
-	auto held = lock.hold();
-	dev.reset();
-	synth_ws.reset();                  // the caller may write: anything derived from the old data is stale
-	return buffer;
-	}
+void PVBuffer::clear_buffer() { mirror.clear( count(), &synth_ws ); }
 
 MF PVBuffer::get_MF( Channel c, Frame f, Bin b ) const { return get_buffer()[get_buffer_pos( c, f, b )]; }
 MF & PVBuffer::get_MF( Channel c, Frame f, Bin b ) { return get_buffer()[get_buffer_pos( c, f, b )]; }
-
-std::shared_ptr<detail::DeviceBlock> PVBuffer::device_block() const
-	{
-	auto held = lock.hold();
-	if( !dev )
-		{
-		if( count() == 0 ) return nullptr;
-		auto block = detail::DeviceBlock::allocate( sizeof( MF ) * count() );
-		if( !block ) return nullptr;
-		if( !detail::upload_from_host( block->ptr, buffer.data(), sizeof( MF ) * count() ) )
-			{
-			std::cerr << "flan: upload of PV failed: " << flanhip_last_error() << std::endl;
-			return nullptr;
-			}
-		dev = std::move( block );
-		}
-	return dev;
-	}
-
-const MF * PVBuffer::device_data() const
-	{
-	const auto block = device_block();
-	return block ? static_cast<const MF*>( block->ptr ) : nullptr;
-	}
 
 Magnitude PVBuffer::get_max_partial_magnitude() const
 	{
@@ -240,6 +173,7 @@ bool PVBuffer::load( const std::string & filename )
 	fmt.analysis_rate = FrameRate( h.hop_field );              // the reference reads the HOP field into analysis_rate (PVBuffer.cpp:245): kept
 	fmt.window_size = Frame( h.window_size );
 	*this = PVBuffer( fmt );
+	std::vector<MF> & buffer = get_buffer();
 
 	std::vector<uint8_t> packed( buffer.size() * 6 );
 	file.read( reinterpret_cast<char*>( packed.data() ), std::streamsize( packed.size() ) );

@@ -13,14 +13,14 @@ namespace flan { namespace detail {
 // so a block whose owner dies is idle); flanhip_malloc / flanhip_free only when the cache cannot serve.
 void * device_acquire( size_t bytes, size_t * capacity, int * device );   // nullptr on failure (flanhip_last_error() says why)
 void device_release( void * ptr, size_t capacity, int device ) noexcept;
-void device_cache_flush() noexcept;
+void device_cache_flush() noexcept;                   // give every idle block back to the device
 // Transfers between ordinary (pageable) host memory and the device (flanhip_download / flanhip_upload).  Synchronous.
 bool download_to_host( void * dst, const void * d_src, size_t bytes );
 bool upload_from_host( void * d_dst, const void * src, size_t bytes );
 void touch_pages( void * p, size_t bytes );                   // first touch of fresh memory on all workers (the kernel zeroes pages per toucher)
 
 struct CopyStreams { void * down = nullptr, * up = nullptr; };  // one per direction, created once; both null when creation failed
-CopyStreams copy_streams();                          // give every idle block back to the device
+CopyStreams copy_streams();
 
 struct DeviceBlock
 	{

@@ -9,11 +9,9 @@
 #include <vector>
 
 #include "flan/defines.h"
-#include "flan/mirror_lock.h"
+#include "flan/mirror.h"
 
 namespace flan {
-
-namespace detail { struct DeviceBlock; }
 
 class AudioBuffer
 	{
@@ -59,22 +57,19 @@ public:
 	bool is_nan_or_inf() const;                                                                                      // :58-64
 	Sample get_max_sample_magnitude( Second start_time = 0, Second end_time = 0 ) const;                             // :416-430
 	void print_summary() const;                                                                                      // :500-509
-	const std::vector<float> & get_buffer() const;                               // downloads from HBM on first use
-	std::vector<float> & get_buffer();                                           // ... and drops the device copy (host now owns the truth)
+	const std::vector<float> & get_buffer() const { return mirror.host( count() ); }   // downloads from HBM on first use
+	std::vector<float> & get_buffer() { return mirror.host( count() ); }               // ... and drops the device copy (host now owns the truth)
 
 	// ---- device residency (MI355X) ----
-	bool is_device_resident() const { auto held = lock.hold(); return bool( dev ); }
-	const float * device_data() const;                                           // uploads on first use; nullptr on failure
+	bool is_device_resident() const { return mirror.is_device_resident(); }
+	const float * device_data() const { return mirror.device_data( count() ); }  // uploads on first use; nullptr on failure
 	static AudioBuffer adopt_device( const Format &, std::shared_ptr<detail::DeviceBlock> );
-	std::shared_ptr<detail::DeviceBlock> device_block() const;                   // the shared handle on the HBM copy (uploads on first use)
+	std::shared_ptr<detail::DeviceBlock> device_block() const { return mirror.device_block( count() ); }   // the shared handle on the HBM copy (uploads on first use)
 
 protected:
 	size_t count() const { return size_t( format.num_channels ) * size_t( format.num_frames ); }
 	Format format;
-	mutable std::vector<float> buffer;
-	mutable bool host_valid = true;
-	mutable std::shared_ptr<detail::DeviceBlock> dev;
-	detail::MirrorLock lock;                       // guards buffer / host_valid / dev against concurrent const methods (mirror_lock.h)
+	detail::Mirror<float> mirror{ "audio" };       // the samples: host vector + HBM copy (mirror.h)
 	};
 
 } // namespace flan

@@ -9,11 +9,9 @@
 #include <vector>
 
 #include "flan/defines.h"
-#include "flan/mirror_lock.h"
+#include "flan/mirror.h"
 
 namespace flan {
-
-namespace detail { struct DeviceBlock; }
 
 class PVBuffer
 	{
@@ -67,8 +65,8 @@ public:
 
 	MF get_MF( Channel c, Frame f, Bin b ) const;
 	MF & get_MF( Channel c, Frame f, Bin b );
-	const std::vector<MF> & get_buffer() const;
-	std::vector<MF> & get_buffer();
+	const std::vector<MF> & get_buffer() const { return mirror.host( count() ); }
+	std::vector<MF> & get_buffer() { return mirror.host( count(), &synth_ws ); }
 
 	// the rest of the host-side accessors (PVBuffer.h:124,190-278): they work on the host copy (brought over on first use; the
 	// non-const ones make it the truth, like get_buffer())
@@ -88,32 +86,29 @@ public:
 	void print_summary() const;                                                                                      // :327-330, :535-548
 
 	// ---- device residency (MI355X) ----
-	bool is_device_resident() const { auto held = lock.hold(); return bool( dev ); }
-	const MF * device_data() const;
-	bool host_copy_is_current() const { auto held = lock.hold(); return host_valid; }                                             // false: the data lives on the device only
+	bool is_device_resident() const { return mirror.is_device_resident(); }
+	const MF * device_data() const { return mirror.device_data( count() ); }
+	bool host_copy_is_current() const { return mirror.host_copy_is_current(); }                          // false: the data lives on the device only
 	static PVBuffer adopt_device( const Format &, std::shared_ptr<detail::DeviceBlock> );
 	/** convert_to_PV leaves convert_to_audio's pre-pass (per-chain phase sums, in a synthesis workspace) next to the data; it is
 	 *  valid while the data is untouched and is consumed by the first convert_to_audio (flanhip_*_fused in flanhip.h). */
 	void attach_synthesis_workspace( std::shared_ptr<detail::DeviceBlock> ws, bool maybe = false ) const
-		{ auto held = lock.hold(); synth_ws = std::move( ws ); synth_ws_maybe = maybe; }
+		{ auto held = mirror.hold(); synth_ws = std::move( ws ); synth_ws_maybe = maybe; }
 	std::shared_ptr<detail::DeviceBlock> take_synthesis_workspace() const                                // one caller gets it, every other one nullptr
-		{ auto held = lock.hold(); auto w = std::move( synth_ws ); synth_ws.reset(); return w; }
+		{ auto held = mirror.hold(); auto w = std::move( synth_ws ); synth_ws.reset(); return w; }
 	/** true: the workspace MAY hold the pre-pass (left by modify_time / stretch, whose time map decides on the device):
 	 *  convert_to_audio then goes through flanhip_synthesize_dev_fused_checked */
-	bool synthesis_workspace_is_conditional() const { auto held = lock.hold(); return synth_ws_maybe; }
+	bool synthesis_workspace_is_conditional() const { auto held = mirror.hold(); return synth_ws_maybe; }
 	/** the shared handle on the HBM copy (uploads on first use; empty on failure): keeps the block alive for as long as a caller works on it,
 	 *  whatever other threads do to this object meanwhile */
-	std::shared_ptr<detail::DeviceBlock> device_block() const;
+	std::shared_ptr<detail::DeviceBlock> device_block() const { return mirror.device_block( count() ); }
 
 protected:
 	size_t count() const { return size_t( format.num_channels ) * size_t( format.num_frames ) * size_t( format.num_bins ); }
 	Format format;
-	mutable std::vector<MF> buffer;
-	mutable bool host_valid = true;
-	mutable std::shared_ptr<detail::DeviceBlock> dev;
-	mutable std::shared_ptr<detail::DeviceBlock> synth_ws;
+	detail::Mirror<MF> mirror{ "PV" };             // the data: host vector + HBM copy (mirror.h)
+	mutable std::shared_ptr<detail::DeviceBlock> synth_ws;   // guarded by mirror.hold(); dropped whenever the host copy may be written
 	mutable bool synth_ws_maybe = false;
-	detail::MirrorLock lock;                       // guards buffer / host_valid / dev / synth_ws against concurrent const methods (mirror_lock.h)
 	};
 
 } // namespace flan

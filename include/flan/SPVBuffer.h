@@ -8,11 +8,9 @@
 #include <vector>
 
 #include "flan/defines.h"
-#include "flan/mirror_lock.h"
+#include "flan/mirror.h"
 
 namespace flan {
-
-namespace detail { struct DeviceBlock; }
 
 class SPVBuffer
 	{
@@ -53,24 +51,20 @@ public:
 
 	MF get_MF( Channel c, Frame f, Bin b ) const;
 	MF & get_MF( Channel c, Frame f, Bin b );
-	const std::vector<MF> & get_buffer() const;                                  // downloads from HBM on first use
-	std::vector<MF> & get_buffer();                                              // ... and drops the device copy (the host owns the truth)
+	const std::vector<MF> & get_buffer() const { return mirror.host( count() ); }   // downloads from HBM on first use
+	std::vector<MF> & get_buffer() { return mirror.host( count() ); }               // ... and drops the device copy (the host owns the truth)
 
 	// ---- device residency (MI355X) ----
-	bool is_device_resident() const { auto held = lock.hold(); return bool( dev ); }
-	bool host_copy_is_current() const { auto held = lock.hold(); return host_valid; }
-	const MF * device_data() const;                                              // uploads on first use; nullptr on failure
-	std::shared_ptr<detail::DeviceBlock> device_block() const;
+	bool is_device_resident() const { return mirror.is_device_resident(); }
+	bool host_copy_is_current() const { return mirror.host_copy_is_current(); }
+	const MF * device_data() const { return mirror.device_data( count() ); }     // uploads on first use; nullptr on failure
+	std::shared_ptr<detail::DeviceBlock> device_block() const { return mirror.device_block( count() ); }
 	static SPVBuffer adopt_device( const Format &, std::shared_ptr<detail::DeviceBlock> );
 
 protected:
 	size_t count() const { return size_t( format.num_channels ) * size_t( format.num_frames ) * size_t( format.num_bins ); }
-	void materialize_locked() const;                                             // the host copy, whole (lock held)
 	Format format;
-	mutable std::vector<MF> buffer;
-	mutable bool host_valid = true;                // with an empty buffer: all zeros, not yet allocated
-	mutable std::shared_ptr<detail::DeviceBlock> dev;
-	detail::MirrorLock lock;
+	detail::Mirror<MF> mirror{ "SPV", true };      // the data: host vector + HBM copy (mirror.h); zeros are not allocated until touched
 	};
 
 } // namespace flan

@@ -400,7 +400,7 @@ static void device_checks()
 				&& std::memcmp( alone[size_t( t )].data(), together[size_t( t )].data(), sizeof( float ) * alone[size_t( t )].size() ) == 0 );
 		}
 	// ---- const methods of ONE object from several threads (pure reads in the reference): lazy download / upload and the workspace
-	//      hand-over are guarded by the object's lock (mirror_lock.h) -- every thread gets the single-threaded answer
+	//      hand-over are guarded by the object's lock (mirror.h) -- every thread gets the single-threaded answer
 		{
 		Audio x = noise( 2, 60000, 911 );
 		const PV shared_pv = x.convert_to_PV( 2048, 512, 2048 );                       // device resident, pre-pass attached, host copy not yet made
