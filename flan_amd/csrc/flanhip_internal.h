@@ -29,6 +29,22 @@ void set_error( const char * fmt, ... );
 
 int require_device();   // FLANHIP_OK or FLANHIP_ERR_NO_DEVICE
 
+static constexpr size_t kMaxLds = 160 * 1024;   // gfx950: 160 KiB LDS per CU, one workgroup may take all of it
+// One kernel launch on a one-dimensional grid (who: the caller's __func__, for the message): refuses what the LDS or a grid cannot hold, raises the
+// kernel's dynamic-LDS limit on every launch that has dynamic LDS, launches and checks.
+template<typename K, typename... Args>
+int launch_kernel( const char * who, K kern, int64_t blocks, int threads, size_t lds, hipStream_t s, const Args &... args )
+	{
+	if( lds > kMaxLds ) { set_error( "%s: %s", who, "window/dft too large for LDS" ); return FLANHIP_ERR_UNSUPPORTED; }
+	if( blocks >= ( int64_t( 1 ) << 31 ) ) { set_error( "%s: %s", who, "too many chains for one launch" ); return FLANHIP_ERR_UNSUPPORTED; }
+	if( lds ) FLANHIP_CHECK( hipFuncSetAttribute( reinterpret_cast<const void*>( kern ), hipFuncAttributeMaxDynamicSharedMemorySize, int( lds ) ) );
+	hipLaunchKernelGGL( kern, dim3( (unsigned) blocks ), dim3( (unsigned) threads ), lds, s, args... );
+	FLANHIP_CHECK( hipGetLastError() );
+	return FLANHIP_OK;
+	}
+// a typed pointer `offset` bytes into a workspace
+template<typename T> T * ws_at( void * d_ws, size_t offset ) { return reinterpret_cast<T*>( static_cast<char*>( d_ws ) + offset ); }
+
 inline bool is_pow2( int64_t n ) { return n > 0 && ( n & ( n - 1 ) ) == 0; }
 inline int ilog2( int64_t n ) { int l = 0; while( ( int64_t( 1 ) << l ) < n ) ++l; return l; }
 inline bool cancelled( volatile int * c ) { return c && *c != 0; }
@@ -86,7 +102,7 @@ DebugOptions & debug_options();
 bool force_generic();
 int cu_count();         // compute units of the current device
 
-// Launchers implemented in analyze.hip / synthesize.hip / processors.hip
+// Launchers implemented in conversions.hip (which routes every shape to its kernel family; the team and sub families' kernels are launched from team.hip / sub.hip)
 // d_fused_ws (optional): a synthesis workspace for the PV being produced; analysis leaves the per-chain phase sums and a NaN flag
 // there so that launch_synthesize( ..., presummed = true ) can skip its pre-pass.
 int launch_analyze( const float * d_audio, int64_t ch, int64_t n, float sr, int W, int hop, int dft, flanhip_MF * d_out, void * d_fused_ws, hipStream_t s );

@@ -43,13 +43,8 @@ static int launch_analyze_sub( const AnalyzeParams & p, hipStream_t s )
 	FLANHIP_REQUIRE( ( int64_t( NCH ) * p.L + 2 ) * std::max( int64_t( p.hop ) * 4, int64_t( ( L::C + 1 ) * 8 ) ) < ( int64_t( 1 ) << 32 ), FLANHIP_ERR_UNSUPPORTED, "chain length x hop too large for the dft 512 / 256 kernels" );
 	const size_t lds = L::bytes( kSubWaves, true );
 	static_assert( L::bytes( kSubWaves, true ) * kSubOcc <= 160 * 1024, "LDS budget" );
-	auto kern = k_analyze_sub<LOG2C, LP, kSubWaves, SUMS, kSubOcc, kSubNv>;
-	FLANHIP_CHECK( hipFuncSetAttribute( reinterpret_cast<const void*>( kern ), hipFuncAttributeMaxDynamicSharedMemorySize, int( lds ) ) );
 	const int64_t blocks = int64_t( ( p.chains_per_channel + NCH - 1 ) / NCH ) * p.num_channels;
-	FLANHIP_REQUIRE( blocks < ( int64_t( 1 ) << 31 ), FLANHIP_ERR_UNSUPPORTED, "too many chains for one launch" );
-	hipLaunchKernelGGL( kern, dim3( (unsigned) blocks ), dim3( 64 * kSubWaves ), lds, s, p );
-	FLANHIP_CHECK( hipGetLastError() );
-	return FLANHIP_OK;
+	return launch_kernel( __func__, k_analyze_sub<LOG2C, LP, kSubWaves, SUMS, kSubOcc, kSubNv>, blocks, 64 * kSubWaves, lds, s, p );
 	}
 
 int run_analyze_sub( const AnalyzeParams & p, int dft, hipStream_t s )
@@ -68,13 +63,8 @@ static int launch_synth_sub( const SynthParams & p, hipStream_t s )
 	constexpr int NCH = kSubWaves * L::G;
 	FLANHIP_REQUIRE( ( int64_t( NCH ) * p.L + 2 ) * ( ( L::C + 1 ) * 8 ) < ( int64_t( 1 ) << 32 ), FLANHIP_ERR_UNSUPPORTED, "chain length too large for the dft 512 / 256 kernels" );
 	const size_t lds = L::bytes( kSubWaves, false );
-	auto kern = k_synthesize_sub<LOG2C, LP, kSubWaves, HOPQ, kSubOcc>;
-	FLANHIP_CHECK( hipFuncSetAttribute( reinterpret_cast<const void*>( kern ), hipFuncAttributeMaxDynamicSharedMemorySize, int( lds ) ) );
 	const int64_t blocks = int64_t( ( p.chains_per_channel + NCH - 1 ) / NCH ) * p.num_channels;
-	FLANHIP_REQUIRE( blocks < ( int64_t( 1 ) << 31 ), FLANHIP_ERR_UNSUPPORTED, "too many chains for one launch" );
-	hipLaunchKernelGGL( kern, dim3( (unsigned) blocks ), dim3( 64 * kSubWaves ), lds, s, p );
-	FLANHIP_CHECK( hipGetLastError() );
-	return FLANHIP_OK;
+	return launch_kernel( __func__, k_synthesize_sub<LOG2C, LP, kSubWaves, HOPQ, kSubOcc>, blocks, 64 * kSubWaves, lds, s, p );
 	}
 
 template<int LOG2C, int LP>

@@ -58,13 +58,8 @@ static int launch_analyze_team( const AnalyzeParams & p, const TeamTables & tb, 
 	using L = TeamLds<R, TEAMS, WINLDS ? 64 * R * WQ : 0>;
 	const size_t lds = L::bytes();
 	static_assert( L::bytes() + 64 <= 160 * 1024, "LDS budget" );
-	auto kern = k_analyze_team<R, TEAMS, WQ, SUMS, WINLDS>;
-	FLANHIP_CHECK( hipFuncSetAttribute( reinterpret_cast<const void*>( kern ), hipFuncAttributeMaxDynamicSharedMemorySize, int( lds ) ) );
 	const int64_t chains = int64_t( ( p.chains_per_channel + TEAMS - 1 ) / TEAMS ) * p.num_channels;       // a block = a group of TEAMS chains of one channel
-	FLANHIP_REQUIRE( chains < ( int64_t( 1 ) << 31 ), FLANHIP_ERR_UNSUPPORTED, "too many chains for one launch" );
-	hipLaunchKernelGGL( kern, dim3( (unsigned) chains ), dim3( 64 * R * TEAMS ), lds, s, p, tb );
-	FLANHIP_CHECK( hipGetLastError() );
-	return FLANHIP_OK;
+	return launch_kernel( __func__, k_analyze_team<R, TEAMS, WQ, SUMS, WINLDS>, chains, 64 * R * TEAMS, lds, s, p, tb );
 	}
 
 template<int R, int WQ, int HS>
@@ -75,13 +70,8 @@ static int launch_synth_team( const SynthParams & p, const TeamTables & tb, hipS
 	using L = TeamLds<R, TEAMS, WINLDS ? 64 * R * WQ : 0>;
 	const size_t lds = L::bytes();
 	static_assert( L::bytes() + 64 <= 160 * 1024, "LDS budget" );
-	auto kern = k_synthesize_team<R, TEAMS, WQ, HS, WINLDS>;
-	FLANHIP_CHECK( hipFuncSetAttribute( reinterpret_cast<const void*>( kern ), hipFuncAttributeMaxDynamicSharedMemorySize, int( lds ) ) );
 	const int64_t chains = int64_t( ( p.chains_per_channel + TEAMS - 1 ) / TEAMS ) * p.num_channels;
-	FLANHIP_REQUIRE( chains < ( int64_t( 1 ) << 31 ), FLANHIP_ERR_UNSUPPORTED, "too many chains for one launch" );
-	hipLaunchKernelGGL( kern, dim3( (unsigned) chains ), dim3( 64 * R * TEAMS ), lds, s, p, tb );
-	FLANHIP_CHECK( hipGetLastError() );
-	return FLANHIP_OK;
+	return launch_kernel( __func__, k_synthesize_team<R, TEAMS, WQ, HS, WINLDS>, chains, 64 * R * TEAMS, lds, s, p, tb );
 	}
 
 template<int R>
