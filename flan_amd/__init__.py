@@ -136,6 +136,11 @@ _SIGS = {
     "flanhip_convolve": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _f32, _i32, _vp, _vp]),
     "flanhip_convolve_dev": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _f32, _i32, _vp, _vp, _vp]),
     "flanhip_convolve_debug_partition": (None, [_i32]),
+    "flanhip_audio_repitch_out_frames": (_i64, [_vp, _i64, _i64]),
+    "flanhip_audio_repitch_plan": (_i64, [_i64, _f32, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "flanhip_audio_repitch_workspace_bytes": (C.c_size_t, [_i64, _f32, _vp, _i64, _i64, _i32]),
+    "flanhip_audio_repitch": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _i64, _i64, _i32, _vp, _vp]),
+    "flanhip_audio_repitch_dev": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
 }
 
 EXPORTS = sorted(_SIGS)
@@ -731,3 +736,56 @@ class convolve_partition_forced:
     def __exit__(self, *exc):
         lib.flanhip_convolve_debug_partition(0)
         return False
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Audio::repitch: variable-rate sinc resampling (inv_factors: the sampled factor already inverted and clamped)
+# ---------------------------------------------------------------------------------------------------------------
+
+REPITCH_SINC, REPITCH_LINEAR, REPITCH_UNINTERPOLATED = 0, 1, 2
+
+
+def audio_repitch_out_frames(inv_factors, granularity_frames):
+    inv = np.ascontiguousarray(inv_factors, np.float32)
+    return int(lib.flanhip_audio_repitch_out_frames(_ptr(inv), inv.size, granularity_frames))
+
+
+def audio_repitch_plan(num_frames, sample_rate, inv_factors, granularity_frames, quality=REPITCH_SINC):
+    """The block loop on the host: a dict of per-block arrays (offset, fracpos, ratio, filtpos, oversize, ideal, first_out, wanted) and
+    out_frames."""
+    inv = np.ascontiguousarray(inv_factors, np.float32)
+    nout = _i64(0)
+    blocks = lib.flanhip_audio_repitch_plan(num_frames, sample_rate, _ptr(inv), inv.size, granularity_frames, quality, 0,
+                                            None, None, None, None, None, None, None, None, C.byref(nout))
+    if blocks < 0:
+        check(int(blocks))
+    p = {"offset": np.empty(blocks, np.int64), "fracpos": np.empty(blocks, np.float64), "ratio": np.empty(blocks, np.float64),
+         "filtpos": np.empty(blocks, np.float64), "oversize": np.empty(blocks, np.int32), "ideal": np.empty(blocks, np.int32),
+         "first_out": np.empty(blocks, np.int64), "wanted": np.empty(blocks, np.int32)}
+    got = lib.flanhip_audio_repitch_plan(num_frames, sample_rate, _ptr(inv), inv.size, granularity_frames, quality, blocks,
+                                         _ptr(p["offset"]), _ptr(p["fracpos"]), _ptr(p["ratio"]), _ptr(p["filtpos"]), _ptr(p["oversize"]),
+                                         _ptr(p["ideal"]), _ptr(p["first_out"]), _ptr(p["wanted"]), C.byref(nout))
+    assert got == blocks
+    p["out_frames"] = int(nout.value)
+    return p
+
+
+def audio_repitch_workspace_bytes(num_frames, sample_rate, inv_factors, granularity_frames, quality=REPITCH_SINC):
+    inv = np.ascontiguousarray(inv_factors, np.float32)
+    return int(lib.flanhip_audio_repitch_workspace_bytes(num_frames, sample_rate, _ptr(inv), inv.size, granularity_frames, quality))
+
+
+def audio_repitch(audio, sample_rate, inv_factors, granularity_frames, quality=REPITCH_SINC):
+    """Audio::repitch after the factor has been sampled, inverted and clamped.  audio float32 [ch][n] -> float32 [ch][out_frames]."""
+    audio = np.ascontiguousarray(audio, np.float32)
+    inv = np.ascontiguousarray(inv_factors, np.float32)
+    ch, n = audio.shape
+    out = np.empty((ch, max(audio_repitch_out_frames(inv, granularity_frames), 0)), np.float32)
+    check(lib.flanhip_audio_repitch(_ptr(audio), ch, n, sample_rate, _ptr(inv), inv.size, granularity_frames, quality, _ptr(out), None))
+    return out
+
+
+def audio_repitch_dev(d_audio, ch, n, sample_rate, inv_factors, granularity_frames, quality, d_out, d_ws, stream=None):
+    inv = np.ascontiguousarray(inv_factors, np.float32)
+    check(lib.flanhip_audio_repitch_dev(_dp(d_audio), ch, n, sample_rate, _ptr(inv), inv.size, granularity_frames, quality, _dp(d_out),
+                                        _dp(d_ws), _vp(stream or 0)))

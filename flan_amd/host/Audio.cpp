@@ -1,8 +1,10 @@
 // Audio.cpp -- construction and conversions of flan::Audio over the C ABI
 // (reference: src/flan/Audio/AudioConstructors.cpp, Conversions/AudioPV.cpp:12-84, Audio/AudioConversions.cpp:14-56,
-// Audio/AudioCombination.cpp:299-352).
+// Audio/AudioCombination.cpp:299-352, Audio/AudioTemporal.cpp:236-299).
 #include "flan/Audio.h"
 
+#include <algorithm>
+#include <cmath>
 #include <iostream>
 
 #include "device_block.h"
@@ -153,6 +155,48 @@ Audio Audio::convolve( const Audio & ir, bool normalize ) const
 		get_sample_rate(), normalize ? 1 : 0, static_cast<float*>( block->ptr ), ws->ptr, nullptr );
 	if( !detail::report( rc, "convolve" ) ) return Audio::create_null();
 	if( !detail::report( flanhip_stream_synchronize( nullptr ), "convolve" ) ) return Audio::create_null();   // the workspace goes back idle
+	return AudioBuffer::adopt_device( f, std::move( block ) );
+	}
+
+Audio Audio::repitch( const Function<Second, float> & factor, Second granularity, WDLResampleType quality ) const
+	{
+	if( is_null() ) return Audio::create_null();                // AudioTemporal.cpp:238
+	if( quality == WDLResampleType::Linear )
+		{
+		std::cout << "Audio::repitch: the Linear quality is not built (Sinc and Uninterpolated are)." << std::endl;
+		return Audio();
+		}
+	Frame g = Frame( time_to_frame( granularity ) );            // :241-242
+	if( g < 1 ) g = 1;
+	const int count = int( std::ceil( get_num_frames() / float( g ) ) );       // :245
+	const auto sampled = factor.sample( 0, count, granularity );
+	std::vector<float> inv( size_t( std::max( count, 0 ) ) );
+	for( size_t i = 0; i < inv.size(); ++i )                     // :246-249, in fp32
+		{
+		const float v = sampled.is_constant() ? sampled.get_constant() : sampled.get_vector()[i];
+		inv[i] = std::clamp( 1.0f / v, 1.0f / 1000.0f, 1000.0f );
+		}
+	const int q = quality == WDLResampleType::Sinc ? FLANHIP_REPITCH_SINC : FLANHIP_REPITCH_UNINTERPOLATED;
+	AudioBuffer::Format f = get_format();                        // :252-256
+	f.num_frames = Frame( flanhip_audio_repitch_out_frames( inv.data(), int64_t( inv.size() ), g ) );
+	const size_t ws_bytes = flanhip_audio_repitch_workspace_bytes( get_num_frames(), get_sample_rate(), inv.data(), int64_t( inv.size() ), g, q );
+	if( f.num_frames <= 0 || ws_bytes == 0 )
+		{
+		std::cerr << "flan: repitch refused: " << get_num_channels() << " x " << get_num_frames() << ", granularity " << g << " frames: ";
+		if( f.num_frames <= 0 ) std::cerr << "no output frames";              // (the length function sets no error text)
+		else std::cerr << flanhip_last_error();
+		std::cerr << std::endl;
+		return Audio::create_null();
+		}
+	const float * d_x = device_data();
+	if( !d_x ) return Audio::create_null();
+	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( f.num_channels ) * size_t( f.num_frames ) );
+	auto ws = detail::DeviceBlock::allocate( ws_bytes );
+	if( !block || !ws ) return Audio::create_null();
+	const int rc = flanhip_audio_repitch_dev( d_x, get_num_channels(), get_num_frames(), get_sample_rate(), inv.data(), int64_t( inv.size() ), g, q,
+		static_cast<float*>( block->ptr ), ws->ptr, nullptr );
+	if( !detail::report( rc, "repitch" ) ) return Audio::create_null();
+	if( !detail::report( flanhip_stream_synchronize( nullptr ), "repitch" ) ) return Audio::create_null();     // the workspace goes back idle
 	return AudioBuffer::adopt_device( f, std::move( block ) );
 	}
 

@@ -4,12 +4,16 @@
 #include <vector>
 
 #include "flan/AudioBuffer.h"
+#include "flan/Function.h"
 #include "flan/defines.h"
 
 namespace flan {
 
 class PV;
 class SPV;
+
+/** The modes of WDL_Resampler that Audio::repitch offers (Audio/Audio.h:439-455, AudioTemporal.cpp:258-261). */
+enum class WDLResampleType { Sinc, Linear, Uninterpolated };
 
 class Audio : public AudioBuffer
 	{
@@ -49,6 +53,12 @@ public:
 	 *  normalize: the result times 1.0f / get_max_sample_magnitude(), so an all-zero result becomes NaN everywhere (0 * inf), as in the
 	 *  reference.  The result stays device-resident until read. */
 	Audio convolve( const Audio & ir, bool normalize = true ) const;
+	/** Pitch and speed changed together by resampling at a rate that changes every `granularity` seconds (Audio/AudioTemporal.cpp:236-299,
+	 *  over WDL_Resampler), on the device (flanhip_audio_repitch_dev).  factor is sampled once per granularity (at least one
+	 *  frame) with Function::sample, each value becomes clamp( 1.0f / v, 1.0f / 1000, 1000 ); a constant behaves like the callable that returns
+	 *  it.  Sinc: 64-tap windowed sinc; Uninterpolated: the nearest earlier sample; Linear is not built: a null Audio and one line on std::cout.
+	 *  A null *this gives a null Audio.  The result stays device-resident until read. */
+	Audio repitch( const Function<Second, float> & factor, Second granularity = .001f, WDLResampleType quality = WDLResampleType::Sinc ) const;
 
 	// the older camelCase spellings BASELINE.json's north_star uses
 	PV convertToPV( Frame window_size = 2048, Frame hop = 128, Frame dft_size = 4096, flan_CANCEL_ARG ) const;

@@ -457,6 +457,50 @@ int flanhip_convolve_dev(const float * d_audio, int64_t num_channels, int64_t nu
  * 4096 makes the calls FLANHIP_ERR_UNSUPPORTED (workspace 0).  Results do not depend on P beyond rounding. */
 void flanhip_convolve_debug_partition(int samples);
 
+/* ---- Audio::repitch: variable-rate sinc resampling (Audio/AudioTemporal.cpp:236-299 over WDL_Resampler, WDL/resample.cpp) ------ */
+/* (the family is flanhip_audio_repitch_*: flanhip_repitch_dev is PV::repitch, above.)
+ * audio: float[ch][n]; inv_factors: float[count], one per granularity_frames input frames, ALREADY inverted and clamped by the caller
+ * ( clamp( 1.0f / factor, 1.0f / 1000, 1000 ), AudioTemporal.cpp:246-249: the C++ layer's job, Audio::repitch ); out: float[ch][out_frames].
+ * Block b of the reference's loop (:267-296) resamples at rate ratio = sr / ( sr * inv_factors[ floor( in_frame / float( g ) ) ] ) and
+ * delivers g output frames.  The hand-over between blocks -- the fractional read position and the samples that stay buffered -- is
+ * reproduced exactly by a host loop in fp64 (flanhip_audio_repitch_plan; one addition per output frame); the samples are computed on the
+ * device, one 2 x 64-tap sum each (1 x 64 where the rates are "ideal", :1095-1141) against a Blackman-Harris x sinc table the kernel builds
+ * per run of blocks with the same ( filtpos, oversize ) (:1157-1202).  Products are fp32, sums fp64 in tap order, as in the SincSample
+ * templates (:106-257).  Within a block the read position is fma( j, ratio, fracpos ), not j additions.  Numerics: within a few fp32 ulps of
+ * the reference; deterministic (two calls agree bit for bit).  Output frames past the last block stay 0; frames past
+ * out_frames are dropped.  Any channel count (the reference hangs above 64, :1220).
+ * quality: FLANHIP_REPITCH_SINC (SetMode( true, 0, true, 64 )), FLANHIP_REPITCH_UNINTERPOLATED (SetMode( false, 0, false ): in[ int( srcpos ) ]);
+ * FLANHIP_REPITCH_LINEAR (a time-varying biquad across the whole stream, :1276-1292, :1529-1543) is FLANHIP_ERR_UNSUPPORTED: not built.
+ * Null pointers, non-positive sizes, sample_rate <= 0, an unknown quality and a count smaller than the loop needs are
+ * FLANHIP_ERR_INVALID_ARG, before any device call.  A call whose loop would run more than 2^22 blocks (56 bytes of record each, on the
+ * host and in the workspace; 70 minutes of output at 1 ms blocks) or 2^33 additions is FLANHIP_ERR_UNSUPPORTED, before anything is
+ * allocated for it beyond the records counted so far. */
+#define FLANHIP_REPITCH_SINC 0
+#define FLANHIP_REPITCH_LINEAR 1
+#define FLANHIP_REPITCH_UNINTERPOLATED 2
+/* AudioTemporal.cpp:252: ceil( accumulate( inv_factors ) * g ), the sum sequential in fp32 (FunctionSample.h:136-148), the product fp32; 0 for
+ * arguments it refuses */
+int64_t flanhip_audio_repitch_out_frames(const float * inv_factors, int64_t count, int64_t granularity_frames);
+/* The block loop alone (host arithmetic, no device): returns the number of blocks (or a negative FLANHIP_ERR_*) and fills the first
+ * `capacity` records of every array that is not null: the stream index of the resampler buffer's first sample (the stream: 31 zeros -- none
+ * for UNINTERPOLATED --, the input, zeros), srcpos of the block's first output frame relative to it, the ratio, the table's filtpos /
+ * oversize / ideal flag (:1095-1141, :1327-1328), the block's first output frame, and what ResamplePrepare asks for (:1241).  *out_frames:
+ * flanhip_audio_repitch_out_frames. */
+int64_t flanhip_audio_repitch_plan(int64_t num_frames, float sample_rate, const float * inv_factors, int64_t count, int64_t granularity_frames,
+                                   int quality, int64_t capacity, int64_t * offsets, double * fracpos, double * ratio, double * filtpos,
+                                   int32_t * oversize, int32_t * ideal, int64_t * first_out, int32_t * wanted, int64_t * out_frames);
+/* bytes of device workspace flanhip_audio_repitch_dev needs (host arithmetic: it runs the plan; 0 for arguments it refuses): the window
+ * factors (64 x 2080 doubles), 56 bytes per block and 40 per run */
+size_t flanhip_audio_repitch_workspace_bytes(int64_t num_frames, float sample_rate, const float * inv_factors, int64_t count,
+                                             int64_t granularity_frames, int quality);
+/* `cancel` is polled before the upload and before the launch; the kernels run to the end once launched. */
+int flanhip_audio_repitch(const float * audio, int64_t num_channels, int64_t num_frames, float sample_rate, const float * inv_factors,
+                          int64_t count, int64_t granularity_frames, int quality, float * out, volatile int * cancel);
+/* d_audio / d_out: device memory; inv_factors: HOST memory (the plan runs on the host).  The workspace need not be cleared.  The plan's
+ * records go up before the launch and the stream is synchronised once for that. */
+int flanhip_audio_repitch_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, float sample_rate, const float * inv_factors,
+                              int64_t count, int64_t granularity_frames, int quality, float * d_out, void * d_workspace, void * stream);
+
 /* ---- Audio::resample (Audio/AudioConversions.cpp:14-30, r8brain CDSPResampler with default parameters) --------- */
 /* AudioConversions.cpp:22: out frames = Frame( float(num_frames) * ( dst_rate / src_rate ) ) */
 int64_t flanhip_resample_out_frames(int64_t num_frames, float src_rate, float dst_rate);

@@ -1,0 +1,295 @@
+"""Audio::repitch (Audio/AudioTemporal.cpp:236-299 over WDL_Resampler, WDL/resample.cpp) restated in Python: the block plan, the
+low-pass table and the tap sums, in the reference's own operation order.  The plan and the table run in scalar Python (math.sin /
+math.cos: the libm the reference calls); the tap sums are numpy fp32 products accumulated in fp64 in tap order.  DESIGN.md 4.13.
+
+Also an fp64 "smooth truth" for constant factors: the same windowed sinc evaluated at the exact fractional position, all in fp64."""
+import math
+import os
+
+import numpy as np
+
+F32 = np.float32
+SINC, LINEAR, UNINTERPOLATED = 0, 1, 2
+SINC_SIZE, SINC_OVERSIZE = 64, 32                       # SetMode( true, 0, true, 64 ): 64 taps, 32 slices unless the rates are "ideal"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_made", "wdl_repitch.npz")
+
+
+def invert(factors):
+    """:246-249 in fp32: clamp( 1.0f / v, 1.0f / 1000.0f, 1000.0f )"""
+    with np.errstate(divide="ignore"):
+        inv = F32(1.0) / np.asarray(factors, F32)
+    return np.clip(inv, F32(1.0) / F32(1000.0), F32(1000.0)).astype(F32)
+
+
+def granularity_frames(granularity_seconds, sr):
+    return max(int(F32(granularity_seconds) * F32(sr)), 1)                 # :241-242
+
+
+def factor_count(n, g):
+    return int(np.ceil(F32(n) / F32(g)))                                    # :245
+
+
+def out_frames(inv, g):
+    """:252: FunctionSample<float>::accumulate() of a vector is a sequential fp32 sum; the product and the ceil are fp32 too"""
+    s = F32(0.0)
+    for v in np.asarray(inv, F32):
+        s = F32(s + v)
+    return int(np.ceil(F32(s * F32(g))))
+
+
+def rates(sr, inv):
+    """SetRates (:1080-1090) as Audio::repitch calls it: ( rate in, rate out, ratio ), both rates at least 1"""
+    rate_in = max(float(F32(sr)), 1.0)
+    rate_out = max(float(F32(sr)) * float(F32(inv)), 1.0)
+    return rate_in, rate_out, rate_in / rate_out
+
+
+def table_shape(rate_in, rate_out, ratio):
+    """BuildLowPass's first half (:1095-1141): ( filtpos, oversize, ideal )"""
+    filtpos = 1.0 / (ratio * 1.03) if ratio > 1.0 else 1.0                  # :1327-1328
+    want, ideal_interp = SINC_OVERSIZE, 0
+    if ratio < 1.0:
+        drat = rate_out / rate_in
+        irat = int(drat + 0.5)
+        if irat > 1 and irat == drat:
+            ideal_interp = irat
+    else:
+        irat = int(ratio + 0.5)
+        if ratio == irat:
+            ideal_interp = 1
+    if not ideal_interp and rate_in < 2147483648.0 and rate_out < 2147483648.0:
+        in1, out1 = int(rate_in), int(rate_out)
+        if out1 > 0 and in1 > 0 and rate_in == in1 and rate_out == out1:
+            min_cd = max(out1 // (2 * want), 1)
+            n1, n2 = out1, in1
+            while n2 >= min_cd:
+                n1, n2 = n2, n1 % n2
+            if not n2:
+                ideal_interp = out1 // n1
+    if 0 < ideal_interp <= want * 2:
+        want = ideal_interp
+    return filtpos, want, ideal_interp == want
+
+
+def plan(n, sr, inv, g, quality=SINC):
+    """The block loop (:267-296 with ResamplePrepare :1218-1265 and ResampleOut's state hand-over :1313, :1558-1566) in fp64, with the
+    reference's chain of srcpos += ratio additions.  One dict per block:
+        offset     stream index of the buffer's first sample (the stream: `prelude` zeros, the input, zeros)
+        fracpos    srcpos at the block's first output sample, relative to `offset`
+        ratio, filtpos, oversize, ideal, first_out, wanted
+    It asserts what the arithmetic promises: every block delivers all g samples, S never drops below the prelude again, and the buffer
+    is a window of one continuous stream."""
+    inv = np.asarray(inv, F32)
+    fsize = SINC_SIZE if quality == SINC else 0
+    prelude = fsize // 2 - 1 if fsize else 0
+    blocks = []
+    fracpos, S, in_frame, out_frame, offset, first = 0.0, 0, 0, 0, 0, True
+    while in_frame < n:
+        index = int(np.floor(F32(in_frame) / F32(g)))                       # :271, the fp32 quotient
+        assert index < inv.size, "count is smaller than the loop needs"
+        rate_in, rate_out, ratio = rates(sr, inv[index])
+        if fsize // 2 > 1 and S < fsize // 2 - 1:                           # :1226-1237
+            assert first, "the prelude is written once: S never drops below it again"
+            S = fsize // 2 - 1
+        first = False
+        wanted = max(int(ratio * g) + 4 + fsize - S, 0)                     # :1241-1244
+        S += wanted                                                         # :1295
+        assert offset + S == prelude + in_frame + wanted, "the buffer is a window of one continuous stream"
+        if fsize:
+            filtpos, oversize, ideal = table_shape(rate_in, rate_out, ratio)
+            limit = S - fsize - 1                                           # ipos >= filtlen - 1 ends the block early (:1343)
+        else:
+            filtpos, oversize, ideal = 1.0, 1, False
+            limit = S                                                       # :1425
+        blocks.append(dict(offset=offset, fracpos=fracpos, ratio=ratio, filtpos=filtpos, oversize=oversize, ideal=ideal,
+                           first_out=out_frame, wanted=wanted))
+        srcpos = fracpos
+        for _ in range(g):
+            assert int(srcpos) < limit, "every block delivers all g samples"
+            srcpos += ratio
+        isrcpos = min(int(srcpos), S)                                       # :1558-1560
+        fracpos = srcpos - isrcpos
+        if fsize and ideal:
+            fracpos = math.floor(oversize * fracpos + 0.5) / oversize       # :1562-1563
+        S -= isrcpos
+        offset += isrcpos
+        in_frame += wanted
+        out_frame += g
+    return blocks
+
+
+def window(x_frac):
+    """the Blackman-Harris factor of :1185 at table position xfrac (slice / oversize + tap)"""
+    wp = (2.0 * math.pi / SINC_SIZE) * x_frac
+    return 0.35875 - 0.48829 * math.cos(wp) + 0.14128 * math.cos(2 * wp) - 0.01168 * math.cos(3 * wp)
+
+
+_tables = {}
+
+
+def table(filtpos, oversize):
+    """BuildLowPass's second half (:1157-1202): float32 [(oversize + 1) * 64]"""
+    key = (filtpos, oversize)
+    if key in _tables:
+        return _tables[key]
+    size, half = SINC_SIZE, SINC_SIZE // 2
+    dsincpos = math.pi * filtpos
+    vals, power = [], 0.0
+    for sl in range(oversize // 2 + 1):
+        frac = sl / float(oversize)
+        count = size if (sl < oversize // 2 or oversize & 1) else half
+        for x in range(count):
+            if sl == 0 and x == half:
+                vals.append(1.0)
+                continue
+            xfrac = frac + x
+            sincpos = dsincpos * (xfrac - half)
+            val = window(xfrac) * math.sin(sincpos) / sincpos
+            power += val * 2 if sl else val
+            vals.append(val)
+    alloc = size * (oversize + 1)
+    assert len(vals) == alloc // 2
+    first = np.array(vals, np.float64).astype(F32)
+    scale = oversize / (power + 1.0)
+    first = (first.astype(np.float64) * scale).astype(F32)
+    out = np.concatenate([first, first[::-1]])
+    _tables[key] = out
+    return out
+
+
+def stream_window(x, prelude, start, length):
+    """float32 [ch][length] of the stream (prelude zeros, x, zeros) from index `start`"""
+    ch, n = x.shape
+    out = np.zeros((ch, length), F32)
+    a, b = max(start - prelude, 0), min(start - prelude + length, n)
+    if b > a:
+        out[:, a - (start - prelude):b - (start - prelude)] = x[:, a:b]
+    return out
+
+
+def tap_sums(coef, taps):
+    """per output sample, the sum over 64 taps of float( coef * tap ) added into fp64 in tap order; coef [m][64], taps [ch][m][64] ->
+    float64 [ch][m]"""
+    prod = (coef[None, :, :] * taps).astype(F32).astype(np.float64)        # fp32 products, each rounded
+    s = np.zeros(taps.shape[:2], np.float64)
+    for i in range(SINC_SIZE):
+        s = s + prod[:, :, i]
+    return s
+
+
+def repitch(x, sr, inv, g, quality=SINC, position="chain"):
+    """The whole method: float32 [ch][out_frames].  position: "chain" forms srcpos by repeated += ratio like the reference, "fma"
+    as fracpos + j * ratio with one rounding like the device kernel (the block hand-over is the chain's in both)."""
+    x = np.ascontiguousarray(x, F32)
+    ch, n = x.shape
+    nout = out_frames(inv, g)
+    out = np.zeros((ch, nout), F32)
+    fsize = SINC_SIZE if quality == SINC else 0
+    prelude = fsize // 2 - 1 if fsize else 0
+    taps_index = np.arange(SINC_SIZE)
+    for b in plan(n, sr, inv, g, quality):
+        ratio, oversize = b["ratio"], b["oversize"]
+        m = min(g, nout - b["first_out"])
+        if m <= 0:
+            continue
+        if position == "fma":
+            srcpos = np.array([_fma(j, ratio, b["fracpos"]) for j in range(m)], np.float64)
+        else:
+            srcpos = np.empty(m, np.float64)
+            p = b["fracpos"]
+            for j in range(m):
+                srcpos[j] = p
+                p += ratio
+        ipos = srcpos.astype(np.int64)                                     # truncation: srcpos >= 0
+        frac = srcpos - ipos
+        buf = stream_window(x, prelude, b["offset"], int(ipos[-1]) + SINC_SIZE + 1)
+        dst = out[:, b["first_out"]:b["first_out"] + m]
+        if not fsize:
+            dst[:] = buf[:, ipos]
+            continue
+        tab = table(b["filtpos"], oversize).reshape(oversize + 1, SINC_SIZE)
+        taps = buf[:, ipos[:, None] + taps_index[None, :]]                 # [ch][m][64]
+        if b["ideal"]:
+            ifpos = (frac * oversize + 0.5).astype(np.int64)
+            dst[:] = tap_sums(tab[oversize - ifpos], taps).astype(F32)
+        else:
+            fr = frac * oversize
+            ifpos = fr.astype(np.int64)
+            fr = fr - ifpos
+            s1 = tap_sums(tab[oversize - ifpos - 1], taps)
+            s2 = tap_sums(tab[oversize - ifpos], taps)
+            dst[:] = (s1 * fr[None, :] + s2 * (1.0 - fr)[None, :]).astype(F32)
+    return out
+
+
+def _fma(j, ratio, fracpos):
+    """fma( j, ratio, fracpos ) with one rounding, from exact rational arithmetic"""
+    from fractions import Fraction
+    return float(Fraction(j) * Fraction(ratio) + Fraction(fracpos))
+
+
+def smooth_truth(x, sr, factor, nout):
+    """fp64 truth for a constant factor: output sample t is the Blackman-Harris windowed sinc (64 taps, cut-off filtpos, gain
+    normalised like the table's) evaluated at the exact position t * ratio of the stream, no table, no slices.  float64 [ch][nout]"""
+    x = np.asarray(x, np.float64)
+    ch, n = x.shape
+    inv = invert([factor])[0]
+    rate_in, rate_out, ratio = rates(sr, inv)
+    filtpos = 1.0 / (ratio * 1.03) if ratio > 1.0 else 1.0
+    half = SINC_SIZE // 2
+    prelude = half - 1
+    padded = np.zeros((ch, prelude + n + int(nout * ratio) + 2 * SINC_SIZE + 8))
+    padded[:, prelude:prelude + n] = x
+    t = np.arange(nout, dtype=np.float64) * ratio
+    ipos = np.floor(t).astype(np.int64)
+    frac = t - ipos
+    taps = np.arange(SINC_SIZE, dtype=np.float64)
+    # slice s of the table holds xfrac = s / oversize + tap and is read at s = oversize - ifpos: the continuous form is tap + 1 - frac
+    xfrac = taps[None, :] + 1.0 - frac[:, None]
+    wp = (2.0 * np.pi / SINC_SIZE) * xfrac
+    w = 0.35875 - 0.48829 * np.cos(wp) + 0.14128 * np.cos(2 * wp) - 0.01168 * np.cos(3 * wp)
+    arg = np.pi * filtpos * (xfrac - half)
+    coef = w * np.sinc(arg / np.pi)
+    coef *= filtpos_gain(filtpos)
+    idx = ipos[:, None] + taps[None, :].astype(np.int64)
+    out = np.empty((ch, nout))
+    for c in range(ch):
+        out[c] = np.sum(coef * padded[c][idx], axis=1)
+    return out
+
+
+def filtpos_gain(filtpos, oversize=SINC_OVERSIZE):
+    """the table's normalisation oversize / ( filtpower + 1 ) (:1193), from the fp64 table values"""
+    half = SINC_SIZE // 2
+    power = 0.0
+    for sl in range(oversize // 2 + 1):
+        count = SINC_SIZE if (sl < oversize // 2 or oversize & 1) else half
+        for x in range(count):
+            if sl == 0 and x == half:
+                continue
+            xfrac = sl / float(oversize) + x
+            sincpos = math.pi * filtpos * (xfrac - half)
+            val = window(xfrac) * math.sin(sincpos) / sincpos
+            power += val * 2 if sl else val
+    return oversize / (power + 1.0)
+
+
+def errors(y, ref):
+    """( relative rms error, max abs error / max |ref| )"""
+    y, ref = np.asarray(y, np.float64), np.asarray(ref, np.float64)
+    d = y - ref
+    scale = np.max(np.abs(ref)) if ref.size else 0.0
+    if scale == 0.0:
+        return (0.0, 0.0) if not np.any(d) else (np.inf, np.inf)
+    return float(np.sqrt(np.sum(d * d) / np.sum(ref * ref))), float(np.max(np.abs(d)) / scale)
+
+
+def load_cases():
+    """the reference-made fixture as a list of dicts: name, x, inv, sr, g, quality, out, wanted, delivered"""
+    z = np.load(GOLDEN)
+    cases = []
+    for k, name in enumerate(z["names"]):
+        sr, g, quality, nout, blocks = z["meta_%d" % k]
+        cases.append(dict(name=str(name), x=z["x_%d" % k], inv=z["inv_%d" % k], sr=float(sr), g=int(g), quality=int(quality),
+                          out=z["out_%d" % k], wanted=z["wanted_%d" % k], delivered=z["delivered_%d" % k], out_frames=int(nout), blocks=int(blocks)))
+    return cases
