@@ -141,6 +141,13 @@ _SIGS = {
     "flanhip_audio_repitch_workspace_bytes": (C.c_size_t, [_i64, _f32, _vp, _i64, _i64, _i32]),
     "flanhip_audio_repitch": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _i64, _i64, _i32, _vp, _vp]),
     "flanhip_audio_repitch_dev": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "flanhip_compress_workspace_bytes": (C.c_size_t, [_i64]),
+    "flanhip_compress": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _i64, _i64] + [_vp, _f32] * 5 + [_vp, _vp, _vp]),
+    "flanhip_compress_dev": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _i64, _i64] + [_vp, _f32] * 5 + [_vp, _vp, _vp, _vp]),
+    "flanhip_compress_debug_run": (None, [_i32]),
+    "flanhip_audio_gain_dev": (C.c_int, [_vp, _i64, _i64, _vp, _f32, _vp, _vp]),
+    "flanhip_audio_set_volume_workspace_bytes": (C.c_size_t, [_i64, _i64]),
+    "flanhip_audio_set_volume_dev": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _f32, _vp, _vp, _vp]),
 }
 
 EXPORTS = sorted(_SIGS)
@@ -789,3 +796,88 @@ def audio_repitch_dev(d_audio, ch, n, sample_rate, inv_factors, granularity_fram
     inv = np.ascontiguousarray(inv_factors, np.float32)
     check(lib.flanhip_audio_repitch_dev(_dp(d_audio), ch, n, sample_rate, _ptr(inv), inv.size, granularity_frames, quality, _dp(d_out),
                                         _dp(d_ws), _vp(stream or 0)))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Audio::compress / modify_volume / set_volume.  A compressor parameter is a float (the scalar) or an array of n floats (a curve)
+# ---------------------------------------------------------------------------------------------------------------
+
+COMPRESS_PARAMS = ("threshold", "ratio", "attack", "release", "knee_width")
+COMPRESS_DEFAULTS = {"threshold": -20.0, "ratio": 3.0, "attack": 0.005, "release": 0.1, "knee_width": 0.0}
+
+
+def compress_workspace_bytes(num_frames):
+    return int(lib.flanhip_compress_workspace_bytes(num_frames))
+
+
+def _compress_params(params, n, pointer):
+    """the ten (curve, scalar) arguments in the header's order; curves are kept alive by the second return value"""
+    unknown = set(params) - set(COMPRESS_PARAMS)
+    if unknown:
+        raise TypeError("unknown compressor parameters: %s" % sorted(unknown))
+    args, keep = [], []
+    for name in COMPRESS_PARAMS:
+        v = params.get(name, COMPRESS_DEFAULTS[name])
+        if isinstance(v, (int, float, np.floating)):
+            args += [None, float(v)]
+        else:
+            if pointer is _ptr:
+                v = np.ascontiguousarray(v, np.float32)
+                assert v.shape == (n,), (name, v.shape)
+            keep.append(v)
+            args += [pointer(v), 0.0]
+    return args, keep
+
+
+def compress(audio, sample_rate, sidechain=None, want_gain=False, **params):
+    """Audio::compress.  audio float32 [ch][n]; sidechain float32 [side_ch][side_n >= n] or None (the audio itself) -> float32 [ch][n],
+    with want_gain also the gain curve float32 [n]."""
+    audio = np.ascontiguousarray(audio, np.float32)
+    side = audio if sidechain is None else np.ascontiguousarray(sidechain, np.float32)
+    ch, n = audio.shape
+    args, keep = _compress_params(params, n, _ptr)
+    out = np.empty_like(audio)
+    gain = np.empty(n, np.float32) if want_gain else None
+    check(lib.flanhip_compress(_ptr(audio), ch, n, sample_rate, _ptr(side), side.shape[0], side.shape[1], *args, _ptr(out),
+                               _ptr(gain) if want_gain else None, None))
+    return (out, gain) if want_gain else out
+
+
+def compress_dev(d_audio, ch, n, sample_rate, d_side, side_ch, side_n, d_out, d_gain_out, d_ws, stream=None, **params):
+    """flanhip_compress_dev: parameters are floats or device arrays of n floats"""
+    args, keep = _compress_params(params, n, _dp)
+    check(lib.flanhip_compress_dev(_dp(d_audio), ch, n, sample_rate, _dp(d_side), side_ch, side_n, *args, _dp(d_out), _dp(d_gain_out),
+                                   _dp(d_ws), _vp(stream or 0)))
+
+
+class compress_run_forced:
+    """with fa.compress_run_forced(3): ...   -- the frames one lane replays in this thread's compressions, back to the library's choice afterwards"""
+
+    def __init__(self, frames):
+        self.frames = frames
+
+    def __enter__(self):
+        lib.flanhip_compress_debug_run(self.frames)
+        return self
+
+    def __exit__(self, *exc):
+        lib.flanhip_compress_debug_run(0)
+        return False
+
+
+def audio_gain_dev(d_audio, ch, n, gain, d_out, stream=None):
+    """Audio::modify_volume: gain is a float or a device array of n floats"""
+    scalar = isinstance(gain, (int, float, np.floating))
+    check(lib.flanhip_audio_gain_dev(_dp(d_audio), ch, n, None if scalar else _dp(gain), float(gain) if scalar else 0.0, _dp(d_out),
+                                     _vp(stream or 0)))
+
+
+def audio_set_volume_workspace_bytes(ch, n):
+    return int(lib.flanhip_audio_set_volume_workspace_bytes(ch, n))
+
+
+def audio_set_volume_dev(d_audio, ch, n, sample_rate, level, d_out, d_ws, stream=None):
+    """Audio::set_volume: level is a float or a device array of n floats"""
+    scalar = isinstance(level, (int, float, np.floating))
+    check(lib.flanhip_audio_set_volume_dev(_dp(d_audio), ch, n, sample_rate, None if scalar else _dp(level), float(level) if scalar else 0.0,
+                                           _dp(d_out), _dp(d_ws), _vp(stream or 0)))

@@ -1,0 +1,597 @@
+// compress.hip -- Audio::compress (Audio/AudioVolume.cpp:190-278), Audio::modify_volume (:5-44) and Audio::set_volume (:46-67).
+// DESIGN.md section 4.14.
+//
+// The reference's compressor is one sequential loop over all frames: a gain computer (per frame, depends on no other frame) followed by a
+// two-stage peak detector, each stage a first-order recurrence.  Here:
+//   k_comp_level     per frame: the detector input max( 0, max_c s[c][f] ) (signed: :211-215 take no abs), x_L = x_G - y_G, a_R, a_A
+//   stage 1          y_1 = max( x_L, a_R y_1 + ( 1 - a_R ) x_L ): the maps y -> max( c, a y + b ) with a >= 0 are closed under
+//                    composition, ( a2 a1, a2 b1 + b2, max( c2, a2 c1 + b2 ) ), identity ( 1, 0, -inf ): a scan
+//   stage 2          y_L = a_A y_L + ( 1 - a_A ) y_1: affine maps ( a2 a1, a2 b1 + b2 ): a scan
+// Each lane owns a run of consecutive frames.  k_comp_sum1 reduces every run to one map (fp64), scans the maps across the wavefront
+// (__shfl_up) and the block (LDS) and leaves the block's total; k_comp_carry scans the block totals (one small block) into the state at
+// every block's first frame; k_comp_replay1 scans the block again, hands every lane the state at its run's first frame and REPLAYS the
+// run with the reference's own fp32 operations in the reference's order, writing y_1 and summarising stage 2 on the way; k_comp_carry
+// again; k_comp_replay2 replays stage 2 and writes c = 10^( -y_L / 20 ).  k_gain_apply multiplies every channel by c.
+// Only the state a run starts from comes out of the fp64 scan (rounded to fp32 once); everything else is the sequential fp32 loop.
+// Every composition runs in a fixed order and there are no atomics: two calls agree bit for bit, and c does not depend on how many
+// channels are scaled.  log10, exp and 10^x are evaluated in fp64 and rounded to fp32 once (what glibc's expf / powf do): the fp32
+// device functions are 1 ... 2 ulp off, and one ulp of a_R = 0.9998 is 3e-4 of the release time.
+#include "flanhip_internal.h"
+
+#include <algorithm>
+
+namespace flanhip {
+
+namespace {
+
+thread_local int t_comp_run = 0;          // flanhip_compress_debug_run: frames per lane forced for the calling thread (0: the library's choice)
+
+constexpr int COMP_THREADS = 256;
+constexpr int COMP_WAVES = COMP_THREADS / 64;
+constexpr int COMP_RUN = 16;              // frames per lane: 4096 per block, 703 blocks for a minute at 48 kHz
+constexpr int COMP_MAX_RUN = 64;
+constexpr int64_t COMP_MAX_FRAMES = int64_t( 1 ) << 36;
+constexpr int64_t COMP_MAX_CHANNELS = 1 << 20;
+constexpr int VOL_MAX_PARTIALS = 1024;    // set_volume: the blocks of k_absmax_partial
+constexpr size_t VOL_PARTIAL_OFF = 256;   // word 0 of the workspace: the maximum; the partial maxima start here
+constexpr size_t VOL_WS_BYTES = 8192;
+
+int comp_run()
+	{
+	const int forced = t_comp_run;
+	return forced > 0 ? std::min( forced, COMP_MAX_RUN ) : COMP_RUN;
+	}
+
+struct Map1 { double a, b, c; };          // y -> max( c, a y + b ), a >= 0
+struct Map2 { double a, b; };             // y -> a y + b
+
+struct CompLayout
+	{
+	int run = 0;
+	int64_t blocks = 0, npad = 0;
+	size_t xl = 0, ar = 0, aa = 0, y1 = 0, gain = 0, tot1 = 0, carry1 = 0, tot2 = 0, carry2 = 0, total = 0;
+	};
+
+bool comp_layout( int64_t n, CompLayout * l )
+	{
+	if( n <= 0 || n > COMP_MAX_FRAMES ) return false;
+	l->run = comp_run();
+	const int64_t per_block = int64_t( COMP_THREADS ) * l->run;
+	l->blocks = ( n + per_block - 1 ) / per_block;
+	l->npad = ( n + 3 ) / 4 * 4;
+	const size_t row = sizeof( float ) * size_t( l->npad );
+	l->xl = 0; l->ar = row; l->aa = 2 * row; l->y1 = 3 * row; l->gain = 4 * row;
+	l->tot1 = 5 * row;
+	l->carry1 = l->tot1 + sizeof( Map1 ) * size_t( l->blocks );
+	l->tot2 = l->carry1 + sizeof( double ) * size_t( l->blocks );
+	l->carry2 = l->tot2 + sizeof( Map2 ) * size_t( l->blocks );
+	l->total = l->carry2 + sizeof( double ) * size_t( l->blocks );
+	return true;
+	}
+
+// AudioBuffer::get_max_sample_magnitude() with default arguments scans frames [0, end): end = clamp( Frame( time_to_frame( get_length() ) ),
+// 0, N - 1 ) in fp32 (AudioBuffer.cpp:401-430), as conv.hip's normalize does
+int64_t volume_end( int64_t n, float sr )
+	{
+	const float length = float( n ) / sr;
+	const float f = length * sr;
+	const int64_t e = f >= 9.0e18f ? n : int64_t( f );
+	return std::clamp<int64_t>( e, 0, n - 1 );
+	}
+
+// ---- the maps -------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ Map1 identity1() { return Map1{ 1.0, 0.0, -INFINITY }; }
+__device__ __forceinline__ Map2 identity2() { return Map2{ 1.0, 0.0 }; }
+// `l` after `e`.  An empty floor stays empty whatever a is (0 x -inf would be NaN)
+__device__ __forceinline__ Map1 then( const Map1 & e, const Map1 & l )
+	{
+	Map1 r;
+	r.a = l.a * e.a;
+	r.b = l.a * e.b + l.b;
+	r.c = fmax( l.c, e.c == -INFINITY ? -INFINITY : l.a * e.c + l.b );
+	return r;
+	}
+__device__ __forceinline__ Map2 then( const Map2 & e, const Map2 & l ) { return Map2{ l.a * e.a, l.a * e.b + l.b }; }
+__device__ __forceinline__ double apply( const Map1 & m, double y ) { return fmax( m.c, m.a * y + m.b ); }
+__device__ __forceinline__ double apply( const Map2 & m, double y ) { return m.a * y + m.b; }
+__device__ __forceinline__ Map1 shfl_up( const Map1 & m, int off ) { return Map1{ __shfl_up( m.a, off ), __shfl_up( m.b, off ), __shfl_up( m.c, off ) }; }
+__device__ __forceinline__ Map2 shfl_up( const Map2 & m, int off ) { return Map2{ __shfl_up( m.a, off ), __shfl_up( m.b, off ) }; }
+__device__ __forceinline__ void set_identity( Map1 & m ) { m = identity1(); }
+__device__ __forceinline__ void set_identity( Map2 & m ) { m = identity2(); }
+
+// Scan of one map per thread over the block, in thread order: excl = the maps of all earlier threads composed, total = the block's.
+// Every thread of the block calls it.
+template<typename M>
+__device__ __forceinline__ void block_scan( const M & mine, M * s_tot, M & excl, M & total )
+	{
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	M inc = mine;
+	#pragma unroll
+	for( int off = 1; off < 64; off <<= 1 )
+		{
+		const M o = shfl_up( inc, off );
+		if( lane >= off ) inc = then( o, inc );
+		}
+	if( lane == 63 ) s_tot[wave] = inc;
+	__syncthreads();
+	M prev = shfl_up( inc, 1 );
+	if( lane == 0 ) set_identity( prev );
+	M pre; set_identity( pre );
+	for( int w = 0; w < wave; ++w ) pre = then( pre, s_tot[w] );
+	excl = then( pre, prev );
+	total = s_tot[0];
+	#pragma unroll
+	for( int w = 1; w < COMP_WAVES; ++w ) total = then( total, s_tot[w] );
+	__syncthreads();
+	}
+
+// four consecutive floats from frame f (a multiple of 4 when VEC: the workspace rows are 16-byte aligned and padded to a multiple of 4)
+template<bool VEC>
+__device__ __forceinline__ void load4( const float * p, int64_t f, int64_t n, float ( &v )[4] )
+	{
+	if constexpr( VEC )
+		{
+		const float4 q = *reinterpret_cast<const float4*>( p + f );
+		v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+		}
+	else
+		{
+		#pragma unroll
+		for( int k = 0; k < 4; ++k ) v[k] = f + k < n ? p[f + k] : 0.0f;
+		}
+	}
+// the first `valid` of four values to frame f on.  VEC: all four (a run is whole quads then, so valid < 4 only where the quad ends in the
+// row's padding); otherwise nothing past the run: those frames are the next lane's
+template<bool VEC>
+__device__ __forceinline__ void store4( float * p, int64_t f, int valid, const float ( &v )[4] )
+	{
+	if constexpr( VEC ) *reinterpret_cast<float4*>( p + f ) = make_float4( v[0], v[1], v[2], v[3] );
+	else
+		{
+		#pragma unroll
+		for( int k = 0; k < 4; ++k ) if( k < valid ) p[f + k] = v[k];
+		}
+	}
+
+// the run of the calling thread: frames [f0, f0 + len)
+__device__ __forceinline__ void lane_run( int64_t n, int run, int64_t & f0, int & len )
+	{
+	f0 = ( int64_t( blockIdx.x ) * COMP_THREADS + threadIdx.x ) * run;
+	len = int( std::min<int64_t>( std::max<int64_t>( n - f0, 0 ), run ) );
+	}
+
+// stage 1 of a run as one map: step f is ( a_R, ( 1 - a_R ) x_L, x_L ), the fp32 values the replay uses, composed in fp64
+template<bool VEC>
+__device__ __forceinline__ Map1 summarise1( const float * xl, const float * ar, int64_t n, int64_t f0, int len )
+	{
+	Map1 m = identity1();
+	for( int i = 0; i < len; i += 4 )
+		{
+		float x[4], a[4];
+		load4<VEC>( xl, f0 + i, n, x );
+		load4<VEC>( ar, f0 + i, n, a );
+		#pragma unroll
+		for( int k = 0; k < 4; ++k )
+			if( i + k < len )
+				m = then( m, Map1{ double( a[k] ), double( 1.0f - a[k] ) * double( x[k] ), double( x[k] ) } );
+		}
+	return m;
+	}
+
+// stage 2 of a run as one map: step f is ( a_A, ( 1 - a_A ) y_1 )
+template<bool VEC>
+__device__ __forceinline__ Map2 summarise2( const float * y1, const float * aa, int64_t n, int64_t f0, int len )
+	{
+	Map2 m = identity2();
+	for( int i = 0; i < len; i += 4 )
+		{
+		float y[4], a[4];
+		load4<VEC>( y1, f0 + i, n, y );
+		load4<VEC>( aa, f0 + i, n, a );
+		#pragma unroll
+		for( int k = 0; k < 4; ++k )
+			if( i + k < len )
+				m = then( m, Map2{ double( a[k] ), double( 1.0f - a[k] ) * double( y[k] ) } );
+		}
+	return m;
+	}
+
+// ---- kernels --------------------------------------------------------------------------------------------------------------------
+struct CompParams
+	{
+	const float * threshold, * ratio, * attack, * release, * knee;    // float[n] on the device, or null: the scalar
+	float threshold_c, ratio_c, attack_c, release_c, knee_c;
+	};
+
+// exp, log10 and 10^x of an fp32 argument, rounded to fp32 once from the fp64 value
+__device__ __forceinline__ float exp_rn( float x ) { return float( exp( double( x ) ) ); }
+__device__ __forceinline__ float log10_rn( float x ) { return float( log10( double( x ) ) ); }
+__device__ __forceinline__ float exp10_rn( float x ) { return float( exp10( double( x ) ) ); }
+
+// AudioVolume.cpp:227-239, as written
+__device__ __forceinline__ float gain_computer( float x_G, float threshold, float knee_width, float ratio )
+	{
+	const float overshoot = x_G - threshold;
+	if( overshoot <= -knee_width / 2.0f ) return x_G;
+	else if( overshoot >= knee_width / 2.0f ) return x_G + overshoot * ( 1 / ratio - 1 );
+	else
+		{
+		const float z = overshoot + knee_width / 2.0f;
+		return x_G + ( 1 / ratio - 1 ) * z * z / ( 2.0f * knee_width );
+		}
+	}
+
+// one frame per thread: :211-215 (the SIGNED maximum over the sidechain's channels, from 0; a NaN sample is never taken), :264-269, :242
+__global__ __launch_bounds__( COMP_THREADS ) void k_comp_level( const float * __restrict__ side, int64_t side_ch, int64_t side_n, int64_t n, float sr,
+	CompParams p, float * __restrict__ xl, float * __restrict__ ar, float * __restrict__ aa )
+	{
+	const int64_t f = int64_t( blockIdx.x ) * COMP_THREADS + threadIdx.x;
+	if( f >= n ) return;
+	float x = 0.0f;
+	for( int64_t c = 0; c < side_ch; ++c )
+		{
+		const float s = side[c * side_n + f];
+		if( x < s ) x = s;
+		}
+	const float x_G = 20.0f * log10_rn( fmaxf( fabsf( x ), 1e-6f ) );
+	const float y_G = gain_computer( x_G, p.threshold ? p.threshold[f] : p.threshold_c, p.knee ? p.knee[f] : p.knee_c, p.ratio ? p.ratio[f] : p.ratio_c );
+	xl[f] = x_G - y_G;
+	ar[f] = exp_rn( -1.0f / ( ( p.release ? p.release[f] : p.release_c ) * sr ) );
+	aa[f] = exp_rn( -1.0f / ( ( p.attack ? p.attack[f] : p.attack_c ) * sr ) );
+	}
+
+template<bool VEC>
+__global__ __launch_bounds__( COMP_THREADS ) void k_comp_sum1( const float * __restrict__ xl, const float * __restrict__ ar, int64_t n, int run,
+	Map1 * __restrict__ tot )
+	{
+	__shared__ Map1 s_tot[COMP_WAVES];
+	int64_t f0; int len;
+	lane_run( n, run, f0, len );
+	Map1 excl, total;
+	block_scan( summarise1<VEC>( xl, ar, n, f0, len ), s_tot, excl, total );
+	if( threadIdx.x == 0 ) tot[blockIdx.x] = total;
+	}
+
+// One block: the state at the first frame of every block of the scan, from the block totals and the state 0 before frame 0 (:258-259)
+template<typename M>
+__global__ __launch_bounds__( COMP_THREADS ) void k_comp_carry( const M * __restrict__ tot, int64_t blocks, double * __restrict__ carry )
+	{
+	__shared__ M s_tot[COMP_WAVES];
+	double state = 0.0;
+	for( int64_t base = 0; base < blocks; base += COMP_THREADS )
+		{
+		const int64_t b = base + threadIdx.x;
+		M mine; set_identity( mine );
+		if( b < blocks ) mine = tot[b];
+		M excl, total;
+		block_scan( mine, s_tot, excl, total );
+		if( b < blocks ) carry[b] = apply( excl, state );
+		state = apply( total, state );
+		}
+	}
+
+// Stage 1 replayed (:250 in fp32, std::max( a, b ) = a < b ? b : a), y_1 written, stage 2 summarised
+template<bool VEC>
+__global__ __launch_bounds__( COMP_THREADS ) void k_comp_replay1( const float * __restrict__ xl, const float * __restrict__ ar,
+	const float * __restrict__ aa, int64_t n, int run, const double * __restrict__ carry1, float * __restrict__ y1_out, Map2 * __restrict__ tot2 )
+	{
+	__shared__ Map1 s_tot1[COMP_WAVES];
+	__shared__ Map2 s_tot2[COMP_WAVES];
+	int64_t f0; int len;
+	lane_run( n, run, f0, len );
+	Map1 excl, total;
+	block_scan( summarise1<VEC>( xl, ar, n, f0, len ), s_tot1, excl, total );
+	float y_1 = float( apply( excl, carry1[blockIdx.x] ) );
+	Map2 m2 = identity2();
+	for( int i = 0; i < len; i += 4 )
+		{
+		float x[4], a[4], A[4], y[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+		load4<VEC>( xl, f0 + i, n, x );
+		load4<VEC>( ar, f0 + i, n, a );
+		load4<VEC>( aa, f0 + i, n, A );
+		#pragma unroll
+		for( int k = 0; k < 4; ++k )
+			if( i + k < len )
+				{
+				const float v = a[k] * y_1 + ( 1.0f - a[k] ) * x[k];
+				y_1 = x[k] < v ? v : x[k];
+				y[k] = y_1;
+				m2 = then( m2, Map2{ double( A[k] ), double( 1.0f - A[k] ) * double( y_1 ) } );
+				}
+		store4<VEC>( y1_out, f0 + i, len - i, y );
+		}
+	Map2 excl2, total2;
+	block_scan( m2, s_tot2, excl2, total2 );
+	if( threadIdx.x == 0 ) tot2[blockIdx.x] = total2;
+	}
+
+// Stage 2 replayed (:251 in fp32) and :272: c = pow( 10.0f, -y_L / 20.0f )
+template<bool VEC>
+__global__ __launch_bounds__( COMP_THREADS ) void k_comp_replay2( const float * __restrict__ y1, const float * __restrict__ aa, int64_t n, int run,
+	const double * __restrict__ carry2, float * __restrict__ gain )
+	{
+	__shared__ Map2 s_tot[COMP_WAVES];
+	int64_t f0; int len;
+	lane_run( n, run, f0, len );
+	Map2 excl, total;
+	block_scan( summarise2<VEC>( y1, aa, n, f0, len ), s_tot, excl, total );
+	float y_L = float( apply( excl, carry2[blockIdx.x] ) );
+	for( int i = 0; i < len; i += 4 )
+		{
+		float y[4], A[4], c[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+		load4<VEC>( y1, f0 + i, n, y );
+		load4<VEC>( aa, f0 + i, n, A );
+		#pragma unroll
+		for( int k = 0; k < 4; ++k )
+			if( i + k < len )
+				{
+				y_L = A[k] * y_L + ( 1.0f - A[k] ) * y[k];
+				c[k] = exp10_rn( -y_L / 20.0f );
+				}
+		store4<VEC>( gain, f0 + i, len - i, c );
+		}
+	}
+
+// out[ch][f] = in[ch][f] * g[f] for every channel: g = curve[f] (or the scalar), OVER_MAX: divided by *d_max first, one fp32 division
+// (:66: level( t ) / max_mag); *d_max == 0 hands the input through (:65).  VEC: four frames per thread, 16 bytes per lane (n a multiple
+// of 4 and 16-byte aligned pointers).  out may be in: a thread reads what it writes.
+template<bool VEC, bool OVER_MAX>
+__global__ __launch_bounds__( 256 ) void k_gain_apply( const float * in, float * out, int64_t ch, int64_t n, const float * curve, float scalar,
+	const float * d_max )
+	{
+	constexpr int W = VEC ? 4 : 1;
+	float m = 1.0f;
+	if constexpr( OVER_MAX ) m = *d_max;
+	const bool through = OVER_MAX && m == 0.0f;
+	const int64_t items = n / W;
+	for( int64_t q = int64_t( blockIdx.x ) * 256 + threadIdx.x; q < items; q += int64_t( gridDim.x ) * 256 )
+		{
+		const int64_t f = q * W;
+		float g[W];
+		if constexpr( VEC )
+			{
+			if( curve ) { const float4 v = *reinterpret_cast<const float4*>( curve + f ); g[0] = v.x; g[1] = v.y; g[2] = v.z; g[3] = v.w; }
+			else { g[0] = g[1] = g[2] = g[3] = scalar; }
+			}
+		else g[0] = curve ? curve[f] : scalar;
+		if constexpr( OVER_MAX )
+			{
+			#pragma unroll
+			for( int k = 0; k < W; ++k ) g[k] = g[k] / m;
+			}
+		for( int64_t c = 0; c < ch; ++c )
+			{
+			if constexpr( VEC )
+				{
+				float4 v = *reinterpret_cast<const float4*>( in + c * n + f );
+				if( !through ) { v.x = v.x * g[0]; v.y = v.y * g[1]; v.z = v.z * g[2]; v.w = v.w * g[3]; }
+				*reinterpret_cast<float4*>( out + c * n + f ) = v;
+				}
+			else
+				{
+				const float v = in[c * n + f];
+				out[c * n + f] = through ? v : v * g[0];
+				}
+			}
+		}
+	}
+
+// max |x| over frames [0, end) of every channel: one partial maximum per block (NaN skipped, as std::max( m, |x| ) skips it), no atomics
+__global__ __launch_bounds__( 256 ) void k_absmax_partial( const float * __restrict__ in, int64_t ch, int64_t n, int64_t end, float * __restrict__ partial )
+	{
+	__shared__ float s_red[4];
+	float mx = 0.0f;
+	for( int64_t f = int64_t( blockIdx.x ) * 256 + threadIdx.x; f < end; f += int64_t( gridDim.x ) * 256 )
+		for( int64_t c = 0; c < ch; ++c ) mx = fmaxf( mx, fabsf( in[c * n + f] ) );
+	#pragma unroll
+	for( int off = 32; off > 0; off >>= 1 ) mx = fmaxf( mx, __shfl_xor( mx, off ) );
+	if( ( threadIdx.x & 63 ) == 0 ) s_red[threadIdx.x >> 6] = mx;
+	__syncthreads();
+	if( threadIdx.x == 0 ) partial[blockIdx.x] = fmaxf( fmaxf( s_red[0], s_red[1] ), fmaxf( s_red[2], s_red[3] ) );
+	}
+
+__global__ __launch_bounds__( 256 ) void k_absmax_final( const float * __restrict__ partial, int count, float * __restrict__ d_max )
+	{
+	__shared__ float s_red[4];
+	float mx = 0.0f;
+	for( int i = threadIdx.x; i < count; i += 256 ) mx = fmaxf( mx, partial[i] );
+	#pragma unroll
+	for( int off = 32; off > 0; off >>= 1 ) mx = fmaxf( mx, __shfl_xor( mx, off ) );
+	if( ( threadIdx.x & 63 ) == 0 ) s_red[threadIdx.x >> 6] = mx;
+	__syncthreads();
+	if( threadIdx.x == 0 ) *d_max = fmaxf( fmaxf( s_red[0], s_red[1] ), fmaxf( s_red[2], s_red[3] ) );
+	}
+
+// ---- launchers ------------------------------------------------------------------------------------------------------------------
+bool aligned16( const void * p ) { return ( reinterpret_cast<uintptr_t>( p ) & 15 ) == 0; }
+
+int launch_gain_apply( const float * d_in, int64_t ch, int64_t n, const float * d_curve, float scalar, const float * d_max, float * d_out, hipStream_t s )
+	{
+	const bool vec = n % 4 == 0 && aligned16( d_in ) && aligned16( d_out ) && aligned16( d_curve );
+	const int64_t items = vec ? n / 4 : n;
+	const unsigned blocks = (unsigned) std::min<int64_t>( ( items + 255 ) / 256, int64_t( 1 ) << 20 );
+	if( vec && d_max ) hipLaunchKernelGGL( ( k_gain_apply<true, true> ), dim3( blocks ), dim3( 256 ), 0, s, d_in, d_out, ch, n, d_curve, scalar, d_max );
+	else if( vec ) hipLaunchKernelGGL( ( k_gain_apply<true, false> ), dim3( blocks ), dim3( 256 ), 0, s, d_in, d_out, ch, n, d_curve, scalar, d_max );
+	else if( d_max ) hipLaunchKernelGGL( ( k_gain_apply<false, true> ), dim3( blocks ), dim3( 256 ), 0, s, d_in, d_out, ch, n, d_curve, scalar, d_max );
+	else hipLaunchKernelGGL( ( k_gain_apply<false, false> ), dim3( blocks ), dim3( 256 ), 0, s, d_in, d_out, ch, n, d_curve, scalar, d_max );
+	FLANHIP_CHECK( hipGetLastError() );
+	return FLANHIP_OK;
+	}
+
+struct CompArgs
+	{
+	const float * audio; int64_t ch, n; float sr;
+	const float * side; int64_t side_ch, side_n;
+	CompParams p;
+	float * out, * gain_out;
+	};
+
+// what both forms refuse before any device call
+int comp_check( const CompArgs & a, CompLayout * l )
+	{
+	FLANHIP_REQUIRE( a.audio && a.side && a.out, FLANHIP_ERR_INVALID_ARG, "null buffer" );
+	FLANHIP_REQUIRE( a.ch > 0 && a.n > 0 && a.side_ch > 0 && a.side_n > 0, FLANHIP_ERR_INVALID_ARG, "non-positive size" );
+	FLANHIP_REQUIRE( a.sr > 0.0f, FLANHIP_ERR_INVALID_ARG, "sample rate not positive" );
+	FLANHIP_REQUIRE( a.side_n >= a.n, FLANHIP_ERR_INVALID_ARG, "the sidechain has fewer frames than the audio" );
+	FLANHIP_REQUIRE( a.ch <= COMP_MAX_CHANNELS && a.side_ch <= COMP_MAX_CHANNELS && comp_layout( a.n, l ), FLANHIP_ERR_UNSUPPORTED, "shape out of range" );
+	return FLANHIP_OK;
+	}
+
+int launch_compress( const CompArgs & a, void * d_ws, hipStream_t s )
+	{
+	CompLayout l;
+	if( int rc = comp_check( a, &l ) ) return rc;
+	FLANHIP_REQUIRE( d_ws, FLANHIP_ERR_INVALID_ARG, "null workspace" );
+	if( int rc = require_device() ) return rc;
+	float * xl = ws_at<float>( d_ws, l.xl ), * ar = ws_at<float>( d_ws, l.ar ), * aa = ws_at<float>( d_ws, l.aa );
+	float * y1 = ws_at<float>( d_ws, l.y1 ), * gain = ws_at<float>( d_ws, l.gain );
+	Map1 * tot1 = ws_at<Map1>( d_ws, l.tot1 );
+	Map2 * tot2 = ws_at<Map2>( d_ws, l.tot2 );
+	double * carry1 = ws_at<double>( d_ws, l.carry1 ), * carry2 = ws_at<double>( d_ws, l.carry2 );
+	const int64_t n = a.n;
+	const dim3 threads( COMP_THREADS ), grid( (unsigned) l.blocks );
+	hipLaunchKernelGGL( k_comp_level, dim3( (unsigned) ( ( n + COMP_THREADS - 1 ) / COMP_THREADS ) ), threads, 0, s,
+		a.side, a.side_ch, a.side_n, n, a.sr, a.p, xl, ar, aa );
+	FLANHIP_CHECK( hipGetLastError() );
+	const bool vec = l.run % 4 == 0 && aligned16( d_ws );        // every run then starts on a 16-byte boundary of the padded rows
+	if( vec ) hipLaunchKernelGGL( k_comp_sum1<true>, grid, threads, 0, s, xl, ar, n, l.run, tot1 );
+	else hipLaunchKernelGGL( k_comp_sum1<false>, grid, threads, 0, s, xl, ar, n, l.run, tot1 );
+	FLANHIP_CHECK( hipGetLastError() );
+	hipLaunchKernelGGL( k_comp_carry<Map1>, dim3( 1 ), threads, 0, s, tot1, l.blocks, carry1 );
+	FLANHIP_CHECK( hipGetLastError() );
+	if( vec ) hipLaunchKernelGGL( k_comp_replay1<true>, grid, threads, 0, s, xl, ar, aa, n, l.run, carry1, y1, tot2 );
+	else hipLaunchKernelGGL( k_comp_replay1<false>, grid, threads, 0, s, xl, ar, aa, n, l.run, carry1, y1, tot2 );
+	FLANHIP_CHECK( hipGetLastError() );
+	hipLaunchKernelGGL( k_comp_carry<Map2>, dim3( 1 ), threads, 0, s, tot2, l.blocks, carry2 );
+	FLANHIP_CHECK( hipGetLastError() );
+	if( vec ) hipLaunchKernelGGL( k_comp_replay2<true>, grid, threads, 0, s, y1, aa, n, l.run, carry2, gain );
+	else hipLaunchKernelGGL( k_comp_replay2<false>, grid, threads, 0, s, y1, aa, n, l.run, carry2, gain );
+	FLANHIP_CHECK( hipGetLastError() );
+	if( a.gain_out ) FLANHIP_CHECK( hipMemcpyAsync( a.gain_out, gain, sizeof( float ) * size_t( n ), hipMemcpyDeviceToDevice, s ) );
+	return launch_gain_apply( a.audio, a.ch, n, gain, 0.0f, nullptr, a.out, s );
+	}
+
+int gain_check( const void * audio, int64_t ch, int64_t n, const void * out )
+	{
+	FLANHIP_REQUIRE( audio && out, FLANHIP_ERR_INVALID_ARG, "null buffer" );
+	FLANHIP_REQUIRE( ch > 0 && n > 0, FLANHIP_ERR_INVALID_ARG, "non-positive size" );
+	FLANHIP_REQUIRE( ch <= COMP_MAX_CHANNELS && n <= COMP_MAX_FRAMES, FLANHIP_ERR_UNSUPPORTED, "shape out of range" );
+	return FLANHIP_OK;
+	}
+
+struct DevBuf
+	{
+	void * p = nullptr;
+	~DevBuf() { if( p ) (void) hipFree( p ); }
+	int alloc( size_t bytes ) { FLANHIP_CHECK( hipMalloc( &p, bytes ? bytes : 1 ) ); return FLANHIP_OK; }
+	};
+
+} // namespace
+
+} // namespace flanhip
+
+using namespace flanhip;
+
+extern "C" {
+
+size_t flanhip_compress_workspace_bytes( int64_t num_frames )
+	{
+	CompLayout l;
+	if( !comp_layout( num_frames, &l ) ) return 0;
+	return l.total;
+	}
+
+void flanhip_compress_debug_run( int frames )
+	{
+	t_comp_run = frames > 0 ? frames : 0;
+	}
+
+int flanhip_compress_dev( const float * d_audio, int64_t num_channels, int64_t num_frames, float sample_rate,
+	const float * d_sidechain, int64_t side_channels, int64_t side_frames,
+	const float * d_threshold, float threshold, const float * d_ratio, float ratio, const float * d_attack, float attack,
+	const float * d_release, float release, const float * d_knee_width, float knee_width,
+	float * d_out, float * d_gain_out, void * d_workspace, void * stream )
+	{
+	const CompArgs a{ d_audio, num_channels, num_frames, sample_rate, d_sidechain, side_channels, side_frames,
+		CompParams{ d_threshold, d_ratio, d_attack, d_release, d_knee_width, threshold, ratio, attack, release, knee_width }, d_out, d_gain_out };
+	return launch_compress( a, d_workspace, (hipStream_t) stream );
+	}
+
+int flanhip_compress( const float * audio, int64_t num_channels, int64_t num_frames, float sample_rate,
+	const float * sidechain, int64_t side_channels, int64_t side_frames,
+	const float * threshold_curve, float threshold, const float * ratio_curve, float ratio, const float * attack_curve, float attack,
+	const float * release_curve, float release, const float * knee_width_curve, float knee_width,
+	float * out, float * gain_out, volatile int * cancel )
+	{
+	CompArgs a{ audio, num_channels, num_frames, sample_rate, sidechain, side_channels, side_frames,
+		CompParams{ nullptr, nullptr, nullptr, nullptr, nullptr, threshold, ratio, attack, release, knee_width }, out, gain_out };
+	CompLayout l;
+	if( int rc = comp_check( a, &l ) ) return rc;
+	if( int rc = require_device() ) return rc;
+	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
+	const size_t x_bytes = sizeof( float ) * size_t( num_channels ) * size_t( num_frames );
+	const size_t s_bytes = sizeof( float ) * size_t( side_channels ) * size_t( side_frames );
+	const size_t row = sizeof( float ) * size_t( num_frames );
+	const bool own_side = sidechain == audio && side_channels == num_channels && side_frames == num_frames;
+	DevBuf d_x, d_s, d_out, d_gain, d_ws, d_curve[5];
+	if( int rc = d_x.alloc( x_bytes ) ) return rc;
+	if( !own_side ) if( int rc = d_s.alloc( s_bytes ) ) return rc;
+	if( int rc = d_out.alloc( x_bytes ) ) return rc;
+	if( gain_out ) if( int rc = d_gain.alloc( row ) ) return rc;
+	if( int rc = d_ws.alloc( l.total ) ) return rc;
+	if( int rc = flanhip_upload( d_x.p, audio, x_bytes ) ) return rc;
+	if( !own_side ) if( int rc = flanhip_upload( d_s.p, sidechain, s_bytes ) ) return rc;
+	const float * curves[5] = { threshold_curve, ratio_curve, attack_curve, release_curve, knee_width_curve };
+	const float ** slots[5] = { &a.p.threshold, &a.p.ratio, &a.p.attack, &a.p.release, &a.p.knee };
+	for( int i = 0; i < 5; ++i )
+		if( curves[i] )
+			{
+			if( int rc = d_curve[i].alloc( row ) ) return rc;
+			if( int rc = flanhip_upload( d_curve[i].p, curves[i], row ) ) return rc;
+			*slots[i] = static_cast<const float*>( d_curve[i].p );
+			}
+	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
+	a.audio = static_cast<const float*>( d_x.p );
+	a.side = own_side ? a.audio : static_cast<const float*>( d_s.p );
+	a.out = static_cast<float*>( d_out.p );
+	a.gain_out = static_cast<float*>( d_gain.p );
+	if( int rc = launch_compress( a, d_ws.p, nullptr ) ) return rc;
+	if( int rc = wait_cancellable( nullptr, cancel ? poll_volatile_int : nullptr, const_cast<int*>( cancel ) ) ) return rc;
+	if( gain_out ) if( int rc = flanhip_download( gain_out, d_gain.p, row ) ) return rc;
+	return flanhip_download( out, d_out.p, x_bytes );
+	}
+
+int flanhip_audio_gain_dev( const float * d_audio, int64_t num_channels, int64_t num_frames, const float * d_gain, float gain, float * d_out, void * stream )
+	{
+	if( int rc = gain_check( d_audio, num_channels, num_frames, d_out ) ) return rc;
+	if( int rc = require_device() ) return rc;
+	return launch_gain_apply( d_audio, num_channels, num_frames, d_gain, gain, nullptr, d_out, (hipStream_t) stream );
+	}
+
+size_t flanhip_audio_set_volume_workspace_bytes( int64_t num_channels, int64_t num_frames )
+	{
+	if( num_channels <= 0 || num_frames <= 0 || num_channels > COMP_MAX_CHANNELS || num_frames > COMP_MAX_FRAMES ) return 0;
+	return VOL_WS_BYTES;
+	}
+
+int flanhip_audio_set_volume_dev( const float * d_audio, int64_t num_channels, int64_t num_frames, float sample_rate, const float * d_level, float level,
+	float * d_out, void * d_workspace, void * stream )
+	{
+	if( int rc = gain_check( d_audio, num_channels, num_frames, d_out ) ) return rc;
+	FLANHIP_REQUIRE( sample_rate > 0.0f, FLANHIP_ERR_INVALID_ARG, "sample rate not positive" );
+	FLANHIP_REQUIRE( d_workspace, FLANHIP_ERR_INVALID_ARG, "null workspace" );
+	if( int rc = require_device() ) return rc;
+	hipStream_t s = (hipStream_t) stream;
+	static_assert( VOL_PARTIAL_OFF + sizeof( float ) * VOL_MAX_PARTIALS <= VOL_WS_BYTES, "the partial maxima fit" );
+	float * d_max = ws_at<float>( d_workspace, 0 );
+	float * partial = ws_at<float>( d_workspace, VOL_PARTIAL_OFF );
+	const int64_t end = volume_end( num_frames, sample_rate );
+	const int blocks = int( std::clamp<int64_t>( ( end + 255 ) / 256, 1, VOL_MAX_PARTIALS ) );
+	hipLaunchKernelGGL( k_absmax_partial, dim3( (unsigned) blocks ), dim3( 256 ), 0, s, d_audio, num_channels, num_frames, end, partial );
+	FLANHIP_CHECK( hipGetLastError() );
+	hipLaunchKernelGGL( k_absmax_final, dim3( 1 ), dim3( 256 ), 0, s, partial, blocks, d_max );
+	FLANHIP_CHECK( hipGetLastError() );
+	return launch_gain_apply( d_audio, num_channels, num_frames, d_level, level, d_max, d_out, s );
+	}
+
+} // extern "C"

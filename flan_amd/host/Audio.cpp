@@ -1,6 +1,6 @@
 // Audio.cpp -- construction and conversions of flan::Audio over the C ABI
 // (reference: src/flan/Audio/AudioConstructors.cpp, Conversions/AudioPV.cpp:12-84, Audio/AudioConversions.cpp:14-56,
-// Audio/AudioCombination.cpp:299-352, Audio/AudioTemporal.cpp:236-299).
+// Audio/AudioCombination.cpp:299-352, Audio/AudioTemporal.cpp:236-299, Audio/AudioVolume.cpp:5-67, 190-278).
 #include "flan/Audio.h"
 
 #include <algorithm>
@@ -11,6 +11,32 @@
 #include "flan/PV.h"
 
 namespace flan {
+
+namespace {
+
+// A Function of time as the device entry points take it: a constant goes as the scalar and samples nothing; a callable is sampled once
+// per frame at x * scale (Function::sample's arithmetic, Function.h:141-153) into a page-locked block and uploaded.
+struct DeviceCurve
+	{
+	std::shared_ptr<detail::DeviceBlock> block;
+	float scalar = 0.0f;
+	bool ok = true;
+	const float * ptr() const { return block ? static_cast<const float*>( block->ptr ) : nullptr; }
+	};
+
+DeviceCurve upload_curve( const Function<Second, float> & fn, Frame n, float scale )
+	{
+	DeviceCurve c;
+	if( fn.is_constant() ) { c.scalar = fn.get_constant(); return c; }
+	detail::StagingVector<float> sampled( size_t( std::max( n, 0 ) ) );
+	detail::for_each_index( 0, n, fn.get_execution_policy(), [&]( int x ){ sampled[size_t( x )] = fn( Second( x * scale ) ); } );
+	c.block = detail::DeviceBlock::allocate( sizeof( float ) * sampled.size() );
+	c.ok = c.block && detail::upload_from_host( c.block->ptr, sampled.data(), sizeof( float ) * sampled.size() );
+	if( c.block && !c.ok ) std::cerr << "flan: upload of a sampled Function failed: " << flanhip_last_error() << std::endl;
+	return c;
+	}
+
+} // namespace
 
 Audio::Audio() : AudioBuffer() {}
 Audio::Audio( AudioBuffer && other ) : AudioBuffer( std::move( other ) ) {}
@@ -198,6 +224,86 @@ Audio Audio::repitch( const Function<Second, float> & factor, Second granularity
 	if( !detail::report( rc, "repitch" ) ) return Audio::create_null();
 	if( !detail::report( flanhip_stream_synchronize( nullptr ), "repitch" ) ) return Audio::create_null();     // the workspace goes back idle
 	return AudioBuffer::adopt_device( f, std::move( block ) );
+	}
+
+Audio Audio::modify_volume( const Function<Second, float> & gain ) const
+	{
+	if( is_null() ) return Audio::create_null();                // AudioVolume.cpp:9
+	const float * d_x = device_data();
+	if( !d_x ) return Audio::create_null();
+	const DeviceCurve g = upload_curve( gain, get_num_frames(), 1.0f / get_sample_rate() );     // :36
+	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( get_num_channels() ) * size_t( get_num_frames() ) );
+	if( !g.ok || !block ) return Audio::create_null();
+	const int rc = flanhip_audio_gain_dev( d_x, get_num_channels(), get_num_frames(), g.ptr(), g.scalar, static_cast<float*>( block->ptr ), nullptr );
+	if( !detail::report( rc, "modify_volume" ) ) return Audio::create_null();
+	if( !detail::report( flanhip_stream_synchronize( nullptr ), "modify_volume" ) ) return Audio::create_null();   // the curve goes back idle
+	return AudioBuffer::adopt_device( get_format(), std::move( block ) );
+	}
+
+// the in-place forms compute into a fresh block and take it over: the block under *this may be shared (device_block())
+Audio & Audio::modify_volume_in_place( const Function<Second, float> & gain )
+	{
+	if( is_null() ) return *this;
+	Audio out = modify_volume( gain );
+	if( !out.is_null() ) *this = std::move( out );
+	return *this;
+	}
+
+Audio Audio::set_volume( const Function<Second, Amplitude> & level ) const
+	{
+	if( is_null() ) return Audio::create_null();                // :50
+	const float * d_x = device_data();
+	if( !d_x ) return Audio::create_null();
+	const DeviceCurve l = upload_curve( level, get_num_frames(), 1.0f / get_sample_rate() );
+	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( get_num_channels() ) * size_t( get_num_frames() ) );
+	auto ws = detail::DeviceBlock::allocate( flanhip_audio_set_volume_workspace_bytes( get_num_channels(), get_num_frames() ) );
+	if( !l.ok || !block || !ws ) return Audio::create_null();
+	// :63-66: the maximum, the m == 0 case and level( t ) / m are the device's
+	const int rc = flanhip_audio_set_volume_dev( d_x, get_num_channels(), get_num_frames(), get_sample_rate(), l.ptr(), l.scalar,
+		static_cast<float*>( block->ptr ), ws->ptr, nullptr );
+	if( !detail::report( rc, "set_volume" ) ) return Audio::create_null();
+	if( !detail::report( flanhip_stream_synchronize( nullptr ), "set_volume" ) ) return Audio::create_null();      // the workspace goes back idle
+	return AudioBuffer::adopt_device( get_format(), std::move( block ) );
+	}
+
+Audio & Audio::set_volume_in_place( const Function<Second, Amplitude> & level )
+	{
+	if( is_null() ) return *this;                               // :60
+	Audio out = set_volume( level );
+	if( !out.is_null() ) *this = std::move( out );
+	return *this;
+	}
+
+Audio Audio::compress( const Function<Second, Decibel> & threshold, const Function<Second, float> & compression_ratio,
+	const Function<Second, Second> & attack, const Function<Second, Second> & release, const Function<Second, Decibel> & knee_width,
+	const Audio * sidechain_source ) const
+	{
+	if( is_null() ) return Audio::create_null();                // :205
+	const Audio & side = sidechain_source ? *sidechain_source : *this;     // :207-208
+	if( side.is_null() ) return Audio::create_null();
+	if( side.get_num_frames() < get_num_frames() )
+		{
+		std::cout << "Audio::compress: the sidechain has fewer frames than the Audio it controls." << std::endl;
+		return Audio::create_null();
+		}
+	const size_t ws_bytes = flanhip_compress_workspace_bytes( get_num_frames() );
+	if( ws_bytes == 0 ) return Audio::create_null();
+	const float * d_x = device_data();
+	const float * d_side = side.device_data();
+	if( !d_x || !d_side ) return Audio::create_null();
+	const float step = frame_to_time( 1 );                       // :220-224
+	const DeviceCurve t = upload_curve( threshold, get_num_frames(), step ), r = upload_curve( compression_ratio, get_num_frames(), step ),
+		a = upload_curve( attack, get_num_frames(), step ), rel = upload_curve( release, get_num_frames(), step ),
+		k = upload_curve( knee_width, get_num_frames(), step );
+	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( get_num_channels() ) * size_t( get_num_frames() ) );
+	auto ws = detail::DeviceBlock::allocate( ws_bytes );
+	if( !t.ok || !r.ok || !a.ok || !rel.ok || !k.ok || !block || !ws ) return Audio::create_null();
+	const int rc = flanhip_compress_dev( d_x, get_num_channels(), get_num_frames(), get_sample_rate(), d_side, side.get_num_channels(),
+		side.get_num_frames(), t.ptr(), t.scalar, r.ptr(), r.scalar, a.ptr(), a.scalar, rel.ptr(), rel.scalar, k.ptr(), k.scalar,
+		static_cast<float*>( block->ptr ), nullptr, ws->ptr, nullptr );
+	if( !detail::report( rc, "compress" ) ) return Audio::create_null();
+	if( !detail::report( flanhip_stream_synchronize( nullptr ), "compress" ) ) return Audio::create_null();        // the workspace and the curves go back idle
+	return AudioBuffer::adopt_device( get_format(), std::move( block ) );
 	}
 
 } // namespace flan

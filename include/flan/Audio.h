@@ -60,6 +60,27 @@ public:
 	 *  A null *this gives a null Audio.  The result stays device-resident until read. */
 	Audio repitch( const Function<Second, float> & factor, Second granularity = .001f, WDLResampleType quality = WDLResampleType::Sinc ) const;
 
+	// ---- volume ----
+	/** Every sample times gain( t ), the same curve for every channel (Audio/AudioVolume.cpp:5-13, 32-44), on the device
+	 *  (flanhip_audio_gain_dev).  gain is sampled once per frame at f * ( 1.0f / sample rate ); a constant is passed as it is
+	 *  and samples nothing.  A null *this gives a null Audio (the in-place form leaves it as it is).  The result stays device-resident. */
+	Audio modify_volume( const Function<Second, float> & gain ) const;
+	Audio & modify_volume_in_place( const Function<Second, float> & gain );
+	/** Normalise, then scale by level( t ) (:46-67): every sample times level / get_max_sample_magnitude(), one fp32 division and one fp32
+	 *  product, on the device (flanhip_audio_set_volume_dev: the maximum never comes to the host).  As in the reference the maximum does not
+	 *  look at the last frame (AudioBuffer.cpp:416-430), and a maximum of 0 returns the input unchanged. */
+	Audio set_volume( const Function<Second, Amplitude> & level ) const;
+	Audio & set_volume_in_place( const Function<Second, Amplitude> & level );
+	/** The dynamic range compressor of :190-278 (Giannoulis, Massberg and Reiss, JAES 2012: gain computer with a soft knee, smooth decoupled
+	 *  peak detector), on the device as two scans (flanhip_compress_dev).  Every parameter is sampled once per frame; a
+	 *  constant samples nothing.  The detector reads the SIGNED maximum over the sidechain's channels, from 0 (:211-215 take no abs): frames
+	 *  whose samples are all negative detect silence.  sidechain_source: null for *this.  Where the reference reads out of bounds -- a
+	 *  sidechain with fewer frames than *this -- and for a null sidechain object the result is a null Audio; a longer sidechain is read up to
+	 *  this Audio's length and its sample rate is not looked at.  The result stays device-resident until read. */
+	Audio compress( const Function<Second, Decibel> & threshold, const Function<Second, float> & compression_ratio = 3.0f,
+		const Function<Second, Second> & attack = 5.0f / 1000.0f, const Function<Second, Second> & release = 100.0f / 1000.0f,
+		const Function<Second, Decibel> & knee_width = Decibel( 0 ), const Audio * sidechain_source = nullptr ) const;
+
 	// the older camelCase spellings BASELINE.json's north_star uses
 	PV convertToPV( Frame window_size = 2048, Frame hop = 128, Frame dft_size = 4096, flan_CANCEL_ARG ) const;
 	};

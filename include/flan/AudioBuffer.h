@@ -62,6 +62,7 @@ public:
 
 	// ---- device residency (MI355X) ----
 	bool is_device_resident() const { return mirror.is_device_resident(); }
+	bool host_copy_is_current() const { return mirror.host_copy_is_current(); }  // false: the samples live on the device only
 	const float * device_data() const { return mirror.device_data( count() ); }  // uploads on first use; nullptr on failure
 	static AudioBuffer adopt_device( const Format &, std::shared_ptr<detail::DeviceBlock> );
 	std::shared_ptr<detail::DeviceBlock> device_block() const { return mirror.device_block( count() ); }   // the shared handle on the HBM copy (uploads on first use)

@@ -501,6 +501,59 @@ int flanhip_audio_repitch(const float * audio, int64_t num_channels, int64_t num
 int flanhip_audio_repitch_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, float sample_rate, const float * inv_factors,
                               int64_t count, int64_t granularity_frames, int quality, float * d_out, void * d_workspace, void * stream);
 
+/* ---- Audio::compress: the dynamic range compressor (Audio/AudioVolume.cpp:190-278) as two scans ------------------------------ */
+/* audio: float[ch][n]; sidechain: float[side_ch][side_n], the detector's input (pass the audio itself for the reference's null
+ * sidechain_source, :207-208); out: float[ch][n], may be the audio; gain_out (may be NULL): float[n], the factor c every channel's
+ * frame is multiplied by.  Each of the five parameters is a curve of n floats (the reference samples every Function once per frame,
+ * :220-224) or, with a NULL curve, the scalar.  Everything is fp32, as in the reference:
+ *   detector input  max( 0, max_c sidechain[c][f] ): the SIGNED sample, no abs (:211-215), so a frame whose samples are all negative
+ *                   detects 0 and the audio passes unchanged; a NaN sample is never taken
+ *   per frame       x_G = 20 log10( max( |x|, 1e-6 ) ), y_G = the gain computer's three branches as written (:229-238; with a knee
+ *                   width of 0 the knee branch is never reached), x_L = x_G - y_G, alpha = exp( -1 / ( t sr ) ) (a time of 0 gives 0)
+ *   peak detector   y_1 = max( x_L, a_R y_1 + ( 1 - a_R ) x_L ), y_L = a_A y_L + ( 1 - a_A ) y_1, both from 0 (:250-251, :258-259)
+ *   output          c = pow( 10, -y_L / 20 ) once per frame (the reference recomputes it per channel), out = in * c
+ * The reference's loop is sequential over all frames; here both recurrences run as scans (flan_amd/csrc/compress.hip):
+ * every lane replays a run of frames with the reference's fp32 operations in its order, from a state carried in by an fp64 scan.
+ * log10, exp and pow are the fp64 functions rounded to fp32 once.  Deterministic (two calls agree bit for bit); c does not depend on ch.
+ * Where the reference has no defined behaviour: a sidechain shorter than the audio (it reads out of bounds there) is
+ * FLANHIP_ERR_INVALID_ARG; a longer one is read up to n; its sample rate is not looked at.  Negative or NaN times and a ratio of 0 go
+ * through the IEEE arithmetic as they come.
+ * Null audio / sidechain / out (and, for _dev, workspace), non-positive sizes, sample_rate <= 0 and side_n < n are
+ * FLANHIP_ERR_INVALID_ARG, before any device call.  The workspace need not be cleared.
+ * `cancel` is polled before the upload and before the launch; the kernels run to the end once launched. */
+/* bytes of device workspace flanhip_compress_dev needs (pure host arithmetic; 0 for arguments it refuses): five rows of n floats (n
+ * rounded up to 4) and 56 bytes per block of 256 runs.  Sized for the calling thread's flanhip_compress_debug_run setting. */
+size_t flanhip_compress_workspace_bytes(int64_t num_frames);
+int flanhip_compress(const float * audio, int64_t num_channels, int64_t num_frames, float sample_rate,
+                     const float * sidechain, int64_t side_channels, int64_t side_frames,
+                     const float * threshold_curve, float threshold, const float * ratio_curve, float ratio,
+                     const float * attack_curve, float attack, const float * release_curve, float release,
+                     const float * knee_width_curve, float knee_width,
+                     float * out, float * gain_out, volatile int * cancel);
+int flanhip_compress_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, float sample_rate,
+                         const float * d_sidechain, int64_t side_channels, int64_t side_frames,
+                         const float * d_threshold, float threshold, const float * d_ratio, float ratio,
+                         const float * d_attack, float attack, const float * d_release, float release,
+                         const float * d_knee_width, float knee_width,
+                         float * d_out, float * d_gain_out, void * d_workspace, void * stream);
+/* test hook: the frames one lane replays in the calling thread's compressions, 1 ... 64 (larger values are taken as 64; 0: the
+ * library's choice, 16).  Results do not depend on it beyond rounding. */
+void flanhip_compress_debug_run(int frames);
+
+/* ---- Audio::modify_volume (Audio/AudioVolume.cpp:5-13, 32-44) and Audio::set_volume (:46-67) --------------------------------- */
+/* out[c][f] = audio[c][f] * g[f], one fp32 product per sample, the same curve for every channel: d_gain is float[n] (the gain Function
+ * sampled at f * ( 1.0f / sr ), :36) or NULL for the scalar `gain`.  d_out may be d_audio. */
+int flanhip_audio_gain_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, const float * d_gain, float gain,
+                           float * d_out, void * stream);
+/* out[c][f] = audio[c][f] * ( level[f] / m ): one fp32 division, then one fp32 product (:66).  m = get_max_sample_magnitude() with
+ * default arguments (:63): the max |sample| over frames [0, end), end = clamp( Frame( float(N) / sr * sr ), 0, N - 1 ), so the LAST FRAME
+ * IS NOT LOOKED AT (AudioBuffer.cpp:416-430; flanhip_convolve's normalize has the same range).  m == 0 hands the input through
+ * unchanged (:65).  m is reduced and read on the device: no host round trip.  d_level: float[n] or NULL for the scalar `level`; d_out may
+ * be d_audio.  Workspace: 8192 bytes (the maximum and up to 1024 partial maxima; need not be cleared). */
+size_t flanhip_audio_set_volume_workspace_bytes(int64_t num_channels, int64_t num_frames);   /* 0 for arguments it refuses */
+int flanhip_audio_set_volume_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, float sample_rate,
+                                 const float * d_level, float level, float * d_out, void * d_workspace, void * stream);
+
 /* ---- Audio::resample (Audio/AudioConversions.cpp:14-30, r8brain CDSPResampler with default parameters) --------- */
 /* AudioConversions.cpp:22: out frames = Frame( float(num_frames) * ( dst_rate / src_rate ) ) */
 int64_t flanhip_resample_out_frames(int64_t num_frames, float src_rate, float dst_rate);
