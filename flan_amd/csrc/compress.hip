@@ -409,13 +409,12 @@ int launch_gain_apply( const float * d_in, int64_t ch, int64_t n, const float * 
 	{
 	const bool vec = n % 4 == 0 && aligned16( d_in ) && aligned16( d_out ) && aligned16( d_curve );
 	const int64_t items = vec ? n / 4 : n;
-	const unsigned blocks = (unsigned) std::min<int64_t>( ( items + 255 ) / 256, int64_t( 1 ) << 20 );
-	if( vec && d_max ) hipLaunchKernelGGL( ( k_gain_apply<true, true> ), dim3( blocks ), dim3( 256 ), 0, s, d_in, d_out, ch, n, d_curve, scalar, d_max );
-	else if( vec ) hipLaunchKernelGGL( ( k_gain_apply<true, false> ), dim3( blocks ), dim3( 256 ), 0, s, d_in, d_out, ch, n, d_curve, scalar, d_max );
-	else if( d_max ) hipLaunchKernelGGL( ( k_gain_apply<false, true> ), dim3( blocks ), dim3( 256 ), 0, s, d_in, d_out, ch, n, d_curve, scalar, d_max );
-	else hipLaunchKernelGGL( ( k_gain_apply<false, false> ), dim3( blocks ), dim3( 256 ), 0, s, d_in, d_out, ch, n, d_curve, scalar, d_max );
-	FLANHIP_CHECK( hipGetLastError() );
-	return FLANHIP_OK;
+	const int64_t blocks = std::min<int64_t>( ( items + 255 ) / 256, int64_t( 1 ) << 20 );
+	auto go = [&]( auto kernel ) { return launch_kernel( "launch_gain_apply", kernel, blocks, 256, 0, s, d_in, d_out, ch, n, d_curve, scalar, d_max ); };
+	if( vec && d_max ) return go( k_gain_apply<true, true> );
+	if( vec ) return go( k_gain_apply<true, false> );
+	if( d_max ) return go( k_gain_apply<false, true> );
+	return go( k_gain_apply<false, false> );
 	}
 
 struct CompArgs
@@ -449,24 +448,15 @@ int launch_compress( const CompArgs & a, void * d_ws, hipStream_t s )
 	Map2 * tot2 = ws_at<Map2>( d_ws, l.tot2 );
 	double * carry1 = ws_at<double>( d_ws, l.carry1 ), * carry2 = ws_at<double>( d_ws, l.carry2 );
 	const int64_t n = a.n;
-	const dim3 threads( COMP_THREADS ), grid( (unsigned) l.blocks );
-	hipLaunchKernelGGL( k_comp_level, dim3( (unsigned) ( ( n + COMP_THREADS - 1 ) / COMP_THREADS ) ), threads, 0, s,
-		a.side, a.side_ch, a.side_n, n, a.sr, a.p, xl, ar, aa );
-	FLANHIP_CHECK( hipGetLastError() );
+	// one launch of COMP_THREADS threads per block; a scan kernel comes as its { 16-byte loads, plain } pair
+	auto go = [&]( auto kernel, int64_t blocks, auto... args ) { return launch_kernel( "launch_compress", kernel, blocks, COMP_THREADS, 0, s, args... ); };
 	const bool vec = l.run % 4 == 0 && aligned16( d_ws );        // every run then starts on a 16-byte boundary of the padded rows
-	if( vec ) hipLaunchKernelGGL( k_comp_sum1<true>, grid, threads, 0, s, xl, ar, n, l.run, tot1 );
-	else hipLaunchKernelGGL( k_comp_sum1<false>, grid, threads, 0, s, xl, ar, n, l.run, tot1 );
-	FLANHIP_CHECK( hipGetLastError() );
-	hipLaunchKernelGGL( k_comp_carry<Map1>, dim3( 1 ), threads, 0, s, tot1, l.blocks, carry1 );
-	FLANHIP_CHECK( hipGetLastError() );
-	if( vec ) hipLaunchKernelGGL( k_comp_replay1<true>, grid, threads, 0, s, xl, ar, aa, n, l.run, carry1, y1, tot2 );
-	else hipLaunchKernelGGL( k_comp_replay1<false>, grid, threads, 0, s, xl, ar, aa, n, l.run, carry1, y1, tot2 );
-	FLANHIP_CHECK( hipGetLastError() );
-	hipLaunchKernelGGL( k_comp_carry<Map2>, dim3( 1 ), threads, 0, s, tot2, l.blocks, carry2 );
-	FLANHIP_CHECK( hipGetLastError() );
-	if( vec ) hipLaunchKernelGGL( k_comp_replay2<true>, grid, threads, 0, s, y1, aa, n, l.run, carry2, gain );
-	else hipLaunchKernelGGL( k_comp_replay2<false>, grid, threads, 0, s, y1, aa, n, l.run, carry2, gain );
-	FLANHIP_CHECK( hipGetLastError() );
+	if( int rc = go( k_comp_level, ( n + COMP_THREADS - 1 ) / COMP_THREADS, a.side, a.side_ch, a.side_n, n, a.sr, a.p, xl, ar, aa ) ) return rc;
+	if( int rc = vec ? go( k_comp_sum1<true>, l.blocks, xl, ar, n, l.run, tot1 ) : go( k_comp_sum1<false>, l.blocks, xl, ar, n, l.run, tot1 ) ) return rc;
+	if( int rc = go( k_comp_carry<Map1>, 1, tot1, l.blocks, carry1 ) ) return rc;
+	if( int rc = vec ? go( k_comp_replay1<true>, l.blocks, xl, ar, aa, n, l.run, carry1, y1, tot2 ) : go( k_comp_replay1<false>, l.blocks, xl, ar, aa, n, l.run, carry1, y1, tot2 ) ) return rc;
+	if( int rc = go( k_comp_carry<Map2>, 1, tot2, l.blocks, carry2 ) ) return rc;
+	if( int rc = vec ? go( k_comp_replay2<true>, l.blocks, y1, aa, n, l.run, carry2, gain ) : go( k_comp_replay2<false>, l.blocks, y1, aa, n, l.run, carry2, gain ) ) return rc;
 	if( a.gain_out ) FLANHIP_CHECK( hipMemcpyAsync( a.gain_out, gain, sizeof( float ) * size_t( n ), hipMemcpyDeviceToDevice, s ) );
 	return launch_gain_apply( a.audio, a.ch, n, gain, 0.0f, nullptr, a.out, s );
 	}
@@ -478,13 +468,6 @@ int gain_check( const void * audio, int64_t ch, int64_t n, const void * out )
 	FLANHIP_REQUIRE( ch <= COMP_MAX_CHANNELS && n <= COMP_MAX_FRAMES, FLANHIP_ERR_UNSUPPORTED, "shape out of range" );
 	return FLANHIP_OK;
 	}
-
-struct DevBuf
-	{
-	void * p = nullptr;
-	~DevBuf() { if( p ) (void) hipFree( p ); }
-	int alloc( size_t bytes ) { FLANHIP_CHECK( hipMalloc( &p, bytes ? bytes : 1 ) ); return FLANHIP_OK; }
-	};
 
 } // namespace
 
@@ -530,35 +513,24 @@ int flanhip_compress( const float * audio, int64_t num_channels, int64_t num_fra
 	if( int rc = require_device() ) return rc;
 	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
 	const size_t x_bytes = sizeof( float ) * size_t( num_channels ) * size_t( num_frames );
-	const size_t s_bytes = sizeof( float ) * size_t( side_channels ) * size_t( side_frames );
 	const size_t row = sizeof( float ) * size_t( num_frames );
 	const bool own_side = sidechain == audio && side_channels == num_channels && side_frames == num_frames;
-	DevBuf d_x, d_s, d_out, d_gain, d_ws, d_curve[5];
-	if( int rc = d_x.alloc( x_bytes ) ) return rc;
-	if( !own_side ) if( int rc = d_s.alloc( s_bytes ) ) return rc;
-	if( int rc = d_out.alloc( x_bytes ) ) return rc;
-	if( gain_out ) if( int rc = d_gain.alloc( row ) ) return rc;
-	if( int rc = d_ws.alloc( l.total ) ) return rc;
-	if( int rc = flanhip_upload( d_x.p, audio, x_bytes ) ) return rc;
-	if( !own_side ) if( int rc = flanhip_upload( d_s.p, sidechain, s_bytes ) ) return rc;
+	HostCall call( cancel );
+	void * d_ws = nullptr;
+	if( int rc = call.in( audio, x_bytes, &a.audio ) ) return rc;
+	a.side = a.audio;
+	if( !own_side ) if( int rc = call.in( sidechain, sizeof( float ) * size_t( side_channels ) * size_t( side_frames ), &a.side ) ) return rc;
+	a.gain_out = nullptr;
+	if( gain_out ) if( int rc = call.out( gain_out, row, &a.gain_out ) ) return rc;
+	if( int rc = call.out( out, x_bytes, &a.out ) ) return rc;
+	if( int rc = call.scratch( l.total, &d_ws ) ) return rc;
 	const float * curves[5] = { threshold_curve, ratio_curve, attack_curve, release_curve, knee_width_curve };
 	const float ** slots[5] = { &a.p.threshold, &a.p.ratio, &a.p.attack, &a.p.release, &a.p.knee };
 	for( int i = 0; i < 5; ++i )
-		if( curves[i] )
-			{
-			if( int rc = d_curve[i].alloc( row ) ) return rc;
-			if( int rc = flanhip_upload( d_curve[i].p, curves[i], row ) ) return rc;
-			*slots[i] = static_cast<const float*>( d_curve[i].p );
-			}
-	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
-	a.audio = static_cast<const float*>( d_x.p );
-	a.side = own_side ? a.audio : static_cast<const float*>( d_s.p );
-	a.out = static_cast<float*>( d_out.p );
-	a.gain_out = static_cast<float*>( d_gain.p );
-	if( int rc = launch_compress( a, d_ws.p, nullptr ) ) return rc;
-	if( int rc = wait_cancellable( nullptr, cancel ? poll_volatile_int : nullptr, const_cast<int*>( cancel ) ) ) return rc;
-	if( gain_out ) if( int rc = flanhip_download( gain_out, d_gain.p, row ) ) return rc;
-	return flanhip_download( out, d_out.p, x_bytes );
+		if( curves[i] ) if( int rc = call.in( curves[i], row, slots[i] ) ) return rc;
+	if( int rc = call.ready() ) return rc;
+	if( int rc = launch_compress( a, d_ws, nullptr ) ) return rc;
+	return call.finish();
 	}
 
 int flanhip_audio_gain_dev( const float * d_audio, int64_t num_channels, int64_t num_frames, const float * d_gain, float gain, float * d_out, void * stream )
@@ -587,10 +559,8 @@ int flanhip_audio_set_volume_dev( const float * d_audio, int64_t num_channels, i
 	float * partial = ws_at<float>( d_workspace, VOL_PARTIAL_OFF );
 	const int64_t end = volume_end( num_frames, sample_rate );
 	const int blocks = int( std::clamp<int64_t>( ( end + 255 ) / 256, 1, VOL_MAX_PARTIALS ) );
-	hipLaunchKernelGGL( k_absmax_partial, dim3( (unsigned) blocks ), dim3( 256 ), 0, s, d_audio, num_channels, num_frames, end, partial );
-	FLANHIP_CHECK( hipGetLastError() );
-	hipLaunchKernelGGL( k_absmax_final, dim3( 1 ), dim3( 256 ), 0, s, partial, blocks, d_max );
-	FLANHIP_CHECK( hipGetLastError() );
+	if( int rc = launch_kernel( __func__, k_absmax_partial, blocks, 256, 0, s, d_audio, num_channels, num_frames, end, partial ) ) return rc;
+	if( int rc = launch_kernel( __func__, k_absmax_final, 1, 256, 0, s, partial, blocks, d_max ) ) return rc;
 	return launch_gain_apply( d_audio, num_channels, num_frames, d_level, level, d_max, d_out, s );
 	}
 

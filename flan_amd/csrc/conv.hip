@@ -257,36 +257,25 @@ __global__ __launch_bounds__( 256 ) void k_conv_scale( float * __restrict__ out,
 
 template<int LOG2C>
 int launch_conv_ffts( bool inverse, const ConvShape & sh, const float * d_x, int64_t ch, int64_t n, const float * d_h, int64_t m,
-	char * ws, float * d_out, int normalize, int64_t end, const Plan & plan, hipStream_t s )
+	void * ws, float * d_out, int normalize, int64_t end, const Plan & plan, hipStream_t s )
 	{
-	cf * X = (cf*) ( ws + sh.x_off );
-	cf * H = (cf*) ( ws + sh.h_off );
-	cf * Y = (cf*) ( ws + sh.y_off );
-	unsigned * word = (unsigned*) ( ws + sh.word_off );
+	cf * X = ws_at<cf>( ws, sh.x_off ), * H = ws_at<cf>( ws, sh.h_off ), * Y = ws_at<cf>( ws, sh.y_off );
+	unsigned * word = ws_at<unsigned>( ws, sh.word_off );
 	const int P = sh.P;
 	if( !inverse )
 		{
-		hipLaunchKernelGGL( k_conv_spectra<LOG2C>, dim3( (unsigned) ( sh.ir_used * sh.K ) ), dim3( CONV_TEAM ), 0, s,
-			d_h, m, sh.K, sh.K, int64_t( 0 ), P, H, plan.d_tw, plan.d_tw2 );
-		FLANHIP_CHECK( hipGetLastError() );
-		hipLaunchKernelGGL( k_conv_spectra<LOG2C>, dim3( (unsigned) ( ch * sh.Jx ) ), dim3( CONV_TEAM ), 0, s,
+		if( int rc = launch_kernel( __func__, k_conv_spectra<LOG2C>, sh.ir_used * sh.K, CONV_TEAM, 0, s,
+			d_h, m, sh.K, sh.K, int64_t( 0 ), P, H, plan.d_tw, plan.d_tw2 ) ) return rc;
+		return launch_kernel( __func__, k_conv_spectra<LOG2C>, ch * sh.Jx, CONV_TEAM, 0, s,
 			d_x, n, sh.Jx, sh.J, int64_t( P ), 2 * P, X, plan.d_tw, plan.d_tw2 );
-		FLANHIP_CHECK( hipGetLastError() );
-		return FLANHIP_OK;
 		}
 	const int64_t nout = n + m;
-	if( normalize )
-		hipLaunchKernelGGL( ( k_conv_inverse<LOG2C, true> ), dim3( (unsigned) ( ch * sh.J ) ), dim3( CONV_TEAM ), 0, s,
-			Y, sh.J, nout, end, d_out, word, plan.d_tw, plan.d_tw2 );
-	else
-		hipLaunchKernelGGL( ( k_conv_inverse<LOG2C, false> ), dim3( (unsigned) ( ch * sh.J ) ), dim3( CONV_TEAM ), 0, s,
-			Y, sh.J, nout, end, d_out, word, plan.d_tw, plan.d_tw2 );
-	FLANHIP_CHECK( hipGetLastError() );
-	return FLANHIP_OK;
+	if( normalize ) return launch_kernel( __func__, k_conv_inverse<LOG2C, true>, ch * sh.J, CONV_TEAM, 0, s, Y, sh.J, nout, end, d_out, word, plan.d_tw, plan.d_tw2 );
+	return launch_kernel( __func__, k_conv_inverse<LOG2C, false>, ch * sh.J, CONV_TEAM, 0, s, Y, sh.J, nout, end, d_out, word, plan.d_tw, plan.d_tw2 );
 	}
 
 int launch_conv_ffts_any( bool inverse, const ConvShape & sh, const float * d_x, int64_t ch, int64_t n, const float * d_h, int64_t m,
-	char * ws, float * d_out, int normalize, int64_t end, const Plan & plan, hipStream_t s )
+	void * ws, float * d_out, int normalize, int64_t end, const Plan & plan, hipStream_t s )
 	{
 	switch( sh.log2P )
 		{
@@ -319,34 +308,20 @@ int launch_convolve( const float * d_x, int64_t ch, int64_t n, const float * d_h
 	if( int rc = require_device() ) return rc;
 	std::shared_ptr<const PlanRef> plan;
 	if( int rc = get_plan( 2 * sh.P, 2 * sh.P, &plan ) ) return rc;      // tw [P] and tw2 [P+1] of a 2P-point real transform
-	char * ws = static_cast<char*>( d_ws );
 	const int64_t nout = n + m;
 	const int64_t end = conv_norm_end( nout, sr );
-	if( int rc = launch_conv_ffts_any( false, sh, d_x, ch, n, d_h, m, ws, d_out, normalize, end, plan->plan, s ) ) return rc;
-	if( normalize ) FLANHIP_CHECK( hipMemsetAsync( ws + sh.word_off, 0, CONV_MAX_BYTES, s ) );
+	if( int rc = launch_conv_ffts_any( false, sh, d_x, ch, n, d_h, m, d_ws, d_out, normalize, end, plan->plan, s ) ) return rc;
+	if( normalize ) FLANHIP_CHECK( hipMemsetAsync( ws_at<char>( d_ws, sh.word_off ), 0, CONV_MAX_BYTES, s ) );
 	const int B = sh.P + 1;
 	const int bpr = ( B + CONV_DELAY_THREADS - 1 ) / CONV_DELAY_THREADS;
 	const int64_t tiles = ( sh.J + CONV_T - 1 ) / CONV_T;
-	hipLaunchKernelGGL( k_conv_delay<CONV_T>, dim3( (unsigned) ( ch * tiles * bpr ) ), dim3( CONV_DELAY_THREADS ), 0, s,
-		(const cf*) ( ws + sh.x_off ), (const cf*) ( ws + sh.h_off ), (cf*) ( ws + sh.y_off ), B, sh.J, sh.Jx, sh.K, tiles, bpr, sh.ir_used );
-	FLANHIP_CHECK( hipGetLastError() );
-	if( int rc = launch_conv_ffts_any( true, sh, d_x, ch, n, d_h, m, ws, d_out, normalize, end, plan->plan, s ) ) return rc;
-	if( normalize )
-		{
-		const int64_t count = ch * nout;
-		const unsigned blocks = (unsigned) std::min<int64_t>( ( count + 255 ) / 256, 8192 );
-		hipLaunchKernelGGL( k_conv_scale, dim3( blocks ), dim3( 256 ), 0, s, d_out, count, (const unsigned*) ( ws + sh.word_off ) );
-		FLANHIP_CHECK( hipGetLastError() );
-		}
-	return FLANHIP_OK;
+	if( int rc = launch_kernel( __func__, k_conv_delay<CONV_T>, ch * tiles * bpr, CONV_DELAY_THREADS, 0, s,
+		ws_at<const cf>( d_ws, sh.x_off ), ws_at<const cf>( d_ws, sh.h_off ), ws_at<cf>( d_ws, sh.y_off ), B, sh.J, sh.Jx, sh.K, tiles, bpr, sh.ir_used ) ) return rc;
+	if( int rc = launch_conv_ffts_any( true, sh, d_x, ch, n, d_h, m, d_ws, d_out, normalize, end, plan->plan, s ) ) return rc;
+	if( !normalize ) return FLANHIP_OK;
+	const int64_t count = ch * nout;
+	return launch_kernel( __func__, k_conv_scale, std::min<int64_t>( ( count + 255 ) / 256, 8192 ), 256, 0, s, d_out, count, ws_at<const unsigned>( d_ws, sh.word_off ) );
 	}
-
-struct DevBuf
-	{
-	void * p = nullptr;
-	~DevBuf() { if( p ) (void) hipFree( p ); }
-	int alloc( size_t bytes ) { FLANHIP_CHECK( hipMalloc( &p, bytes ? bytes : 1 ) ); return FLANHIP_OK; }
-	};
 
 } // namespace
 
@@ -388,21 +363,15 @@ int flanhip_convolve( const float * audio, int64_t num_channels, int64_t num_fra
 	if( int rc = conv_check( audio, num_channels, num_frames, ir, ir_channels, ir_frames, sample_rate, out, &sh ) ) return rc;
 	if( int rc = require_device() ) return rc;
 	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
-	const size_t x_bytes = sizeof( float ) * size_t( num_channels ) * size_t( num_frames );
-	const size_t h_bytes = sizeof( float ) * size_t( ir_channels ) * size_t( ir_frames );
-	const size_t out_bytes = sizeof( float ) * size_t( num_channels ) * size_t( num_frames + ir_frames );
-	DevBuf d_x, d_h, d_out, d_ws;
-	if( int rc = d_x.alloc( x_bytes ) ) return rc;
-	if( int rc = d_h.alloc( h_bytes ) ) return rc;
-	if( int rc = d_out.alloc( out_bytes ) ) return rc;
-	if( int rc = d_ws.alloc( sh.total ) ) return rc;
-	if( int rc = flanhip_upload( d_x.p, audio, x_bytes ) ) return rc;
-	if( int rc = flanhip_upload( d_h.p, ir, h_bytes ) ) return rc;
-	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
-	if( int rc = launch_convolve( (const float*) d_x.p, num_channels, num_frames, (const float*) d_h.p, ir_channels, ir_frames, sample_rate,
-		normalize, (float*) d_out.p, d_ws.p, nullptr ) ) return rc;
-	if( int rc = wait_cancellable( nullptr, cancel ? poll_volatile_int : nullptr, const_cast<int*>( cancel ) ) ) return rc;
-	return flanhip_download( out, d_out.p, out_bytes );
+	HostCall call( cancel );
+	const float * d_x = nullptr, * d_h = nullptr; float * d_out = nullptr; void * d_ws = nullptr;
+	if( int rc = call.in( audio, sizeof( float ) * size_t( num_channels ) * size_t( num_frames ), &d_x ) ) return rc;
+	if( int rc = call.in( ir, sizeof( float ) * size_t( ir_channels ) * size_t( ir_frames ), &d_h ) ) return rc;
+	if( int rc = call.out( out, sizeof( float ) * size_t( num_channels ) * size_t( num_frames + ir_frames ), &d_out ) ) return rc;
+	if( int rc = call.scratch( sh.total, &d_ws ) ) return rc;
+	if( int rc = call.ready() ) return rc;
+	if( int rc = launch_convolve( d_x, num_channels, num_frames, d_h, ir_channels, ir_frames, sample_rate, normalize, d_out, d_ws, nullptr ) ) return rc;
+	return call.finish();
 	}
 
 } // extern "C"

@@ -967,13 +967,6 @@ int launch_synthesize( const flanhip_MF * d_pv, int64_t ch, int64_t F, int bins,
 	return FLANHIP_OK;
 	}
 
-struct DeviceBuffer
-	{
-	void * p = nullptr;
-	~DeviceBuffer() { if( p ) (void) hipFree( p ); }
-	int alloc( size_t bytes ) { FLANHIP_CHECK( hipMalloc( &p, bytes ? bytes : 1 ) ); return FLANHIP_OK; }
-	};
-
 } // namespace flanhip
 
 using namespace flanhip;
@@ -1028,15 +1021,13 @@ int flanhip_analyze( const float * audio, int64_t ch, int64_t n, float sr, int W
 	const int bins = dft / 2 + 1;
 	if( num_pv_frames ) *num_pv_frames = F;
 	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;       // flan_CANCEL_POINT, AudioPV.cpp:49
-	DeviceBuffer d_audio, d_pv;
-	if( int rc = d_audio.alloc( sizeof( float ) * size_t( ch ) * n ) ) return rc;
-	if( int rc = d_pv.alloc( sizeof( flanhip_MF ) * size_t( ch ) * F * bins ) ) return rc;
-	if( int rc_t = flanhip_upload( d_audio.p, audio, sizeof( float ) * size_t( ch ) * n ) ) return rc_t;
-	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
-	if( int rc = launch_analyze( (const float*) d_audio.p, ch, n, sr, W, hop, dft, (flanhip_MF*) d_pv.p, nullptr, nullptr ) ) return rc;
-	if( int rc = wait_cancellable( nullptr, cancel ? poll_volatile_int : nullptr, const_cast<int*>( cancel ) ) ) return rc;   // a flag raised while the kernels run stops them (core.hip)
-	if( int rc_t = flanhip_download( out, d_pv.p, sizeof( flanhip_MF ) * size_t( ch ) * F * bins ) ) return rc_t;
-	return FLANHIP_OK;
+	HostCall call( cancel );
+	const float * d_audio = nullptr; flanhip_MF * d_pv = nullptr;
+	if( int rc = call.in( audio, sizeof( float ) * size_t( ch ) * n, &d_audio ) ) return rc;
+	if( int rc = call.out( out, sizeof( flanhip_MF ) * size_t( ch ) * F * bins, &d_pv ) ) return rc;
+	if( int rc = call.ready() ) return rc;
+	if( int rc = launch_analyze( d_audio, ch, n, sr, W, hop, dft, d_pv, nullptr, nullptr ) ) return rc;
+	return call.finish();
 	}
 
 int flanhip_synthesize_dev_stages( const flanhip_MF * d_pv, int64_t ch, int64_t F, int bins, float sr, float ar, int W,
@@ -1107,21 +1098,18 @@ int flanhip_synthesize( const flanhip_MF * pv, int64_t ch, int64_t F, int bins, 
 	if( int rc = synth_layout( ch, F, bins, sr, ar, W, &lay ) ) return rc;
 	if( int rc = require_device() ) return rc;
 	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;       // flan_CANCEL_POINT, AudioPV.cpp:115
-	const size_t pv_bytes = sizeof( flanhip_MF ) * size_t( ch ) * F * bins;
-	const size_t out_bytes = sizeof( float ) * size_t( ch ) * F * lay.hop;
-	DeviceBuffer d_pv, d_out, d_ws, d_flag;
-	if( int rc = d_pv.alloc( pv_bytes ) ) return rc;
-	if( int rc = d_out.alloc( out_bytes ) ) return rc;
-	if( int rc = d_ws.alloc( lay.total_bytes ) ) return rc;
-	if( int rc = d_flag.alloc( sizeof( int ) ) ) return rc;
-	FLANHIP_CHECK( hipMemset( d_flag.p, 0, sizeof( int ) ) );
-	if( int rc_t = flanhip_upload( d_pv.p, pv, pv_bytes ) ) return rc_t;
-	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
-	if( int rc = launch_synthesize( (const flanhip_MF*) d_pv.p, ch, F, bins, sr, ar, W, (float*) d_out.p, d_ws.p, (int*) d_flag.p, false, nullptr ) ) return rc;
-	if( int rc = wait_cancellable( nullptr, cancel ? poll_volatile_int : nullptr, const_cast<int*>( cancel ) ) ) return rc;
-	if( int rc_t = flanhip_download( out, d_out.p, out_bytes ) ) return rc_t;
+	HostCall call( cancel );
+	const flanhip_MF * d_pv = nullptr; float * d_out = nullptr; void * d_ws = nullptr; int * d_flag = nullptr;
+	if( int rc = call.in( pv, sizeof( flanhip_MF ) * size_t( ch ) * F * bins, &d_pv ) ) return rc;
+	if( int rc = call.out( out, sizeof( float ) * size_t( ch ) * F * lay.hop, &d_out ) ) return rc;
+	if( int rc = call.scratch( lay.total_bytes, &d_ws ) ) return rc;
+	if( int rc = call.scratch( sizeof( int ), &d_flag ) ) return rc;
+	FLANHIP_CHECK( hipMemset( d_flag, 0, sizeof( int ) ) );
+	if( int rc = call.ready() ) return rc;
+	if( int rc = launch_synthesize( d_pv, ch, F, bins, sr, ar, W, d_out, d_ws, d_flag, false, nullptr ) ) return rc;
+	if( int rc = call.finish() ) return rc;
 	int flag = 0;
-	FLANHIP_CHECK( hipMemcpy( &flag, d_flag.p, sizeof( int ), hipMemcpyDeviceToHost ) );
+	FLANHIP_CHECK( hipMemcpy( &flag, d_flag, sizeof( int ), hipMemcpyDeviceToHost ) );
 	if( nan_flag ) *nan_flag = flag;
 	return FLANHIP_OK;
 	}

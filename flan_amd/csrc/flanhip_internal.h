@@ -54,6 +54,54 @@ int * thread_cancel_word( hipStream_t s );
 int wait_cancellable( hipStream_t s, int ( *poll )( void * ), void * user );
 inline int poll_volatile_int( void * user ) { volatile int * c = static_cast<volatile int*>( user ); return c && *c != 0; }
 
+// An owning device allocation: hipMalloc on alloc() (zero bytes become one), hipFree when it goes
+struct DevBuf
+	{
+	void * p = nullptr;
+	DevBuf() = default;
+	DevBuf( const DevBuf & ) = delete;
+	DevBuf & operator=( const DevBuf & ) = delete;
+	~DevBuf() { if( p ) (void) hipFree( p ); }
+	int alloc( size_t bytes ) { FLANHIP_CHECK( hipMalloc( &p, bytes ? bytes : 1 ) ); return FLANHIP_OK; }
+	};
+
+// The host form of an entry point (host pointers and a cancel flag around the family's launcher): after its own argument check, require_device()
+// and the first cancellation point it names its buffers with in() / out() / scratch(), passes ready(), calls the launcher on the null
+// stream and returns finish().  Everything allocated here is freed when the HostCall goes, on every path.
+class HostCall
+	{
+	public:
+	explicit HostCall( volatile int * cancel ) : cancel_( cancel ) {}
+	template<typename T> int scratch( size_t bytes, T ** d ) { return add( nullptr, bytes, d ); }
+	template<typename T> int in( const void * host, size_t bytes, T ** d ) { if( int rc = add( nullptr, bytes, d ) ) return rc; return flanhip_upload( slots_[used_ - 1].buf.p, host, bytes ); }
+	template<typename T> int out( void * host, size_t bytes, T ** d ) { return add( host, bytes, d ); }   // downloaded by finish()
+	int ready() const { return cancelled( cancel_ ) ? FLANHIP_ERR_CANCELLED : FLANHIP_OK; }                // the cancellation point after the uploads
+	// waits for the null stream while it polls the flag (a flag raised while the kernels run stops those that read the stream's cancel word:
+	// core.hip), then downloads the outputs in the order they were named
+	int finish()
+		{
+		if( int rc = wait_cancellable( nullptr, cancel_ ? poll_volatile_int : nullptr, const_cast<int*>( cancel_ ) ) ) return rc;
+		for( int i = 0; i < used_; ++i )
+			if( slots_[i].host ) if( int rc = flanhip_download( slots_[i].host, slots_[i].buf.p, slots_[i].bytes ) ) return rc;
+		return FLANHIP_OK;
+		}
+	private:
+	static constexpr int kSlots = 12;
+	struct Slot { DevBuf buf; void * host = nullptr; size_t bytes = 0; };
+	template<typename T> int add( void * host, size_t bytes, T ** d )
+		{
+		FLANHIP_REQUIRE( used_ < kSlots, FLANHIP_ERR_UNSUPPORTED, "more buffers than a HostCall holds" );
+		Slot & s = slots_[used_++];
+		if( int rc = s.buf.alloc( bytes ) ) return rc;
+		s.host = host; s.bytes = bytes;
+		*d = static_cast<T*>( s.buf.p );
+		return FLANHIP_OK;
+		}
+	volatile int * cancel_;
+	Slot slots_[kSlots];
+	int used_ = 0;
+	};
+
 // Device tables for one (window, dft) pair on one device: the analogue of the reference's FFTHelper plan
 // (FFTHelper.cpp:16-26) plus the sampled Hann window (AudioPV.cpp:30-34).  Built once, cached (core.hip: get_plan).
 struct Plan

@@ -873,20 +873,14 @@ int flanhip_modify_time( const flanhip_MF * pv, int64_t ch, int64_t F, int bins,
 	if( int rc = check_pv_args( pv, out, ch, F, bins, sr ) ) return rc;
 	FLANHIP_REQUIRE( mod && hop >= 1 && Fo > 0, FLANHIP_ERR_INVALID_ARG, "bad map / output length" );
 	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
-	DevBuf d_pv, d_mod, d_out;
-	const size_t in_bytes = sizeof( flanhip_MF ) * size_t( ch ) * F * bins, mod_bytes = sizeof( float ) * size_t( F ) * bins;
-	const size_t out_bytes = sizeof( flanhip_MF ) * size_t( ch ) * Fo * bins;
-	if( int rc = d_pv.alloc( in_bytes ) ) return rc;
-	if( int rc = d_mod.alloc( mod_bytes ) ) return rc;
-	if( int rc = d_out.alloc( out_bytes ) ) return rc;
-	if( int rc_t = flanhip_upload( d_pv.p, pv, in_bytes ) ) return rc_t;
-	if( int rc_t = flanhip_upload( d_mod.p, mod, mod_bytes ) ) return rc_t;
-	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
-	if( int rc = flanhip_modify_time_dev( (const flanhip_MF*) d_pv.p, ch, F, bins, sr, hop, (const float*) d_mod.p, Fo, (flanhip_MF*) d_out.p, nullptr ) ) return rc;
-	FLANHIP_CHECK( hipDeviceSynchronize() );
-	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
-	if( int rc_t = flanhip_download( out, d_out.p, out_bytes ) ) return rc_t;
-	return FLANHIP_OK;
+	HostCall call( cancel );
+	const flanhip_MF * d_pv = nullptr; const float * d_mod = nullptr; flanhip_MF * d_out = nullptr;
+	if( int rc = call.in( pv, sizeof( flanhip_MF ) * size_t( ch ) * F * bins, &d_pv ) ) return rc;
+	if( int rc = call.in( mod, sizeof( float ) * size_t( F ) * bins, &d_mod ) ) return rc;
+	if( int rc = call.out( out, sizeof( flanhip_MF ) * size_t( ch ) * Fo * bins, &d_out ) ) return rc;
+	if( int rc = call.ready() ) return rc;
+	if( int rc = flanhip_modify_time_dev( d_pv, ch, F, bins, sr, hop, d_mod, Fo, d_out, nullptr ) ) return rc;
+	return call.finish();
 	}
 
 int flanhip_stretch_map_dev( float * d_factor, int64_t F, int bins, float sr, int hop, float * d_max, void * stream )
@@ -1007,22 +1001,16 @@ int flanhip_modify_frequency( const flanhip_MF * pv, int64_t ch, int64_t F, int 
 	if( int rc = check_pv_args( pv, out, ch, F, bins, sr ) ) return rc;
 	FLANHIP_REQUIRE( mod && in_modified, FLANHIP_ERR_INVALID_ARG, "null map" );
 	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
-	DevBuf d_pv, d_mod, d_inm, d_out;
-	const size_t pv_bytes = sizeof( flanhip_MF ) * size_t( ch ) * F * bins, mod_bytes = sizeof( float ) * size_t( F ) * bins;
-	const size_t inm_bytes = sizeof( float ) * size_t( ch ) * F * bins;
-	if( int rc = d_pv.alloc( pv_bytes ) ) return rc;
-	if( int rc = d_mod.alloc( mod_bytes ) ) return rc;
-	if( int rc = d_inm.alloc( inm_bytes ) ) return rc;
-	if( int rc = d_out.alloc( pv_bytes ) ) return rc;
-	if( int rc_t = flanhip_upload( d_pv.p, pv, pv_bytes ) ) return rc_t;
-	if( int rc_t = flanhip_upload( d_mod.p, mod, mod_bytes ) ) return rc_t;
-	if( int rc_t = flanhip_upload( d_inm.p, in_modified, inm_bytes ) ) return rc_t;
-	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
-	if( int rc = flanhip_modify_frequency_dev( (const flanhip_MF*) d_pv.p, ch, F, bins, sr, (const float*) d_mod.p, (const float*) d_inm.p, (flanhip_MF*) d_out.p, nullptr ) ) return rc;
-	FLANHIP_CHECK( hipDeviceSynchronize() );
-	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
-	if( int rc_t = flanhip_download( out, d_out.p, pv_bytes ) ) return rc_t;
-	return FLANHIP_OK;
+	HostCall call( cancel );
+	const flanhip_MF * d_pv = nullptr; const float * d_mod = nullptr, * d_inm = nullptr; flanhip_MF * d_out = nullptr;
+	const size_t pv_bytes = sizeof( flanhip_MF ) * size_t( ch ) * F * bins;
+	if( int rc = call.in( pv, pv_bytes, &d_pv ) ) return rc;
+	if( int rc = call.in( mod, sizeof( float ) * size_t( F ) * bins, &d_mod ) ) return rc;
+	if( int rc = call.in( in_modified, sizeof( float ) * size_t( ch ) * F * bins, &d_inm ) ) return rc;
+	if( int rc = call.out( out, pv_bytes, &d_out ) ) return rc;
+	if( int rc = call.ready() ) return rc;
+	if( int rc = flanhip_modify_frequency_dev( d_pv, ch, F, bins, sr, d_mod, d_inm, d_out, nullptr ) ) return rc;
+	return call.finish();
 	}
 
 int flanhip_repitch_map_dev( const flanhip_MF * d_pv, int64_t ch, int64_t F, int bins, float sr, float * d_factor,
@@ -1120,16 +1108,14 @@ int flanhip_shape_affine( const flanhip_MF * pv, int64_t ch, int64_t F, int bins
 	{
 	if( int rc = check_pv_args( pv, out, ch, F, bins, sr ) ) return rc;
 	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
-	DevBuf d_pv, d_out;
+	HostCall call( cancel );
+	const flanhip_MF * d_pv = nullptr; flanhip_MF * d_out = nullptr;
 	const size_t bytes = sizeof( flanhip_MF ) * size_t( ch ) * F * bins;
-	if( int rc = d_pv.alloc( bytes ) ) return rc;
-	if( int rc = d_out.alloc( bytes ) ) return rc;
-	if( int rc_t = flanhip_upload( d_pv.p, pv, bytes ) ) return rc_t;
-	if( int rc = flanhip_shape_affine_dev( (const flanhip_MF*) d_pv.p, ch, F, bins, sr, a, b, c, d, align, (flanhip_MF*) d_out.p, nullptr ) ) return rc;
-	FLANHIP_CHECK( hipDeviceSynchronize() );
-	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
-	if( int rc_t = flanhip_download( out, d_out.p, bytes ) ) return rc_t;
-	return FLANHIP_OK;
+	if( int rc = call.in( pv, bytes, &d_pv ) ) return rc;
+	if( int rc = call.out( out, bytes, &d_out ) ) return rc;
+	if( int rc = call.ready() ) return rc;
+	if( int rc = flanhip_shape_affine_dev( d_pv, ch, F, bins, sr, a, b, c, d, align, d_out, nullptr ) ) return rc;
+	return call.finish();
 	}
 
 } // extern "C"

@@ -309,13 +309,6 @@ __device__ __forceinline__ void column_scan_piped( float * lds, int64_t F, Addr 
 		}
 	}
 
-struct DevBuf
-	{
-	void * p = nullptr;
-	~DevBuf() { if( p ) (void) hipFree( p ); }
-	int alloc( size_t bytes ) { FLANHIP_CHECK( hipMalloc( &p, bytes ? bytes : 1 ) ); return FLANHIP_OK; }
-	};
-
 // Entry points that need a transient workspace take it from the stream's memory pool (hipMallocAsync).  By default the pool hands
 // its memory back to the driver at every synchronisation, so each call would pay for mapping its workspace again (milliseconds for
 // hundreds of MB); tell the device's pool once to keep what it has been given.

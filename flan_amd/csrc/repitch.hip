@@ -432,13 +432,6 @@ int launch_repitch( const float * d_x, int64_t ch, int64_t n, int64_t g, int qua
 		(const RpRun*) ( ws + l.run_off ), (const double*) d_win, groups, cpw, d_out );
 	}
 
-struct RpDevBuf
-	{
-	void * p = nullptr;
-	~RpDevBuf() { if( p ) (void) hipFree( p ); }
-	int alloc( size_t bytes ) { FLANHIP_CHECK( hipMalloc( &p, bytes ? bytes : 1 ) ); return FLANHIP_OK; }
-	};
-
 } // namespace
 
 } // namespace flanhip
@@ -511,18 +504,14 @@ int flanhip_audio_repitch( const float * audio, int64_t num_channels, int64_t nu
 	if( int rc = rp_prepare( num_channels, num_frames, sample_rate, inv_factors, count, granularity_frames, quality, &plan, &runs ) ) return rc;
 	if( int rc = require_device() ) return rc;
 	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
-	const size_t x_bytes = sizeof( float ) * size_t( num_channels ) * size_t( num_frames );
-	const size_t out_bytes = sizeof( float ) * size_t( num_channels ) * size_t( plan.out_frames );
-	RpDevBuf d_x, d_out, d_ws;
-	if( int rc = d_x.alloc( x_bytes ) ) return rc;
-	if( int rc = d_out.alloc( out_bytes ) ) return rc;
-	if( int rc = d_ws.alloc( rp_layout( int64_t( plan.blocks.size() ), int64_t( runs.size() ) ).total ) ) return rc;
-	if( int rc = flanhip_upload( d_x.p, audio, x_bytes ) ) return rc;
-	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
-	if( int rc = launch_repitch( (const float*) d_x.p, num_channels, num_frames, granularity_frames, quality, plan, runs, (float*) d_out.p, d_ws.p,
-		nullptr ) ) return rc;
-	if( int rc = wait_cancellable( nullptr, cancel ? poll_volatile_int : nullptr, const_cast<int*>( cancel ) ) ) return rc;
-	return flanhip_download( out, d_out.p, out_bytes );
+	HostCall call( cancel );
+	const float * d_x = nullptr; float * d_out = nullptr; void * d_ws = nullptr;
+	if( int rc = call.in( audio, sizeof( float ) * size_t( num_channels ) * size_t( num_frames ), &d_x ) ) return rc;
+	if( int rc = call.out( out, sizeof( float ) * size_t( num_channels ) * size_t( plan.out_frames ), &d_out ) ) return rc;
+	if( int rc = call.scratch( rp_layout( int64_t( plan.blocks.size() ), int64_t( runs.size() ) ).total, &d_ws ) ) return rc;
+	if( int rc = call.ready() ) return rc;
+	if( int rc = launch_repitch( d_x, num_channels, num_frames, granularity_frames, quality, plan, runs, d_out, d_ws, nullptr ) ) return rc;
+	return call.finish();
 	}
 
 } // extern "C"

@@ -1090,17 +1090,13 @@ int flanhip_resample( const float * in, int64_t ch, int64_t n, float src_rate, f
 	if( int rc = require_device() ) return rc;
 	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
 	const int64_t n_out = flanhip_resample_out_frames( n, src_rate, dst_rate );
-	float * d_in = nullptr; float * d_out = nullptr;
-	FLANHIP_CHECK( hipMalloc( &d_in, sizeof( float ) * size_t( ch * n ) ) );
-	if( hipMalloc( &d_out, sizeof( float ) * size_t( std::max<int64_t>( ch * n_out, 1 ) ) ) != hipSuccess ) { (void) hipFree( d_in ); set_error( "hipMalloc failed" ); return FLANHIP_ERR_HIP; }
-	int rc = FLANHIP_OK;
-	rc = flanhip_upload( d_in, in, sizeof( float ) * size_t( ch * n ) );
-	if( !rc ) rc = flanhip_resample_dev( d_in, ch, n, src_rate, dst_rate, d_out, nullptr );
-	if( !rc && hipDeviceSynchronize() != hipSuccess ) { set_error( "resample kernel failed" ); rc = FLANHIP_ERR_HIP; }
-	if( !rc && cancelled( cancel ) ) rc = FLANHIP_ERR_CANCELLED;
-	if( !rc ) rc = flanhip_download( out, d_out, sizeof( float ) * size_t( ch * n_out ) );
-	(void) hipFree( d_in ); (void) hipFree( d_out );
-	return rc;
+	HostCall call( cancel );
+	const float * d_in = nullptr; float * d_out = nullptr;
+	if( int rc = call.in( in, sizeof( float ) * size_t( ch * n ), &d_in ) ) return rc;
+	if( int rc = call.out( out, sizeof( float ) * size_t( ch * n_out ), &d_out ) ) return rc;
+	if( int rc = call.ready() ) return rc;
+	if( int rc = flanhip_resample_dev( d_in, ch, n, src_rate, dst_rate, d_out, nullptr ) ) return rc;
+	return call.finish();
 	}
 
 } // extern "C"

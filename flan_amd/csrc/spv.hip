@@ -425,12 +425,8 @@ template<int B>
 int launch_ana_b( const SpvAna & p, int64_t blocks, hipStream_t s )
 	{
 	const size_t tab_bytes = sizeof( float2 ) * size_t( p.L );
-	if( tab_bytes <= 64 * 1024 )
-		hipLaunchKernelGGL( ( k_spv_analyze<B, true> ), dim3( (unsigned) blocks ), dim3( 64 ), tab_bytes, s, p );
-	else
-		hipLaunchKernelGGL( ( k_spv_analyze<B, false> ), dim3( (unsigned) blocks ), dim3( 64 ), 0, s, p );
-	FLANHIP_CHECK( hipGetLastError() );
-	return FLANHIP_OK;
+	if( tab_bytes <= 64 * 1024 ) return launch_kernel( __func__, k_spv_analyze<B, true>, blocks, 64, tab_bytes, s, p );
+	return launch_kernel( __func__, k_spv_analyze<B, false>, blocks, 64, 0, s, p );
 	}
 
 int spv_check( int64_t ch, int64_t n, int N, float sr )
@@ -456,7 +452,6 @@ int launch_spv_analyze( const float * d_audio, int64_t ch, int64_t n, float sr, 
 	p.C = spv_analysis_chain( ch, n, N, p.tiles );
 	p.chains = ( n + p.C - 1 ) / p.C;
 	const int64_t blocks = ch * p.chains * p.tiles;
-	FLANHIP_REQUIRE( blocks < ( int64_t( 1 ) << 31 ), FLANHIP_ERR_UNSUPPORTED, "too many chains" );
 	switch( B )
 		{
 		case 1: return launch_ana_b<1>( p, blocks, s );
@@ -479,40 +474,27 @@ int launch_spv_synthesize( const flanhip_MF * d_spv, int64_t ch, int64_t n, int 
 	if( int rc = spv_check( ch, n, N, sr ) ) return rc;
 	if( int rc = require_device() ) return rc;
 	SpvSyn p;
-	p.spv = d_spv; p.carry = (double*) d_ws; p.out = d_out;
+	p.spv = d_spv; p.carry = ws_at<double>( d_ws, 0 ); p.out = d_out;
 	p.n = n; p.N = N; p.ar = sr;
 	p.C = spv_synthesis_chain( ch, n );
 	p.chains = ( n + p.C - 1 ) / p.C;
 	const int64_t blocks = ch * p.chains;
-	FLANHIP_REQUIRE( blocks < ( int64_t( 1 ) << 31 ), FLANHIP_ERR_UNSUPPORTED, "too many chains" );
 	if( p.chains > 1 )
 		{
-		const int64_t th = ch * p.chains * N;
-		hipLaunchKernelGGL( k_spv_chain_sums, dim3( (unsigned) ( ( th + 255 ) / 256 ) ), dim3( 256 ), 0, s, p, ch );
-		FLANHIP_CHECK( hipGetLastError() );
-		const int64_t tc = ch * N;
-		hipLaunchKernelGGL( k_spv_scan, dim3( (unsigned) ( ( tc + 255 ) / 256 ) ), dim3( 256 ), 0, s, p, ch );
-		FLANHIP_CHECK( hipGetLastError() );
+		const int64_t th = ch * p.chains * N, tc = ch * N;
+		if( int rc = launch_kernel( __func__, k_spv_chain_sums, ( th + 255 ) / 256, 256, 0, s, p, ch ) ) return rc;
+		if( int rc = launch_kernel( __func__, k_spv_scan, ( tc + 255 ) / 256, 256, 0, s, p, ch ) ) return rc;
 		}
 	else FLANHIP_CHECK( hipMemsetAsync( d_ws, 0, sizeof( double ) * size_t( ch ) * N, s ) );
 	const int K = ( N + SPV_SYN_THREADS - 1 ) / SPV_SYN_THREADS;
-	const dim3 g( (unsigned) blocks ), t( SPV_SYN_THREADS );
-	if( K <= 1 ) hipLaunchKernelGGL( k_spv_synthesize<1>, g, t, 0, s, p );
-	else if( K <= 2 ) hipLaunchKernelGGL( k_spv_synthesize<2>, g, t, 0, s, p );
-	else if( K <= 4 ) hipLaunchKernelGGL( k_spv_synthesize<4>, g, t, 0, s, p );
-	else if( K <= 8 ) hipLaunchKernelGGL( k_spv_synthesize<8>, g, t, 0, s, p );
-	else if( K <= 16 ) hipLaunchKernelGGL( k_spv_synthesize<16>, g, t, 0, s, p );
-	else hipLaunchKernelGGL( k_spv_synthesize<0>, g, t, 0, s, p );
-	FLANHIP_CHECK( hipGetLastError() );
-	return FLANHIP_OK;
+	auto go = [&]( auto kernel ) { return launch_kernel( "launch_spv_synthesize", kernel, blocks, SPV_SYN_THREADS, 0, s, p ); };
+	if( K <= 1 ) return go( k_spv_synthesize<1> );
+	if( K <= 2 ) return go( k_spv_synthesize<2> );
+	if( K <= 4 ) return go( k_spv_synthesize<4> );
+	if( K <= 8 ) return go( k_spv_synthesize<8> );
+	if( K <= 16 ) return go( k_spv_synthesize<16> );
+	return go( k_spv_synthesize<0> );
 	}
-
-struct DevBuf
-	{
-	void * p = nullptr;
-	~DevBuf() { if( p ) (void) hipFree( p ); }
-	int alloc( size_t bytes ) { FLANHIP_CHECK( hipMalloc( &p, bytes ? bytes : 1 ) ); return FLANHIP_OK; }
-	};
 
 } // namespace
 
@@ -546,16 +528,13 @@ int flanhip_spv_analyze( const float * audio, int64_t ch, int64_t n, float sr, i
 	if( int rc = spv_check( ch, n, num_bins, sr ) ) return rc;
 	if( int rc = require_device() ) return rc;
 	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
-	const size_t in_bytes = sizeof( float ) * size_t( ch ) * size_t( n );
-	const size_t out_bytes = sizeof( flanhip_MF ) * size_t( ch ) * size_t( n ) * size_t( num_bins );
-	DevBuf d_audio, d_out;
-	if( int rc = d_audio.alloc( in_bytes ) ) return rc;
-	if( int rc = d_out.alloc( out_bytes ) ) return rc;
-	if( int rc = flanhip_upload( d_audio.p, audio, in_bytes ) ) return rc;
-	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
-	if( int rc = launch_spv_analyze( (const float*) d_audio.p, ch, n, sr, num_bins, (flanhip_MF*) d_out.p, nullptr ) ) return rc;
-	if( int rc = wait_cancellable( nullptr, cancel ? poll_volatile_int : nullptr, const_cast<int*>( cancel ) ) ) return rc;
-	return flanhip_download( out, d_out.p, out_bytes );
+	HostCall call( cancel );
+	const float * d_audio = nullptr; flanhip_MF * d_out = nullptr;
+	if( int rc = call.in( audio, sizeof( float ) * size_t( ch ) * size_t( n ), &d_audio ) ) return rc;
+	if( int rc = call.out( out, sizeof( flanhip_MF ) * size_t( ch ) * size_t( n ) * size_t( num_bins ), &d_out ) ) return rc;
+	if( int rc = call.ready() ) return rc;
+	if( int rc = launch_spv_analyze( d_audio, ch, n, sr, num_bins, d_out, nullptr ) ) return rc;
+	return call.finish();
 	}
 
 size_t flanhip_spv_synthesize_workspace_bytes( int64_t ch, int64_t n, int num_bins, float sr )
@@ -575,17 +554,14 @@ int flanhip_spv_synthesize( const flanhip_MF * spv, int64_t ch, int64_t n, int n
 	if( int rc = spv_check( ch, n, num_bins, sr ) ) return rc;
 	if( int rc = require_device() ) return rc;
 	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
-	const size_t in_bytes = sizeof( flanhip_MF ) * size_t( ch ) * size_t( n ) * size_t( num_bins );
-	const size_t out_bytes = sizeof( float ) * size_t( ch ) * size_t( n );
-	DevBuf d_spv, d_out, d_ws;
-	if( int rc = d_spv.alloc( in_bytes ) ) return rc;
-	if( int rc = d_out.alloc( out_bytes ) ) return rc;
-	if( int rc = d_ws.alloc( spv_ws_bytes( ch, n, num_bins ) ) ) return rc;
-	if( int rc = flanhip_upload( d_spv.p, spv, in_bytes ) ) return rc;
-	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
-	if( int rc = launch_spv_synthesize( (const flanhip_MF*) d_spv.p, ch, n, num_bins, sr, (float*) d_out.p, d_ws.p, nullptr ) ) return rc;
-	if( int rc = wait_cancellable( nullptr, cancel ? poll_volatile_int : nullptr, const_cast<int*>( cancel ) ) ) return rc;
-	return flanhip_download( out, d_out.p, out_bytes );
+	HostCall call( cancel );
+	const flanhip_MF * d_spv = nullptr; float * d_out = nullptr; void * d_ws = nullptr;
+	if( int rc = call.in( spv, sizeof( flanhip_MF ) * size_t( ch ) * size_t( n ) * size_t( num_bins ), &d_spv ) ) return rc;
+	if( int rc = call.out( out, sizeof( float ) * size_t( ch ) * size_t( n ), &d_out ) ) return rc;
+	if( int rc = call.scratch( spv_ws_bytes( ch, n, num_bins ), &d_ws ) ) return rc;
+	if( int rc = call.ready() ) return rc;
+	if( int rc = launch_spv_synthesize( d_spv, ch, n, num_bins, sr, d_out, d_ws, nullptr ) ) return rc;
+	return call.finish();
 	}
 
 int flanhip_spv_modify_frequency_const_dev( const flanhip_MF * d_spv, int64_t ch, int64_t n, int num_bins, float value, int multiply,
@@ -595,10 +571,8 @@ int flanhip_spv_modify_frequency_const_dev( const flanhip_MF * d_spv, int64_t ch
 	FLANHIP_REQUIRE( ch > 0 && n > 0 && num_bins > 0, FLANHIP_ERR_INVALID_ARG, "bad sizes" );
 	if( int rc = require_device() ) return rc;
 	const int64_t count = ch * n * int64_t( num_bins );
-	const unsigned blocks = (unsigned) std::min<int64_t>( ( count + 255 ) / 256, 8192 );
-	hipLaunchKernelGGL( k_spv_modify_frequency_const, dim3( blocks ), dim3( 256 ), 0, (hipStream_t) stream, d_spv, count, value, multiply, d_out );
-	FLANHIP_CHECK( hipGetLastError() );
-	return FLANHIP_OK;
+	const int64_t blocks = std::min<int64_t>( ( count + 255 ) / 256, 8192 );
+	return launch_kernel( __func__, k_spv_modify_frequency_const, blocks, 256, 0, (hipStream_t) stream, d_spv, count, value, multiply, d_out );
 	}
 
 } // extern "C"
