@@ -438,26 +438,10 @@ __global__ __launch_bounds__( 128 * TEAMS ) void k_analyze_eo_team( AnalyzeParam
 			if( chain == 0 && role == 0 ) { p.nan_out[2] = p.nan_epoch; p.nan_out[4] = p.nan_epoch; }
 			if( any_bad ) p.nan_out[0] = p.nan_epoch;
 			}
-			{
-			if( p.group_sums )
-				{
-				// one total per group lets the synthesis kernel work out its own carries (k_analyze_v2 does the same with its groups of 8; no scan
-				// kernel between the two)
-				__syncthreads();
-				const int live = min( TEAMS, p.chains_per_channel - group * TEAMS );      // teams of this group that walked a chain
-				double * gdst = p.group_sums + ( int64_t( gchannel ) * gpc + group ) * ( N2 + 1 );
-				for( int bin = tid; bin <= N2; bin += NT )
-					{
-					double run = 0.0;
-					for( int w = 0; w < live; ++w )
-						{
-						const double v = run + reinterpret_cast<const double*>( s + L::BUF + w * ( DOUBLE ? 4 : 2 ) * L::BUF_LEN )[slot( bin )];
-						run = ( __builtin_fabs( v ) < FLANHIP_FOLD_FAST_LIMIT ) ? fold_phase_fast( v ) : fold_phase_any( v );
-						}
-					gdst[bin] = run;
-					}
-				}
-			}
+		// one total per group lets the synthesis kernel work out its own carries (no scan kernel between the two): group_total, pv_carry.h
+		if( p.group_sums )
+			group_total<N2, NT, TEAMS>( p, gchannel, gpc, group,
+				[&]( int w, int bin ) { return reinterpret_cast<const double*>( s + L::BUF + w * ( DOUBLE ? 4 : 2 ) * L::BUF_LEN ) + slot( bin ); } );
 		}
 	}
 
@@ -480,7 +464,7 @@ __global__ __launch_bounds__( 128 * TEAMS ) void k_analyze_eo_team( AnalyzeParam
 // HS = -1 (round 5): ANY hop <= window and any window -- the overlap-add accumulator is a ring of W floats per team in LDS instead of registers (one A / B
 // buffer set: the ring takes the second set's place; windows above 2048: three teams per block).  Both wavefronts add their windowed halves into the
 // ring, meet, and between that meeting and the next (the one that guards the A / B buffers anyway) send off and clear the hop samples that are final.
-// One wavefront's side of the chains' overlaps added inside a team synthesis kernel instead of by k_ola_fixup4 (round 6; k_synthesize_v2's protocol, whose
+// One wavefront's side of the chains' overlaps added inside a team synthesis kernel instead of by k_ola_fixup4 (round 6; the protocol of settle_overlap in pv_carry.h, whose
 // words explain it: a tagged word per boundary, written by atomic exchange; the head's owner says so from inside its frame loop once the head's last store
 // has been issued, behind a drained queue; the tail's owner looks a frame before its end and adds the head to its accumulator as it leaves, or deposits the
 // tail; whoever finds the other side's tag adds -- tail + head, one addition per sample, k_ola_fixup4's bits).  Every WAVEFRONT of a team runs it for its own
@@ -663,7 +647,7 @@ __global__ __launch_bounds__( 128 * TEAMS ) void k_synthesize_eo_team( SynthPara
 		const int64_t a = a0 + 4 * lane + 2 * role;
 		cf * dst = ( a0 < own_start ) ? head2 + ( ( a - chain_start ) >> 1 ) : out2 + ( a >> 1 );
 		if( a0 >= own_start && !( a >= 0 && a < p.out_len ) ) dst = dump2;
-		if( fix && a0 < own_start ) st_agent( dst, v );                          // (the head another wavefront may come to add up: the end of the kernel)
+		if( fix && a0 < own_start ) st_agent( dst, v );                          // (the head another wavefront may come to add up: ChainOverlap::finish)
 		else *dst = v;
 		};
 	// hop 128: one 128-sample half step -- the lanes 32 part .. 32 part + 31 of v hold samples a0 + 4 ( lane & 31 ) + 2 role (+1); the other lanes dump
@@ -821,69 +805,11 @@ __global__ __launch_bounds__( 128 * TEAMS ) void k_synthesize_eo_team( SynthPara
 	if( frames > 0 ) load_row( t0 );
 	if( p.group_sums )
 		{
-		// No scan over the chains ran: `carry` still holds the chains' own sums, group_carry the running phase on entry to every group of TEAMS chains.
-		// The running phase on entry to a chain = that, then the chains of this group before it, added and folded in order -- as in k_synthesize_v2, whose words
-		// these are: one thread per bin, four or five bins side by side, every load ahead of the dependent additions; every team's carries
+		// No scan over the chains ran: carry_prologue (pv_carry.h) with TEAMS chains per block, 8 group totals in flight per bin.  Every team's carries
 		// land in the team's SECOND buffer set, which nobody writes before the first meeting (one set: in the set itself, and the team meets once
 		// more before filling it).
-		auto fold = []( double r ) { return ( __builtin_fabs( r ) < FLANHIP_FOLD_FAST_LIMIT ) ? fold_phase_loop( r ) : fold_phase_any( r ); };
-		const int live = min( TEAMS, p.chains_per_channel - group * TEAMS );
-		const double * gs = ( p.group_carry ? p.group_carry : p.group_sums ) + int64_t( gchannel ) * gpc * ( N2 + 1 );
-		const double * sums0 = p.carry + ( int64_t( gchannel ) * p.chains_per_channel + int64_t( group ) * TEAMS ) * ( N2 + 1 );
-		constexpr int NB = ( N2 + NT ) / NT;                                       // bins per thread: 5 for 512 threads (the fifth only for thread 0)
-		int bins_of[NB]; bool has[NB]; double run[NB];
-		#pragma unroll
-		for( int b = 0; b < NB; ++b ) { bins_of[b] = tid + NT * b; has[b] = bins_of[b] <= N2; if( !has[b] ) bins_of[b] = N2; run[b] = 0.0; }
-		double vc[NB][TEAMS];
-		#pragma unroll
-		for( int b = 0; b < NB; ++b )
-			{
-			#pragma unroll
-			for( int w = 0; w < TEAMS; ++w ) vc[b][w] = ( w < live ) ? sums0[int64_t( w ) * ( N2 + 1 ) + bins_of[b]] : 0.0;
-			}
-		if( p.group_carry )
-			{
-			#pragma unroll
-			for( int b = 0; b < NB; ++b ) run[b] = gs[int64_t( group ) * ( N2 + 1 ) + bins_of[b]];   // the running phase on entry to this group (k_phase_scan2<SEG, true>)
-			}
-		else
-			{
-			// few groups per channel: this group adds up the totals of the groups before it itself (see k_synthesize_v2)
-			constexpr int BATCH = 8;
-			for( int g0 = 0; g0 < group; g0 += BATCH )
-				{
-				double v[NB][BATCH];
-				#pragma unroll
-				for( int b = 0; b < NB; ++b )
-					{
-					#pragma unroll
-					for( int u = 0; u < BATCH; ++u ) v[b][u] = ( g0 + u < group ) ? gs[int64_t( g0 + u ) * ( N2 + 1 ) + bins_of[b]] : 0.0;
-					}
-				#pragma unroll
-				for( int u = 0; u < BATCH; ++u )
-					{
-					#pragma unroll
-					for( int b = 0; b < NB; ++b ) run[b] = fold( run[b] + v[b][u] );       // + 0.0 past the end: fold( x ) of a folded x is x
-					}
-				}
-			}
-		#pragma unroll
-		for( int w = 0; w < TEAMS; ++w )
-			{
-			#pragma unroll
-			for( int b = 0; b < NB; ++b )
-				{
-				if( has[b] ) reinterpret_cast<double*>( s + L::BUF + w * ( DOUBLE ? 4 : 2 ) * L::BUF_LEN )[team_stage_slot<!DOUBLE>( bins_of[b], 2 * L::BUF_LEN )] = run[b];   // phase_buffer on entry to chain w of the group
-				run[b] = fold( run[b] + vc[b][w] );
-				}
-			}
-		if( tid == 0 && blockIdx.x == 0 )
-			{
-			if( p.nan_in && p.nan_flag && p.nan_in[0] == p.nan_in[2] && p.nan_in[2] != 0 ) atomicOr( p.nan_flag, 1 );
-			if( p.expect_epoch && p.nan_in && p.nan_flag && p.nan_in[2] != p.expect_epoch ) atomicOr( p.nan_flag, 2 );   // the sums in this workspace are not the noted producer's
-			if( p.skip_words ) const_cast<int*>( p.skip_words )[4] = 0;              // a handed-over pre-pass is good for one convert_to_audio (k_sums_and_groups has read the word: a launch ago)
-			}
-		__syncthreads();
+		carry_prologue<N2, NT, TEAMS, 8>( p, gchannel, gpc, group,
+			[&]( int w, int bin ) { return reinterpret_cast<double*>( s + L::BUF + w * ( DOUBLE ? 4 : 2 ) * L::BUF_LEN ) + team_stage_slot<!DOUBLE>( bin, 2 * L::BUF_LEN ); }, []() __attribute__(( always_inline )) {} );
 		const double * mine = reinterpret_cast<const double*>( buf0 );
 		auto slot = [&]( int bin ) { return team_stage_slot<!DOUBLE>( bin, 2 * L::BUF_LEN ); };
 		#pragma unroll

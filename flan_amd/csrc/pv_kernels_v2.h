@@ -17,6 +17,7 @@
 //   * the NaN / Inf scan rides on the fp64 sums (a non-finite f makes its sum non-finite) and a running maximum of m.
 #pragma once
 #include "pv_kernels_fast.h"
+#include "pv_carry.h"
 
 namespace flanhip {
 
@@ -106,17 +107,6 @@ struct Stamps
 #endif
 
 // (round_half_away_v, polar_tail / polar_v: pv_math.h)
-
-// Before a chain publishes its head's tag from inside the frame loop (k_synthesize_v2 / _v3): every store this wavefront has issued has retired.
-// FLANHIP_PUBLISH_DRAIN=0 is the A/B partner (round 5's form: the compiler's counted wait for the next row as the only proof)
-#ifndef FLANHIP_PUBLISH_DRAIN
-#define FLANHIP_PUBLISH_DRAIN 1
-#endif
-__device__ __forceinline__ void publish_drain()
-	{
-	if constexpr( FLANHIP_PUBLISH_DRAIN != 0 ) asm volatile( "s_waitcnt vmcnt(0)" ::: "memory" );
-	else asm volatile( "" ::: "memory" );
-	}
 
 // =================================================================================================================
 // Audio::convert_to_PV (Conversions/AudioPV.cpp:12-78), dft 2048
@@ -487,52 +477,9 @@ __global__ __launch_bounds__( 64 * WAVES ) void k_analyze_v2( AnalyzeParams p, F
 
 	if constexpr( SUMS )
 		{
-		// the chain's sums, folded like phase_vocoder.cpp:59, go to the workspace (what k_phase_sums2 would compute) and -- staged in this
-		// wavefront's now idle transform buffer -- into the group's total: with one total per group of 8 chains the synthesis kernel can
-		// work out its own carries (a few dozen additions per bin) and the scan kernel between the two is not launched at all
-		double * stage = reinterpret_cast<double*>( buf );                        // 1025 doubles = 8200 B of the buffer's 8712
-		bool bad = mmax >= 0x7f800000u;
-		auto fold = [&]( double sq ) -> double
-			{
-			bad |= !( __builtin_fabs( sq ) <= 1.7976931348623157e308 );              // a NaN / Inf frequency poisons its sum
-			return ( __builtin_fabs( sq ) < FLANHIP_FOLD_FAST_LIMIT ) ? fold_phase_fast( sq ) : fold_phase_any( sq );
-			};
-		if( active )
-			{
-			double * dst = p.sums + chain * ( C + 1 );
-			#pragma unroll
-			for( int q = 0; q < H; ++q )
-				{
-				const double a = fold( sumk[q] ), b = fold( summ[q] );
-				dst[lane + 64 * q] = a;             stage[lane + 64 * q] = a;
-				dst[C - lane - 64 * q] = b;         stage[C - lane - 64 * q] = b;
-				}
-			const double vx = fold( sumx );
-			if( lane == 0 ) { dst[C / 2] = vx; stage[C / 2] = vx; }
-			}
-		const bool any_bad = __any( bad );
-		if( p.nan_out && lane == 0 && active )
-			{
-			// no clearing pass: the flag word is "set" when it equals this launch's epoch (written beside it by chain 0)
-			if( chain == 0 ) { p.nan_out[2] = p.nan_epoch; p.nan_out[4] = p.nan_epoch; }   // [4]: the sums of this epoch are in the workspace
-			if( any_bad ) p.nan_out[0] = p.nan_epoch;
-			}
-		if( p.group_sums )
-			{
-			__syncthreads();
-			const int live = min( WAVES, p.chains_per_channel - group * WAVES );      // wavefronts of this group that walked a chain
-			double * gdst = p.group_sums + ( int64_t( channel ) * groups + group ) * ( C + 1 );
-			for( int bin = tid; bin <= C; bin += NT )
-				{
-				double run = 0.0;
-				for( int w = 0; w < live; ++w )
-					{
-					const double v = run + reinterpret_cast<const double*>( s + L::BUF + w * L::BUF_LEN )[bin];
-					run = ( __builtin_fabs( v ) < FLANHIP_FOLD_FAST_LIMIT ) ? fold_phase_fast( v ) : fold_phase_any( v );
-					}
-				gdst[bin] = run;
-				}
-			}
+		// the chain's sums and -- staged in this wavefront's now idle transform buffer (1025 doubles = 8200 B of its 8712) -- the group's total
+		chain_sums_epilogue<C, H, NT, WAVES>( p, sumk, summ, sumx, mmax, active, chain, lane, channel, groups, group, reinterpret_cast<double*>( buf ),
+			[&]( int w, int bin ) { return reinterpret_cast<const double*>( s + L::BUF + w * L::BUF_LEN ) + bin; } );
 		}
 	}
 
@@ -545,19 +492,6 @@ __global__ __launch_bounds__( 64 * WAVES ) void k_analyze_v2( AnalyzeParams p, F
 //     row t + 1 ] -- so that the wait for the MF row is a counted one that leaves the output stores in flight;
 //   * the MF rows are read once: non-temporal loads.
 // =================================================================================================================
-// 8-byte loads / stores that other XCDs' wavefronts see inside a launch (agent scope: the L2s of two XCDs are not coherent for ordinary accesses)
-__device__ __forceinline__ void st_agent( cf * p, cf v )
-	{
-	unsigned long long bits; __builtin_memcpy( &bits, &v, 8 );
-	__hip_atomic_store( reinterpret_cast<unsigned long long*>( p ), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
-	}
-__device__ __forceinline__ cf ld_agent( const cf * p )
-	{
-	const unsigned long long bits = __hip_atomic_load( reinterpret_cast<const unsigned long long*>( p ), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
-	cf v; __builtin_memcpy( &v, &bits, 8 );
-	return v;
-	}
-
 struct V2LdsSyn
 	{
 	static constexpr int C = 1024;
@@ -677,7 +611,7 @@ __global__ __launch_bounds__( 64 * WAVES ) void k_synthesize_v2( SynthParams p, 
 		const int64_t a = a0 + 2 * lane;
 		cf * dst = ( a0 < own_start ) ? head2 + ( ( a - chain_start ) >> 1 ) : out2 + ( a >> 1 );
 		if( ( ABL & 4 ) || ( a0 >= own_start && !( a >= 0 && a < p.out_len ) ) ) dst = dump2;           // ABL 4 (timing only): every store to the dump area
-		if( fix && a0 < own_start ) st_agent( dst, v );                          // (the head another wavefront may come to add up: see the end of the kernel)
+		if( fix && a0 < own_start ) st_agent( dst, v );                          // (the head another wavefront may come to add up: settle_overlap, pv_carry.h)
 		else *dst = v;
 		};
 	// MF row of frame t: ( m, f ) of the lane's pairs and of bin C/2
@@ -701,76 +635,10 @@ __global__ __launch_bounds__( 64 * WAVES ) void k_synthesize_v2( SynthParams p, 
 	double phk[H], phm[H], phx;
 	if( p.group_sums )
 		{
-		// no scan over the chains ran: `carry` still holds the chains' own sums, group_carry the running phase on entry to every group of 8 chains
-		// (a scan over the producer's group totals: an eighth of the elements).  The running phase on entry to this chain = that, then the chains of
-		// this group before this one, added and folded in order (phase_vocoder.cpp:57-59 modulo pi2: the prefix k_phase_scan2 forms, associated group-wise).
-		// x + y folded like phase_vocoder.cpp:59: the branch-free fold of the frame loop (pv_math.h) wherever it is exact, i.e. always but
-		// for sums beyond 3e9 rad or NaN, which take the general routine
-		auto fold = []( double r )
-			{
-			return ( __builtin_fabs( r ) < FLANHIP_FOLD_FAST_LIMIT ) ? fold_phase_loop( r ) : fold_phase_any( r );
-			};
-		// One thread per bin, its two or three bins side by side (independent dependency chains), along the chains of this group, leaving every
-		// wavefront's carries in that wavefront's own transform buffer (1025 doubles of its 8712 bytes).  Every load goes out ahead of the
-		// dependent additions: one memory round trip.
-		const double * gs = ( p.group_carry ? p.group_carry : p.group_sums ) + int64_t( channel ) * groups * ( C + 1 );
-		const double * sums0 = p.carry + ( int64_t( channel ) * p.chains_per_channel + int64_t( group ) * WAVES ) * ( C + 1 );   // the first chain of this group
-		const int live = min( WAVES, p.chains_per_channel - group * WAVES );
-		constexpr int NB = ( C + NT ) / NT;                                       // bins per thread: 3 for 512 threads (the third only for thread 0)
-		int bins_of[NB]; bool has[NB]; double run[NB];
-		#pragma unroll
-		for( int b = 0; b < NB; ++b ) { bins_of[b] = tid + NT * b; has[b] = bins_of[b] <= C; if( !has[b] ) bins_of[b] = C; run[b] = 0.0; }
-		double vc[NB][WAVES];                                                     // the chains of this group: requested first, used last
-		#pragma unroll
-		for( int b = 0; b < NB; ++b )
-			{
-			#pragma unroll
-			for( int w = 0; w < WAVES; ++w ) vc[b][w] = ( w < live ) ? sums0[int64_t( w ) * ( C + 1 ) + bins_of[b]] : 0.0;
-			}
-		if( p.group_carry )
-			{
-			#pragma unroll
-			for( int b = 0; b < NB; ++b ) run[b] = gs[int64_t( group ) * ( C + 1 ) + bins_of[b]];   // the running phase on entry to this group (k_phase_scan2<SEG, true>)
-			}
-		if( active ) load_row( relf0 );                                           // the first MF row travels while the carries are worked out
-		if( !p.group_carry )
-			{
-			// few groups per channel (the host's choice): no scan over the group totals was launched -- this group adds up the totals of the groups
-			// before it itself, 16 loads per bin in flight (group g reads g totals: O(groups^2) bytes in all, cheaper than a kernel up to ~40 groups)
-			for( int g0 = 0; g0 < group; g0 += 16 )
-				{
-				double v[NB][16];
-				#pragma unroll
-				for( int b = 0; b < NB; ++b )
-					{
-					#pragma unroll
-					for( int u = 0; u < 16; ++u ) v[b][u] = ( g0 + u < group ) ? gs[int64_t( g0 + u ) * ( C + 1 ) + bins_of[b]] : 0.0;
-					}
-				#pragma unroll
-				for( int u = 0; u < 16; ++u )
-					{
-					#pragma unroll
-					for( int b = 0; b < NB; ++b ) run[b] = fold( run[b] + v[b][u] );      // + 0.0 past the end: fold( x ) of a folded x is x
-					}
-				}
-			}
-		#pragma unroll
-		for( int w = 0; w < WAVES; ++w )
-			{
-			#pragma unroll
-			for( int b = 0; b < NB; ++b )
-				{
-				if( has[b] ) reinterpret_cast<double*>( s + L::BUF + w * L::BUF_LEN )[bins_of[b]] = run[b];   // phase_buffer on entry to chain w of the group
-				run[b] = fold( run[b] + vc[b][w] );
-				}
-			}
-		if( tid == 0 && blockIdx.x == 0 )
-			{
-			if( p.nan_in && p.nan_flag && p.nan_in[0] == p.nan_in[2] && p.nan_in[2] != 0 ) atomicOr( p.nan_flag, 1 );
-			if( p.expect_epoch && p.nan_in && p.nan_flag && p.nan_in[2] != p.expect_epoch ) atomicOr( p.nan_flag, 2 );   // the sums in this workspace are not the noted producer's
-			if( p.skip_words ) const_cast<int*>( p.skip_words )[4] = 0;              // a handed-over pre-pass is good for one convert_to_audio (k_sums_and_groups has read the word: a launch ago)
-			}
-		__syncthreads();
+		// the carries of the block's chains, left in every wavefront's own transform buffer (1025 doubles of its 8712 bytes); the first MF row travels meanwhile
+		carry_prologue<C, NT, WAVES, 16>( p, channel, groups, group,
+			[&]( int w, int bin ) { return reinterpret_cast<double*>( s + L::BUF + w * L::BUF_LEN ) + bin; },
+			[&]() { if( active ) load_row( relf0 ); } );
 		const double * mine = reinterpret_cast<const double*>( buf );
 		#pragma unroll
 		for( int q = 0; q < H; ++q ) { phk[q] = mine[lane + 64 * q]; phm[q] = mine[C - lane - 64 * q]; }
@@ -885,17 +753,10 @@ __global__ __launch_bounds__( 64 * WAVES ) void k_synthesize_v2( SynthParams p, 
 	bins_of_row();
 	int64_t pos = chain_start;
 	int rel = 0;                                                                // pos - chain_start: the same number in every wavefront, a scalar
-	// ---- the overlaps of neighbouring chains added here instead of by a launch of their own (k_ola_fixup: a launch and two round trips to memory
-	// behind every convert_to_audio; p.fix_state set).  The W - hop samples at a boundary get the LAST partial sums of the chain before it (in its
-	// `acc` when it ends) and the FIRST ones of the chain after it (in its `head` buffer since its first frames).  One word per boundary, tagged with
-	// the launch's epoch, written by atomic exchange; whoever finds the other side's tag there adds the two halves, so no wavefront ever waits for
-	// another and the order in which blocks are scheduled cannot matter.  Round 5: the head's owner publishes INSIDE its frame loop, as soon as the
-	// loop's own counted wait has proven the head's stores acknowledged (memory operations retire in order) -- in a launch of one round that is
-	// ~100 us before its neighbour ends; the tail's owner reads the word one frame before its last (the answer arrives under that frame's row wait),
-	// requests the head under its LAST transform and adds it to its accumulator as it leaves: no exchange, no round trip at the end of the launch
-	// (round 4's form -- both sides at their ends -- cost the launch the 5-7 us the separate kernel took).  The halves cross XCDs inside a launch:
-	// written and read at agent scope (st_agent / ld_agent).  One addition per sample, tail + head, as k_ola_fixup does it: the same bits.
-	const int tag_tail = p.fix_tag | 1, tag_head = p.fix_tag | 2;
+	// ---- the overlaps of neighbouring chains added here instead of by a launch of their own (p.fix_state set; the protocol: settle_overlap, pv_carry.h).
+	// In the loop: the head's owner publishes its tag at frame i_pub, the tail's owner peeks at the word one frame before its last and requests the
+	// neighbour's head under its LAST transform; settle_overlap behind the loop does the rest
+	const int tag_head = p.fix_tag | 2;
 	const int nsteps = p.head_len / 128;                                        // steps of 128 samples a boundary holds (W - hop, a multiple of 128 here)
 	const bool has_head = chain_in_channel != 0, has_tail = !last_chain;
 	int * const word_h = p.fix_state + chain, * const word_t = p.fix_state + ( chain + 1 );      // (used under `fix` only)
@@ -1026,59 +887,7 @@ __global__ __launch_bounds__( 64 * WAVES ) void k_synthesize_v2( SynthParams p, 
 			}
 		for( int64_t a0 = pos + 128 * E; a0 < flush_end; a0 += 128 ) emit_step( a0, mk( 0.0f, 0.0f ) );
 		}
-	if( fix )
-		{
-		if( has_head && !published )
-			{
-			// a chain too short to have published from its loop: now, behind a drained queue
-			asm volatile( "s_waitcnt vmcnt(0)" ::: "memory" );
-			if( lane == 0 ) old_h = __hip_atomic_exchange( word_h, tag_head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
-			}
-		if( has_tail )
-			{
-			// this chain's tail meets the next chain's head
-			cf * tail_next = reinterpret_cast<cf*>( p.tail + ( chain + 1 ) * p.head_len ) + lane;
-			bool add = have_head;
-			if( !add )
-				{
-				// the neighbour had not published a frame ago (a launch of several rounds, a chain of one frame): leave the tail where it will
-				// find it, BEHIND a drained queue, and say so; if its tag has appeared meanwhile the addition is ours after all
-				#pragma unroll
-				for( int q = 0; q < E; ++q ) if( q < nsteps ) st_agent( tail_next + 64 * q, acc[q] );
-				asm volatile( "s_waitcnt vmcnt(0)" ::: "memory" );
-				int old = 0;
-				if( lane == 0 ) old = __hip_atomic_exchange( word_t, tag_tail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
-				add = __builtin_amdgcn_readfirstlane( old ) == tag_head;
-				if( add )
-					{
-					#pragma unroll
-					for( int q = 0; q < E; ++q ) hx[q] = ( q < nsteps ) ? ld_agent( head_next + 64 * q ) : mk( 0.0f, 0.0f );
-					}
-				}
-			if( add )
-				{
-				#pragma unroll
-				for( int q = 0; q < E; ++q )
-					{
-					const int64_t a = pos + 128 * q + 2 * lane;
-					if( q < nsteps && a >= 0 && a < p.out_len ) out2[a >> 1] = mk( acc[q].x + hx[q].x, acc[q].y + hx[q].y );
-					}
-				}
-			}
-		if( has_head && __builtin_amdgcn_readfirstlane( old_h ) == tag_tail )
-			{
-			// this chain's head meets the previous chain's tail, which was there when the head's tag went out
-			const cf * tl = reinterpret_cast<const cf*>( p.tail + chain * p.head_len ) + lane;
-			const cf * hd = head2 + lane;
-			#pragma unroll 4
-			for( int q = 0; q < nsteps; ++q )
-				{
-				const cf t = ld_agent( tl + 64 * q ), h = ld_agent( hd + 64 * q );
-				const int64_t a = chain_start + 128 * q + 2 * lane;
-				if( a >= 0 && a < p.out_len ) out2[a >> 1] = mk( t.x + h.x, t.y + h.y );
-				}
-			}
-		}
+	if( fix ) settle_overlap( p, acc, hx, have_head, published, old_h, has_head, has_tail, chain, chain_start, pos, lane, out2 );   // pv_carry.h
 	st.flush( lane );
 	}
 

@@ -410,50 +410,9 @@ __global__ __launch_bounds__( 64 * WAVES, OCC ) void k_analyze_v3( AnalyzeParams
 
 	if constexpr( SUMS )
 		{
-		// the chain's sums, folded like phase_vocoder.cpp:59, go to the workspace (what k_phase_sums2 would compute) and -- staged in this
-		// wavefront's now idle transform buffer -- into the group's total (see k_analyze_v2)
-		double * stage = reinterpret_cast<double*>( buf );
-		bool bad = mmax >= 0x7f800000u;
-		auto fold = [&]( double sq ) -> double
-			{
-			bad |= !( __builtin_fabs( sq ) <= 1.7976931348623157e308 );              // a NaN / Inf frequency poisons its sum
-			return ( __builtin_fabs( sq ) < FLANHIP_FOLD_FAST_LIMIT ) ? fold_phase_fast( sq ) : fold_phase_any( sq );
-			};
-		if( active )
-			{
-			double * dst = p.sums + chain * ( C + 1 );
-			#pragma unroll
-			for( int q = 0; q < H; ++q )
-				{
-				const double a = fold( sumk[q] ), b = fold( summ[q] );
-				dst[lane + 64 * q] = a;             stage[lane + 64 * q] = a;
-				dst[C - lane - 64 * q] = b;         stage[C - lane - 64 * q] = b;
-				}
-			const double vx = fold( sumx );
-			if( lane == 0 ) { dst[C / 2] = vx; stage[C / 2] = vx; }
-			}
-		const bool any_bad = __any( bad );
-		if( p.nan_out && lane == 0 && active )
-			{
-			if( chain == 0 ) { p.nan_out[2] = p.nan_epoch; p.nan_out[4] = p.nan_epoch; }   // [4]: the sums of this epoch are in the workspace
-			if( any_bad ) p.nan_out[0] = p.nan_epoch;
-			}
-		if( p.group_sums )
-			{
-			__syncthreads();
-			const int live = min( WAVES, p.chains_per_channel - group * WAVES );      // wavefronts of this group that walked a chain
-			double * gdst = p.group_sums + ( int64_t( channel ) * groups + group ) * ( C + 1 );
-			for( int bin = tid; bin <= C; bin += NT )
-				{
-				double run = 0.0;
-				for( int w = 0; w < live; ++w )
-					{
-					const double v = run + reinterpret_cast<const double*>( s + L::buf0( true ) + w * L::BUF_LEN )[bin];
-					run = ( __builtin_fabs( v ) < FLANHIP_FOLD_FAST_LIMIT ) ? fold_phase_fast( v ) : fold_phase_any( v );
-					}
-				gdst[bin] = run;
-				}
-			}
+		// the chain's sums and -- staged in this wavefront's now idle transform buffer -- the group's total
+		chain_sums_epilogue<C, H, NT, WAVES>( p, sumk, summ, sumx, mmax, active, chain, lane, channel, groups, group, reinterpret_cast<double*>( buf ),
+			[&]( int w, int bin ) { return reinterpret_cast<const double*>( s + L::buf0( true ) + w * L::BUF_LEN ) + bin; } );
 		}
 	}
 
@@ -584,7 +543,8 @@ __global__ __launch_bounds__( 64 * WAVES, OCC ) void k_synthesize_v3( SynthParam
 	double phk[H], phm[H], phx;
 	if( p.group_sums )
 		{
-		// the carry prologue of k_synthesize_v2: group_carry (or the totals of the groups before this one) + the chains of this group before this chain
+		// carry_prologue (pv_carry.h), statement for statement, as this kernel's OWN text: called as the shared function the dft 1024 instantiations come out of the
+		// compiler with 16 more bytes of scratch each and their synthesis measured 1.5-2 % slower (interleaved A/B, 8 ch x 60 s); any change there is repeated here
 		auto fold = []( double r )
 			{
 			return ( __builtin_fabs( r ) < FLANHIP_FOLD_FAST_LIMIT ) ? fold_phase_loop( r ) : fold_phase_any( r );
@@ -752,10 +712,10 @@ __global__ __launch_bounds__( 64 * WAVES, OCC ) void k_synthesize_v3( SynthParam
 	bins_of_row();
 	int64_t pos = chain_start;
 	int rel = 0;
-	// the overlaps of neighbouring chains added by the chains themselves (p.fix_state set): k_synthesize_v2's protocol, statement for statement --
-	// a tagged word per boundary, the head's owner publishing from inside its frame loop, the tail's owner reading the word a frame before its last
-	// and requesting the head under its last transform
-	const int tag_tail = p.fix_tag | 1, tag_head = p.fix_tag | 2;
+	// the overlaps of neighbouring chains added by the chains themselves (p.fix_state set): k_synthesize_v2's in-loop steps, statement for statement -- the
+	// head's owner publishing from inside its frame loop, the tail's owner reading the word a frame before its last and requesting the head under its
+	// last transform -- and settle_overlap (pv_carry.h) behind the loop
+	const int tag_head = p.fix_tag | 2;
 	const int nsteps = p.head_len / 128;
 	const bool has_head = chain_in_channel != 0, has_tail = !last_chain;
 	int * const word_h = p.fix_state + chain, * const word_t = p.fix_state + ( chain + 1 );      // (used under `fix` only)
@@ -840,7 +800,7 @@ __global__ __launch_bounds__( 64 * WAVES, OCC ) void k_synthesize_v3( SynthParam
 			bins_of_row();
 			if( fix && has_head && i == i_pub )
 				{
-				publish_drain();                                                 // (the head's stores have retired: an explicit drain, once per chain -- pv_kernels_v2.h)
+				publish_drain();                                                 // (the head's stores have retired: an explicit drain, once per chain -- pv_carry.h)
 				if( lane == 0 ) old_h = __hip_atomic_exchange( word_h, tag_head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
 				asm volatile( "" ::: "memory" );
 				published = true;
@@ -878,54 +838,7 @@ __global__ __launch_bounds__( 64 * WAVES, OCC ) void k_synthesize_v3( SynthParam
 			}
 		for( int64_t a0 = pos + 128 * E; a0 < flush_end; a0 += 128 ) emit_step( a0, mk( 0.0f, 0.0f ) );
 		}
-	if( fix )
-		{
-		if( has_head && !published )
-			{
-			asm volatile( "s_waitcnt vmcnt(0)" ::: "memory" );
-			if( lane == 0 ) old_h = __hip_atomic_exchange( word_h, tag_head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
-			}
-		if( has_tail )
-			{
-			cf * tail_next = reinterpret_cast<cf*>( p.tail + ( chain + 1 ) * p.head_len ) + lane;
-			bool add = have_head;
-			if( !add )
-				{
-				#pragma unroll
-				for( int q = 0; q < E; ++q ) if( q < nsteps ) st_agent( tail_next + 64 * q, acc[q] );
-				asm volatile( "s_waitcnt vmcnt(0)" ::: "memory" );
-				int old = 0;
-				if( lane == 0 ) old = __hip_atomic_exchange( word_t, tag_tail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
-				add = __builtin_amdgcn_readfirstlane( old ) == tag_head;
-				if( add )
-					{
-					#pragma unroll
-					for( int q = 0; q < E; ++q ) hx[q] = ( q < nsteps ) ? ld_agent( head_next + 64 * q ) : mk( 0.0f, 0.0f );
-					}
-				}
-			if( add )
-				{
-				#pragma unroll
-				for( int q = 0; q < E; ++q )
-					{
-					const int64_t a = pos + 128 * q + 2 * lane;
-					if( q < nsteps && a >= 0 && a < p.out_len ) out2[a >> 1] = mk( acc[q].x + hx[q].x, acc[q].y + hx[q].y );
-					}
-				}
-			}
-		if( has_head && __builtin_amdgcn_readfirstlane( old_h ) == tag_tail )
-			{
-			const cf * tl = reinterpret_cast<const cf*>( p.tail + chain * p.head_len ) + lane;
-			const cf * hd = head2 + lane;
-			#pragma unroll 4
-			for( int q = 0; q < nsteps; ++q )
-				{
-				const cf t = ld_agent( tl + 64 * q ), h = ld_agent( hd + 64 * q );
-				const int64_t a = chain_start + 128 * q + 2 * lane;
-				if( a >= 0 && a < p.out_len ) out2[a >> 1] = mk( t.x + h.x, t.y + h.y );
-				}
-			}
-		}
+	if( fix ) settle_overlap( p, acc, hx, have_head, published, old_h, has_head, has_tail, chain, chain_start, pos, lane, out2 );   // pv_carry.h
 	}
 
 } // namespace flanhip

@@ -4,9 +4,13 @@
     python tools/ab_libs.py --a flan_amd/libflanhip_base.so --b flan_amd/libflanhip.so [--dft 2048] [--hop 512] [--rounds 9] [--reps 20]
 
 Per library: median / min ms of the fused analysis launch, of everything convert_to_audio launches, and of the whole step, on the bench
-shape (8 ch x 60 s); and whether B's PV and audio are bit-identical to A's.
+shape (8 ch x 60 s); and whether B's PV, audio and NaN flag word are bit-identical to A's.
+--no-timing: one fused analysis and one fused synthesis per library, then the comparison only.  --chain-len N, --inline-fixup M, --no-sub: the
+chain_len / inline_fixup / no_sub debug hooks, set in both libraries (flan_amd.debug_options).  main( argv ) may be called again and again in one
+process: the libraries are loaded once.
 """
 import argparse
+import contextlib
 import ctypes
 import importlib.util
 import json
@@ -26,7 +30,17 @@ def load(name, path):
     return m
 
 
-def main():
+_LOADED = {}
+
+
+def load_once(name, path):
+    key = (name, os.path.abspath(path))
+    if key not in _LOADED:
+        _LOADED[key] = load(name, path)
+    return _LOADED[key]
+
+
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--a", required=True)
     ap.add_argument("--b", required=True)
@@ -38,10 +52,21 @@ def main():
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default="")
-    args = ap.parse_args()
-    import numpy as np
+    ap.add_argument("--chain-len", type=int, default=0, help="frames per chain (the chain_len debug hook; 0: the library's choice)")
+    ap.add_argument("--inline-fixup", type=int, default=0, help="the inline_fixup debug hook: 0 the library's choice, 1 the overlaps inside the kernel, 2 by the separate launch")
+    ap.add_argument("--no-sub", action="store_true", help="the no_sub debug hook: dft 512 by the one-wavefront kernels")
+    ap.add_argument("--no-timing", action="store_true", help="one analysis and one synthesis per library, then the comparison")
+    args = ap.parse_args(argv)
     import torch
-    libs = {"A": load("fa_a", args.a), "B": load("fa_b", args.b)}
+    libs = {"A": load_once("fa_a", args.a), "B": load_once("fa_b", args.b)}
+    hooks = {"chain_len": args.chain_len, "inline_fixup": args.inline_fixup, "no_sub": int(args.no_sub)}
+    with contextlib.ExitStack() as stack:
+        for fa in libs.values():
+            stack.enter_context(fa.debug_options(**hooks))
+        return run(args, libs, hooks, torch)
+
+
+def run(args, libs, hooks, torch):
     W, HOP, DFT, SR = args.window, args.hop, args.dft, 48000.0
     BINS = DFT // 2 + 1
     dev = torch.device("cuda", 0)
@@ -77,29 +102,36 @@ def main():
         return e0.elapsed_time(e1) / reps
 
     for k in libs:                                   # warm-up (and the device's clocks)
-        for _ in range(150):
+        for _ in range(1 if args.no_timing else 150):
             ana(k); syn(k)
     torch.cuda.synchronize()
-    for r in range(args.rounds):
+    for r in range(0 if args.no_timing else args.rounds):
         for k in (("A", "B") if r % 2 == 0 else ("B", "A")):
             st[k]["ana"].append(timed(lambda: ana(k), args.reps))
             st[k]["syn"].append(timed(lambda: syn(k), args.reps))
             st[k]["step"].append(timed(lambda: (ana(k), syn(k)), args.reps))
-    res = {"shape": {"channels": ch, "seconds": args.seconds, "window": W, "hop": HOP, "dft": DFT, "frames": ch * st["A"]["F"]}}
+    res = {"shape": {"channels": ch, "seconds": args.seconds, "window": W, "hop": HOP, "dft": DFT, "frames": ch * st["A"]["F"]}, "hooks": hooks}
+    if args.chain_len:
+        res["shape"]["chains_per_channel"] = -(-st["A"]["F"] // args.chain_len)
     for k in libs:
         res[k] = {"lib": args.a if k == "A" else args.b}
         for what in ("ana", "syn", "step"):
             v = sorted(st[k][what])
-            res[k][what + "_ms_median"] = round(v[len(v) // 2], 5)
-            res[k][what + "_ms_min"] = round(v[0], 5)
-    res["B_over_A"] = {w: round(res["B"][w + "_ms_median"] / res["A"][w + "_ms_median"], 4) for w in ("ana", "syn", "step")}
+            if v:
+                res[k][what + "_ms_median"] = round(v[len(v) // 2], 5)
+                res[k][what + "_ms_min"] = round(v[0], 5)
+    if not args.no_timing:
+        res["B_over_A"] = {w: round(res["B"][w + "_ms_median"] / res["A"][w + "_ms_median"], 4) for w in ("ana", "syn", "step")}
     res["pv_bit_identical"] = bool(torch.equal(st["A"]["pv"].view(torch.int32), st["B"]["pv"].view(torch.int32)))
     res["audio_bit_identical"] = bool(torch.equal(st["A"]["out"].view(torch.int32), st["B"]["out"].view(torch.int32)))
+    res["flag_word"] = {k: int(st[k]["flag"].item()) for k in libs}
+    res["flag_identical"] = res["flag_word"]["A"] == res["flag_word"]["B"]
     line = json.dumps(res)
     print(line)
     if args.out:
         with open(args.out, "w") as f:
             f.write(line + "\n")
+    return res
 
 
 if __name__ == "__main__":
