@@ -148,6 +148,10 @@ _SIGS = {
     "flanhip_audio_gain_dev": (C.c_int, [_vp, _i64, _i64, _vp, _f32, _vp, _vp]),
     "flanhip_audio_set_volume_workspace_bytes": (C.c_size_t, [_i64, _i64]),
     "flanhip_audio_set_volume_dev": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _f32, _vp, _vp, _vp]),
+    "flanhip_filter_1pole_workspace_bytes": (C.c_size_t, [_i64, _i64]),
+    "flanhip_filter_1pole": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _f32, _i32, _i32, _vp, _vp]),
+    "flanhip_filter_1pole_dev": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _f32, _i32, _i32, _vp, _vp, _vp]),
+    "flanhip_filter_debug_run": (None, [_i32]),
 }
 
 EXPORTS = sorted(_SIGS)
@@ -881,3 +885,50 @@ def audio_set_volume_dev(d_audio, ch, n, sample_rate, level, d_out, d_ws, stream
     scalar = isinstance(level, (int, float, np.floating))
     check(lib.flanhip_audio_set_volume_dev(_dp(d_audio), ch, n, sample_rate, None if scalar else _dp(level), float(level) if scalar else 0.0,
                                            _dp(d_out), _dp(d_ws), _vp(stream or 0)))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Audio::filter_1pole_lowpass / _highpass / _repeat_low / _repeat_high.  The cutoff is a float (the scalar) or an array of n floats (a curve)
+# ---------------------------------------------------------------------------------------------------------------
+
+FILTER_BUTTERWORTH_LOW, FILTER_BUTTERWORTH_HIGH, FILTER_REPEAT_LOW, FILTER_REPEAT_HIGH = 0, 1, 2, 3
+
+
+def filter_1pole_workspace_bytes(ch, n):
+    return int(lib.flanhip_filter_1pole_workspace_bytes(ch, n))
+
+
+def filter_1pole(audio, sample_rate, cutoff, kind=FILTER_BUTTERWORTH_LOW, order=1):
+    """Audio::filter_1pole_lowpass / _highpass (the Butterworth kinds, order N) and filter_1pole_repeat_low / _high (the repeat kinds,
+    order = repeats).  audio float32 [ch][n] -> float32 [ch][n]."""
+    audio = np.ascontiguousarray(audio, np.float32)
+    ch, n = audio.shape
+    scalar = isinstance(cutoff, (int, float, np.floating))
+    curve = None if scalar else np.ascontiguousarray(cutoff, np.float32)
+    assert scalar or curve.shape == (n,), curve.shape
+    out = np.empty_like(audio)
+    check(lib.flanhip_filter_1pole(_ptr(audio), ch, n, sample_rate, None if scalar else _ptr(curve), float(cutoff) if scalar else 0.0,
+                                   kind, order, _ptr(out), None))
+    return out
+
+
+def filter_1pole_dev(d_audio, ch, n, sample_rate, cutoff, kind, order, d_out, d_ws, stream=None):
+    """flanhip_filter_1pole_dev: cutoff is a float or a device array of n floats; d_out may be d_audio"""
+    scalar = isinstance(cutoff, (int, float, np.floating))
+    check(lib.flanhip_filter_1pole_dev(_dp(d_audio), ch, n, sample_rate, None if scalar else _dp(cutoff), float(cutoff) if scalar else 0.0,
+                                       kind, order, _dp(d_out), _dp(d_ws), _vp(stream or 0)))
+
+
+class filter_run_forced:
+    """with fa.filter_run_forced(3): ...   -- the frames one lane replays in this thread's filters, back to the library's choice afterwards"""
+
+    def __init__(self, frames):
+        self.frames = frames
+
+    def __enter__(self):
+        lib.flanhip_filter_debug_run(self.frames)
+        return self
+
+    def __exit__(self, *exc):
+        lib.flanhip_filter_debug_run(0)
+        return False

@@ -1,6 +1,7 @@
 // Audio.cpp -- construction and conversions of flan::Audio over the C ABI
 // (reference: src/flan/Audio/AudioConstructors.cpp, Conversions/AudioPV.cpp:12-84, Audio/AudioConversions.cpp:14-56,
-// Audio/AudioCombination.cpp:299-352, Audio/AudioTemporal.cpp:236-299, Audio/AudioVolume.cpp:5-67, 190-278).
+// Audio/AudioCombination.cpp:299-352, Audio/AudioTemporal.cpp:236-299, Audio/AudioVolume.cpp:5-67, 190-278,
+// Audio/AudioFilter.cpp:280-425).
 #include "flan/Audio.h"
 
 #include <algorithm>
@@ -34,6 +35,24 @@ DeviceCurve upload_curve( const Function<Second, float> & fn, Frame n, float sca
 	c.ok = c.block && detail::upload_from_host( c.block->ptr, sampled.data(), sizeof( float ) * sampled.size() );
 	if( c.block && !c.ok ) std::cerr << "flan: upload of a sampled Function failed: " << flanhip_last_error() << std::endl;
 	return c;
+	}
+
+// One cascade of flanhip_filter_1pole_dev over `me` with a cutoff already on the device (or a scalar): a fresh device block
+Audio filter_cascade( const Audio & me, const DeviceCurve & cutoff, int kind, uint16_t order, const char * who )
+	{
+	if( me.is_null() ) return Audio::create_null();             // AudioFilter.cpp:287, :376, :385
+	const size_t ws_bytes = flanhip_filter_1pole_workspace_bytes( me.get_num_channels(), me.get_num_frames() );
+	if( ws_bytes == 0 ) return Audio::create_null();
+	const float * d_x = me.device_data();
+	if( !d_x ) return Audio::create_null();
+	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( me.get_num_channels() ) * size_t( me.get_num_frames() ) );
+	auto ws = detail::DeviceBlock::allocate( ws_bytes );
+	if( !cutoff.ok || !block || !ws ) return Audio::create_null();
+	const int rc = flanhip_filter_1pole_dev( d_x, me.get_num_channels(), me.get_num_frames(), me.get_sample_rate(), cutoff.ptr(), cutoff.scalar,
+		kind, int( order ), static_cast<float*>( block->ptr ), ws->ptr, nullptr );
+	if( !detail::report( rc, who ) ) return Audio::create_null();
+	if( !detail::report( flanhip_stream_synchronize( nullptr ), who ) ) return Audio::create_null();                 // the workspace and the curve go back idle
+	return AudioBuffer::adopt_device( me.get_format(), std::move( block ) );
 	}
 
 } // namespace
@@ -304,6 +323,50 @@ Audio Audio::compress( const Function<Second, Decibel> & threshold, const Functi
 	if( !detail::report( rc, "compress" ) ) return Audio::create_null();
 	if( !detail::report( flanhip_stream_synchronize( nullptr ), "compress" ) ) return Audio::create_null();        // the workspace and the curves go back idle
 	return AudioBuffer::adopt_device( get_format(), std::move( block ) );
+	}
+
+// :119, :291, :342: sample_function_over_domain is the Function sampled once per frame at f * frame_to_time( 1 ); the clamp is the device's
+Audio Audio::filter_1pole_lowpass( const Function<Second, Frequency> & cutoff, uint16_t order ) const
+	{
+	if( is_null() || !device_data() ) return Audio::create_null();     // :376; without a device nothing is sampled
+	return filter_cascade( *this, upload_curve( cutoff, get_num_frames(), frame_to_time( 1 ) ), FLANHIP_FILTER_BUTTERWORTH_LOW, order, "filter_1pole_lowpass" );
+	}
+
+Audio Audio::filter_1pole_highpass( const Function<Second, Frequency> & cutoff, uint16_t order ) const
+	{
+	if( is_null() || !device_data() ) return Audio::create_null();     // :385; without a device nothing is sampled
+	return filter_cascade( *this, upload_curve( cutoff, get_num_frames(), frame_to_time( 1 ) ), FLANHIP_FILTER_BUTTERWORTH_HIGH, order, "filter_1pole_highpass" );
+	}
+
+std::vector<Audio> Audio::filter_1pole_split( const Function<Second, Frequency> & cutoff, uint16_t order ) const
+	{
+	std::vector<Audio> outs;
+	if( is_null() || !device_data() ) { outs.push_back( Audio::create_null() ); outs.push_back( Audio::create_null() ); return outs; }
+	// :401-404: the cutoff is sampled once; the reference's round( time_to_frame( t ) ) indexing hands the sampled curve itself to every call
+	const DeviceCurve c = upload_curve( cutoff, get_num_frames(), frame_to_time( 1 ) );
+	const uint16_t n = order <= 1 ? uint16_t( 1 ) : order;     // :406-412
+	Audio low = filter_cascade( *this, c, FLANHIP_FILTER_BUTTERWORTH_LOW, n, "filter_1pole_split" );
+	Audio high = filter_cascade( *this, c, FLANHIP_FILTER_BUTTERWORTH_HIGH, n, "filter_1pole_split" );
+	if( order > 1 )                                             // :414-422
+		{
+		low = filter_cascade( low, c, FLANHIP_FILTER_BUTTERWORTH_LOW, n, "filter_1pole_split" );
+		high = filter_cascade( high, c, FLANHIP_FILTER_BUTTERWORTH_HIGH, n, "filter_1pole_split" );
+		}
+	outs.push_back( std::move( low ) );
+	outs.push_back( std::move( high ) );
+	return outs;
+	}
+
+Audio Audio::filter_1pole_repeat_low( const Function<Second, Frequency> & cutoff, const uint16_t repeats ) const
+	{
+	if( is_null() || !device_data() ) return Audio::create_null();     // :287
+	return filter_cascade( *this, upload_curve( cutoff, get_num_frames(), frame_to_time( 1 ) ), FLANHIP_FILTER_REPEAT_LOW, repeats, "filter_1pole_repeat_low" );
+	}
+
+Audio Audio::filter_1pole_repeat_high( const Function<Second, Frequency> & cutoff, const uint16_t repeats ) const
+	{
+	if( is_null() || !device_data() ) return Audio::create_null();
+	return filter_cascade( *this, upload_curve( cutoff, get_num_frames(), frame_to_time( 1 ) ), FLANHIP_FILTER_REPEAT_HIGH, repeats, "filter_1pole_repeat_high" );
 	}
 
 } // namespace flan

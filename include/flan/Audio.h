@@ -1,6 +1,7 @@
 // flan/Audio.h -- the Audio side of the phase-vocoder path (mirrors the reference's src/flan/Audio/Audio.h:25-176 for
 // construction and conversions; every method is const and returns a fresh object, invalid input gives a null object).
 #pragma once
+#include <cstdint>
 #include <vector>
 
 #include "flan/AudioBuffer.h"
@@ -80,6 +81,25 @@ public:
 	Audio compress( const Function<Second, Decibel> & threshold, const Function<Second, float> & compression_ratio = 3.0f,
 		const Function<Second, Second> & attack = 5.0f / 1000.0f, const Function<Second, Second> & release = 100.0f / 1000.0f,
 		const Function<Second, Decibel> & knee_width = Decibel( 0 ), const Audio * sidechain_source = nullptr ) const;
+
+	// ---- filters ----
+	/** The Butterworth low-pass of any order with a cutoff that may change every frame (Audio/AudioFilter.cpp:327-378; Zavalishin, The
+	 *  Art of VA Filter Design, 8.6), on the device (flanhip_filter_1pole_dev): for an odd order a 1-pole TPT section first,
+	 *  then order / 2 2-pole state-variable sections, each a scan over the frames.  cutoff is sampled once per frame at f * frame_to_time( 1 )
+	 *  and clamped to [1, sample rate / 2]; a constant samples nothing.  Order 0 is a copy.  A null *this gives a null Audio.  The result
+	 *  stays device-resident until read. */
+	Audio filter_1pole_lowpass( const Function<Second, Frequency> & cutoff, uint16_t order = 1 ) const;
+	/** The Butterworth high-pass (:380-387): the same cascade with every section's high output.  Order 0 is a copy. */
+	Audio filter_1pole_highpass( const Function<Second, Frequency> & cutoff, uint16_t order = 1 ) const;
+	/** { low, high } around one cutoff (:389-425): order <= 1 gives { filter_1pole_lowpass( 1 ), filter_1pole_highpass( 1 ) }, a higher
+	 *  order each filter applied twice, { low( N ).low( N ), high( N ).high( N ) }.  The cutoff is sampled ONCE and the device curve serves
+	 *  all calls.  Order 0 behaves as order 1.  A null *this gives two null Audios, as the reference's calls on it do. */
+	std::vector<Audio> filter_1pole_split( const Function<Second, Frequency> & cutoff, uint16_t order = 1 ) const;
+	/** The same 1-pole low-pass `repeats` times over (:280-316; the atmospheric scattering of the spatialisers).  No repeats give SILENCE of
+	 *  this Audio's format, not a copy: the reference's loop never writes its zero-initialised output. */
+	Audio filter_1pole_repeat_low( const Function<Second, Frequency> & cutoff, const uint16_t repeats ) const;
+	/** The same 1-pole high-pass `repeats` times over (:318-324).  No repeats give silence. */
+	Audio filter_1pole_repeat_high( const Function<Second, Frequency> & cutoff, const uint16_t repeats ) const;
 
 	// the older camelCase spellings BASELINE.json's north_star uses
 	PV convertToPV( Frame window_size = 2048, Frame hop = 128, Frame dft_size = 4096, flan_CANCEL_ARG ) const;

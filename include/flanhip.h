@@ -554,6 +554,46 @@ size_t flanhip_audio_set_volume_workspace_bytes(int64_t num_channels, int64_t nu
 int flanhip_audio_set_volume_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, float sample_rate,
                                  const float * d_level, float level, float * d_out, void * d_workspace, void * stream);
 
+/* ---- Audio::filter_1pole_lowpass / _highpass (Audio/AudioFilter.cpp:327-387) and filter_1pole_repeat_low / _high (:280-324):
+ * cascades of TPT sections with a per-frame cutoff, every section a scan --------------------------------------------------------- */
+/* audio: float[ch][n]; out: float[ch][n], may be the audio; the cutoff is a curve of n floats (the reference samples the Function once
+ * per frame, :119, :291, :342) or, with a NULL curve, the scalar.  Everything is fp32, one rounding per operation, in the reference's order:
+ *   per frame        T_half = pi / sr (pi = acosf( -1 )), c = std::clamp( cutoff, 1, sr / 2 ) (two comparisons: a NaN stays NaN),
+ *                    w = tan( T_half c ) / T_half, g = w T_half (:19-30, :57, :67, :120); shared by all channels and sections
+ *   1-pole section   G = g / ( 1 + g ), v = G ( x - s ), lp = v + s, s = lp + v; taps lp | x - lp (:61-74), s from 0
+ *   2-pole section   g1 = 2 R + g, d = 1 / ( 1 + 2 R g + g g ), hp = ( x - g1 s1 - s2 ) d, v1 = g hp, bp = v1 + s1, s1 = bp + v1,
+ *                    v2 = g bp, lp = v2 + s2, s2 = lp + v2; taps lp | hp (:164-182), s1 and s2 from 0
+ *   BUTTERWORTH      order N: for odd N a 1-pole section first, then floor( N / 2 ) 2-pole sections with R_i = -cos( theta_i ),
+ *                    theta_i = delta i + pi / 2 + delta / 2, delta = 2 pi / ( 2 N ) (:32-44, :338-365); every section taps low (_LOW) or
+ *                    high (_HIGH); section k reads section k - 1's output.  Order 0 is a copy of the input (:337).
+ *   REPEAT           `order` identical 1-pole sections, all tapping low or all tapping high (:296-303).  Order 0 is SILENCE, not a copy:
+ *                    the reference's loop never writes its zero-initialised output.
+ * The reference's loop is sequential over all frames; here every section is a scan over the frames (flan_amd/csrc/filter.hip, DESIGN.md
+ * 4.15): a section is an affine map of its state, every lane replays a run of frames with the reference's fp32 operations from a state
+ * carried in by an fp64 scan (rounded to fp32 once).  tan (and the cosine of R_i) is the fp64 function rounded to fp32 once.
+ * Deterministic (two calls agree bit for bit); a channel's output does not depend on the channels filtered with it.
+ * order: 0 ... 65535 (the reference's uint16_t).  Null audio / out (and, for _dev, workspace), non-positive sizes, sample_rate <= 0, an
+ * unknown kind and an order outside the range are FLANHIP_ERR_INVALID_ARG, before any device call.  The workspace need not be cleared.
+ * `cancel` is polled before the upload and before the launch; the kernels run to the end once launched. */
+#define FLANHIP_FILTER_BUTTERWORTH_LOW  0
+#define FLANHIP_FILTER_BUTTERWORTH_HIGH 1
+#define FLANHIP_FILTER_REPEAT_LOW       2
+#define FLANHIP_FILTER_REPEAT_HIGH      3
+/* bytes of device workspace flanhip_filter_1pole_dev needs (pure host arithmetic; 0 for arguments it refuses): the row g of n floats (n
+ * rounded up to 4), then 48 bytes (a block's map, sized for a 2-pole section's six doubles) per channel and block of 256 runs, then 16
+ * bytes (the state carried into the block) per channel and block: 4 * roundup( n, 4 ) + 64 * ch * ceil( n / ( 256 * run ) ).  Sized for the
+ * calling thread's flanhip_filter_debug_run setting. */
+size_t flanhip_filter_1pole_workspace_bytes(int64_t num_channels, int64_t num_frames);
+int flanhip_filter_1pole(const float * audio, int64_t num_channels, int64_t num_frames, float sample_rate,
+                         const float * cutoff_curve, float cutoff, int kind, int order,
+                         float * out, volatile int * cancel);
+int flanhip_filter_1pole_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, float sample_rate,
+                             const float * d_cutoff, float cutoff, int kind, int order,
+                             float * d_out, void * d_workspace, void * stream);
+/* test hook: the frames one lane replays in the calling thread's filters, 1 ... 64 (larger values are taken as 64; 0: the library's
+ * choice, 16).  Results do not depend on it beyond rounding. */
+void flanhip_filter_debug_run(int frames);
+
 /* ---- Audio::resample (Audio/AudioConversions.cpp:14-30, r8brain CDSPResampler with default parameters) --------- */
 /* AudioConversions.cpp:22: out frames = Frame( float(num_frames) * ( dst_rate / src_rate ) ) */
 int64_t flanhip_resample_out_frames(int64_t num_frames, float src_rate, float dst_rate);
