@@ -1075,6 +1075,13 @@ int flanhip_debug_read_spans( unsigned long long * out8192 )
 	FLANHIP_CHECK( hipMemcpyFromSymbol( out8192, HIP_SYMBOL( g_stamp_span ), 8192 * sizeof( unsigned long long ) ) );
 	return FLANHIP_OK;
 	}
+// ... and k_synthesize_v2's phase marks of the last launch (4 x 4096 words: entry, behind the last head frame, behind the frame loop, unused)
+int flanhip_debug_read_marks( unsigned long long * out16384 )
+	{
+	FLANHIP_CHECK( hipDeviceSynchronize() );
+	FLANHIP_CHECK( hipMemcpyFromSymbol( out16384, HIP_SYMBOL( g_stamp_mark ), 16384 * sizeof( unsigned long long ) ) );
+	return FLANHIP_OK;
+	}
 #endif
 
 size_t flanhip_synthesize_workspace_bytes( int64_t ch, int64_t F, int bins, float sr, float ar, int W )

@@ -40,9 +40,10 @@ struct V2Lds
 // frame loop, per-section sums in scalar registers, added to g_stamp_acc once per wavefront.  Never quote this build's run time.
 __device__ unsigned long long g_stamp_acc[16];
 __device__ unsigned long long g_stamp_span[2 * 4096];      // per wavefront (block * 8 + wave): s_memrealtime (100 MHz) at the start and at the end of its life
+__device__ unsigned long long g_stamp_mark[4 * 4096];      // clock-only build, k_synthesize_v2: s_memrealtime on entry to the kernel, behind the last head frame, behind the frame loop (tools/wave_spans.py --phases)
 struct Stamps
 	{
-	unsigned long long last, acc[12], t_begin, r_begin;
+	unsigned long long last, acc[12], t_begin, r_begin, r_mark;
 	__device__ __forceinline__ static unsigned long long realtime()
 		{
 		unsigned long long t;
@@ -65,7 +66,18 @@ struct Stamps
 		const unsigned w = blockIdx.x * ( blockDim.x >> 6 ) + ( threadIdx.x >> 6 );
 		if( ( threadIdx.x & 63 ) == 0 && w < 4096 ) g_stamp_span[2 * w] = r;
 		}
+	// marks of the synthesis' phases: 0 the kernel's first instructions and 2 the end of the frame loop go to memory at once; 1, taken inside the frame loop
+	// (behind the last head frame), waits in two scalar registers for 2 -- a store inside the loop would join the queue its counted waits count
+	__device__ __forceinline__ void mark( int k )
+		{
+		const unsigned long long r = realtime();
+		const unsigned w = blockIdx.x * ( blockDim.x >> 6 ) + ( threadIdx.x >> 6 );
+		if( k == 0 ) r_mark = 0;                                              // (a chain without whole head frames never takes mark 1)
+		if( k == 1 ) { r_mark = r; return; }
+		if( ( threadIdx.x & 63 ) == 0 && w < 4096 ) { g_stamp_mark[4 * w + k] = r; if( k == 2 ) g_stamp_mark[4 * w + 1] = r_mark; }
+		}
 #else
+	__device__ __forceinline__ void mark( int ) {}
 	__device__ __forceinline__ void init() { for( int i = 0; i < 12; ++i ) acc[i] = 0; r_begin = realtime(); last = now(); t_begin = last; }
 #endif
 #ifdef FLANHIP_STAMPS_CLOCK_ONLY
@@ -101,6 +113,7 @@ struct Stamps
 struct Stamps
 	{
 	__device__ __forceinline__ void init() {}
+	__device__ __forceinline__ void mark( int ) {}
 	__device__ __forceinline__ void operator()( int ) const {}
 	__device__ __forceinline__ void flush( int ) {}
 	};
@@ -518,6 +531,8 @@ __global__ __launch_bounds__( 64 * WAVES ) void k_synthesize_v2( SynthParams p, 
 	cf * s = reinterpret_cast<cf*>( smem );
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	const int W = p.window_size;
+	Stamps st;                                                                  // (diagnostic builds: the wavefront's life and its phases, tools/wave_spans.py)
+	st.mark( 0 );
 	const int cancel_word = cancel_peek( p.cancel );
 	for( int i = tid; i < 240; i += NT ) s[L::TW1 + i] = tb.tw1[i];
 	for( int i = tid; i < 768; i += NT ) s[L::TW3 + i] = tb.tw3[i];
@@ -563,6 +578,10 @@ __global__ __launch_bounds__( 64 * WAVES ) void k_synthesize_v2( SynthParams p, 
 	const unsigned lane8 = 8u * unsigned( lane );
 	// every step a chain emits once its head is written lies inside the output, except for a channel's chain 0 (positions below 0)
 	const bool plain_emit = __builtin_amdgcn_readfirstlane( int( chain_in_channel != 0 ) ) != 0 && ( ABL & 4 ) == 0;
+	// ... and the steps before that all go to the chain's head buffer: the same address form, a scalar base per block (the head of the group's first chain)
+	// plus a 32-bit per-lane offset (this chain's head, the lane's pair)
+	char * const hb = reinterpret_cast<char*>( p.head + ( int64_t( channel ) * p.chains_per_channel + int64_t( group ) * WAVES ) * p.head_len );
+	const unsigned hoff = unsigned( active ? wave : 0 ) * unsigned( p.head_len ) * 4u + lane8;
 	const int padl = lane + ( lane >> 4 );
 	cf * mirror = buf + ( C * 17 ) / 16 - ( lane + ( ( lane + 15 ) >> 4 ) );      // mirror[-68 q] = slot PAD( C - lane - 64 q )
 
@@ -619,16 +638,16 @@ __global__ __launch_bounds__( 64 * WAVES ) void k_synthesize_v2( SynthParams p, 
 	auto load_row = [&]( int fr )                                               // fr: the frame, counted from tb0
 		{
 		const unsigned ro = unsigned( ( ABL & 2 ) ? relf0 : fr ) * unsigned( ( C + 1 ) * 8 );   // ABL 2 (timing only): a hot row
-		const cf * row = reinterpret_cast<const cf*>( pvb + ro );
 		const cf * rowk = reinterpret_cast<const cf*>( pvb + ( ro + lane8 ) );
 		const cf * rowm = reinterpret_cast<const cf*>( pvb + ( ro + unsigned( C * 8 ) - lane8 ) );
+		const cf * rowx = reinterpret_cast<const cf*>( pvb + ( ro + unsigned( C / 2 * 8 ) ) );   // (4096 is one past the immediate's reach: in the 32-bit offset, not in a 64-bit address)
 		#pragma unroll
 		for( int q = 0; q < H; ++q )
 			{
 			mfk[q] = ( ABL & 1 ) ? rowk[64 * q] : __builtin_nontemporal_load( rowk + 64 * q );
 			mfm[q] = ( ABL & 1 ) ? rowm[-64 * q] : __builtin_nontemporal_load( rowm - 64 * q );
 			}
-		mfx = ( ABL & 1 ) ? row[C / 2] : __builtin_nontemporal_load( row + C / 2 );
+		mfx = ( ABL & 1 ) ? *rowx : __builtin_nontemporal_load( rowx );
 		};
 
 	// phase_buffer (AudioPV.cpp:105) on entry to the chain, of the lane's pairs and of bin C/2
@@ -653,12 +672,12 @@ __global__ __launch_bounds__( 64 * WAVES ) void k_synthesize_v2( SynthParams p, 
 		phx = carry[C / 2];
 		}
 	if( !active ) return;
-	Stamps st;                                                                  // (diagnostic builds: the wavefront's life, tools/wave_spans.py)
-	st.init();
+	st.init();                                                                  // (the carries are in: the span tools/wave_spans.py calls the wavefront's life starts here)
 	cf z[E];
 	// inverse phase vocoder of the row in mfk / mfm / mfx (AudioPV.cpp:117-120, phase_vocoder.cpp:55-61), merge of X[0..C] into the
 	// half-size spectrum conj( A + i B ) (the forward transform of it is the conjugate of the inverse one): leaves z[] complete
-	auto bins_of_row = [&]()
+	// (always_inline: with a third walk calling it the compiler would make it a function of its own, the chain's whole state passed through memory)
+	auto bins_of_row = [&]() __attribute__(( always_inline ))
 		{
 		bool slow = false;
 		// f / analysis_rate of the row's 17 bins under ONE test of the divisor's plan (div_c per bin is a scalar branch per bin: 17 islands of
@@ -759,15 +778,27 @@ __global__ __launch_bounds__( 64 * WAVES ) void k_synthesize_v2( SynthParams p, 
 	const int tag_head = p.fix_tag | 2;
 	const int nsteps = p.head_len / 128;                                        // steps of 128 samples a boundary holds (W - hop, a multiple of 128 here)
 	const bool has_head = chain_in_channel != 0, has_tail = !last_chain;
-	int * const word_h = p.fix_state + chain, * const word_t = p.fix_state + ( chain + 1 );      // (used under `fix` only)
+	// (the chain's number is wave-uniform but derived from threadIdx: said so, the two word addresses are scalars instead of two VGPR pairs that live -- spilled --
+	// across the whole walk; the host admits fewer than 2^31 chains per launch)
+	const int chain_s = __builtin_amdgcn_readfirstlane( int( chain ) );
+	int * const word_h = p.fix_state + chain_s, * const word_t = p.fix_state + ( int64_t( chain_s ) + 1 );      // (used under `fix` only)
 	const cf * const head_next = reinterpret_cast<const cf*>( p.head + ( chain + 1 ) * p.head_len ) + lane;
 	const int i_pub = ( p.head_len + hop - 1 ) / hop;                           // the frame whose row wait proves the head's stores have landed
 	int old_h = 0, seen_t = 0;                                                  // (lane 0's: what the head word held before this chain's tag; what the tail word holds)
 	bool published = false;
 	cf hx[E];                                                                   // the next chain's head (the last frame only: in the registers the MF rows leave)
-	auto frame_step = [&]( int i, auto last_tag ) -> bool
+	// WALK (a compile-time switch): 0 the general walk, which decides per step AND per lane where a step goes (emit_step).  1 and 2 are the two phases of a
+	// chain that settles its overlaps here, is not a channel's chain 0 and has a head of whole frames: 1 its head frames -- HOPQ agent-scope stores into the
+	// head buffer -- and 2 the frames behind them -- HOPQ plain stores into the output --, both through a scalar base, an offset of lane8 plus immediates and
+	// NO branch.  A phase is a loop of its own because the wait for the next row is a counted one only where every static path from the row request to
+	// the wait holds the same number of stores: the general walk's stores sit under exec-mask branches, the compiler has to assume that none was issued,
+	// and where the plain steps shared its loop body the row wait of EVERY frame ended in s_waitcnt vmcnt(0), behind the acknowledgement of the stores
+	// issued just before it.  Two store kinds under one wave-uniform branch in one loop body end the same way (the structurised flow keeps a static path
+	// around both arms).  
+	auto frame_step = [&]( int i, auto last_tag, auto walk_tag ) -> bool
 		{
 		constexpr bool LAST = decltype( last_tag )::value;
+		constexpr int WALK = decltype( walk_tag )::value;
 		bool have_head = false;
 		if constexpr( LAST )
 			{
@@ -784,7 +815,7 @@ __global__ __launch_bounds__( 64 * WAVES ) void k_synthesize_v2( SynthParams p, 
 		else
 			{
 			load_row( relf0 + i + 1 );
-			if( fix && has_tail && i == nf - 2 && lane == 0 ) seen_t = __hip_atomic_load( word_t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
+			if( WALK != 1 && fix && has_tail && i == nf - 2 && lane == 0 ) seen_t = __hip_atomic_load( word_t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
 			}
 		if constexpr( ( ABL & 8 ) == 0 )                                        // ABL 8 (timing only): no transform
 		fft_fast<10>( z, buf, s_tw1, s_tw3, lane );
@@ -825,7 +856,19 @@ __global__ __launch_bounds__( 64 * WAVES ) void k_synthesize_v2( SynthParams p, 
 		// HOPQ stores in either arm (the wait for the next row counts them).  The plain arm: past the chain's head every step goes to the
 		// output proper, all of it inside -- a scalar base, one 32-bit offset, immediates; the general arm (head steps, chain 0) costs ~17
 		// 64-bit vector instructions per step
-		if( plain_emit && rel >= p.head_len )
+		if constexpr( WALK == 1 )
+			{
+			const unsigned oo = hoff + unsigned( rel ) * 4u;
+			#pragma unroll
+			for( int q = 0; q < HOPQ; ++q ) st_agent( reinterpret_cast<cf*>( hb + oo + 512 * q ), acc[q] );   // (the head another wavefront may come to add up)
+			}
+		else if constexpr( WALK == 2 )
+			{
+			const unsigned oo = unsigned( hop * ( relf0 + i ) ) * 4u + lane8;
+			#pragma unroll
+			for( int q = 0; q < HOPQ; ++q ) *reinterpret_cast<cf*>( ob + oo + 512 * q ) = acc[q];
+			}
+		else if( plain_emit && rel >= p.head_len )
 			{
 			const unsigned oo = unsigned( hop * ( relf0 + i ) ) * 4u + lane8;
 			#pragma unroll
@@ -843,7 +886,7 @@ __global__ __launch_bounds__( 64 * WAVES ) void k_synthesize_v2( SynthParams p, 
 		if constexpr( !LAST )
 			{
 			bins_of_row();
-			if( fix && has_head && i == i_pub )
+			if( WALK != 1 && fix && has_head && i == i_pub )
 				{
 				// the head's stores went out iterations ago and the wait for row i + 1 has retired them with everything else issued before that row was
 				// requested -- but that is the compiler's counted wait, not a statement of this source: the queue is drained explicitly (once per chain:
@@ -853,11 +896,29 @@ __global__ __launch_bounds__( 64 * WAVES ) void k_synthesize_v2( SynthParams p, 
 				asm volatile( "" ::: "memory" );
 				published = true;
 				}
+			if( WALK == 0 && i + 1 == i_pub ) st.mark( 1 );                        // (diagnostic builds: the last frame whose steps go to the head buffer)
 			}
 		return have_head;
 		};
-	for( int i = 0; i + 1 < nf; ++i ) frame_step( i, std::false_type{} );
-	const bool have_head = frame_step( nf - 1, std::true_type{} );
+	// The phased walk: the overlaps settled here (`fix`: the head's stores are all of the agent-scope kind), not chain 0 of a channel (steps in front of the
+	// output), the head a whole number of frames, and the chain long enough to leave its head, publish and peek in that order (what the host asks of a
+	// launch with `fix`; the last chain of a channel may still be shorter).  Everything else -- chain 0, RING, hop 128, a head of 2.75 hops (window 1920),
+	// chains of a few frames, the overlaps by k_ola_fixup4 -- walks as before.
+	// Not at hop 128 (HOPQ 1): its phase loops compiled with scratch reloads INSIDE the loops (eight in the head frames' loop, each one a wait behind the row
+	// request) and the launch measured 3.9 % slower than with the one loop (profiles/syn_v2_isa_loops.txt).
+	constexpr bool PHASES = HOPQ >= 2;
+	const bool phased = PHASES && fix && plain_emit && p.head_len % hop == 0 && nf >= i_pub + 3;
+	constexpr std::false_type not_last{};
+	if constexpr( !PHASES ) { for( int i = 0; i + 1 < nf; ++i ) frame_step( i, not_last, std::integral_constant<int, 0>{} ); }
+	else if( phased )
+		{
+		for( int i = 0; i < i_pub; ++i ) frame_step( i, not_last, std::integral_constant<int, 1>{} );
+		st.mark( 1 );
+		for( int i = i_pub; i + 1 < nf; ++i ) frame_step( i, not_last, std::integral_constant<int, 2>{} );
+		}
+	else { for( int i = 0; i + 1 < nf; ++i ) frame_step( i, not_last, std::integral_constant<int, 0>{} ); }
+	const bool have_head = frame_step( nf - 1, std::true_type{}, std::integral_constant<int, 0>{} );
+	st.mark( 2 );
 	// flush the partial sums that the next chain's head completes; the last chain zero-fills to the end of the output
 	const int64_t ring_end = pos + ( W - hop );
 	const int64_t flush_end = last_chain ? max( ring_end, p.out_len ) : ring_end;

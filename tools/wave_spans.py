@@ -4,7 +4,11 @@
     FLAN_AMD_LIB=tools/ubench/libflanhip_clock.so python tools/wave_spans.py
 
 The launch lasts as long as its LAST wavefront: this prints the distribution of the wavefronts' lives (10 ns ticks of s_memrealtime),
-the skew of their starts, and which chains finish last (first / last chain of a channel walk the clamped-load loop body)."""
+the skew of their starts, and which chains finish last (first / last chain of a channel walk the clamped-load loop body).
+
+    --syn            the same for the main synthesis kernel (a life starts behind the carry prologue)
+    --syn --phases   the synthesis' phases per wavefront: kernel entry, end of the carry prologue, end of the last head frame, end of the
+                     frame loop, end of the overlap settle (Stamps::mark, pv_kernels_v2.h); [--out FILE] keeps the table"""
 import ctypes
 import os
 import sys
@@ -47,7 +51,7 @@ def main():
         fa.analyze_dev_fused(audio, ch, n, SR, W, HOP, DFT, pv, ws, stream)
     torch.cuda.synchronize()
     buf = (ctypes.c_ulonglong * 8192)()
-    lives, starts, ends = [], [], []
+    lives, starts, ends, phases = [], [], [], []
     print("synthesis (main kernel)" if synth else "analysis")
     for rep in range(5):
         fa.analyze_dev_fused(audio, ch, n, SR, W, HOP, DFT, pv, ws, stream)
@@ -59,6 +63,14 @@ def main():
         starts.append((a[:, 0] - t0) * 0.01)
         ends.append((a[:, 1] - t0) * 0.01)
         lives.append((a[:, 1] - a[:, 0]) * 0.01)
+        if synth and "--phases" in sys.argv:
+            mbuf = (ctypes.c_ulonglong * 16384)()
+            lib.flanhip_debug_read_marks(mbuf)
+            m = np.array(mbuf, dtype=np.uint64).reshape(4096, 4)[:2048].astype(np.int64)
+            # columns: entry, end of the carry prologue, end of the last head frame, end of the frame loop, end of the settle -- after the launch's first entry
+            phases.append((np.stack([m[:, 0], a[:, 0], m[:, 1], m[:, 2], a[:, 1]], 1) - m[:, 0].min()) * 0.01)
+    if phases:
+        return report_phases(np.median(phases, 0), HOP, W, F, ch)
     st, en, li = np.median(starts, 0), np.median(ends, 0), np.median(lives, 0)
     print("2048 wavefronts (256 per channel: chain c of a channel = wavefront c; c = 0 and 255 are the edge chains), microseconds, median of 5 launches")
     print("start after the first wavefront's: median %.2f  p95 %.2f  max %.2f" % (np.median(st), np.percentile(st, 95), st.max()))
@@ -79,6 +91,39 @@ def main():
     print("end of the group's last wavefront (median over channels): " + " ".join("%.0f" % v for v in np.median(by_group_end, 0)))
     per_simd = li.reshape(256, 8)
     print("per block: fastest wave %.1f  slowest %.1f (median over blocks)" % (np.median(per_simd.min(1)), np.median(per_simd.max(1))))
+
+
+def report_phases(t, hop, window, frames, ch):
+    """t[wavefront][5]: microseconds after the launch's first kernel entry (median of the launches), wavefront = block * 8 + wave slot,
+    block = channel * 32 + group."""
+    import numpy as np
+    nhead = -(-(window - hop) // hop)
+    lines = ["k_synthesize_v2, %d ch, window %d hop %d: 2048 wavefronts, %d head frames per chain; microseconds, median of 5 launches" % (ch, window, hop, nhead),
+             "at: time after the launch's first kernel entry;  in: time spent in the phase (prologue = entry .. carries in; head = .. end of the last head frame,",
+             "the first row's per-bin work included; body = .. end of the frame loop; settle = .. end of settle_overlap)",
+             "%-34s %7s | %8s %8s %8s %8s | %8s %8s %8s %8s" % ("median over", "entry", "at:prol", "at:head", "at:loop", "at:end", "in:prol", "in:head", "in:body", "in:settl")]
+    w = np.arange(2048)
+    slot, group = w % 8, (w // 8) % 32
+    chain = group * 8 + slot
+    interior = (chain != 0) & (chain != 255)
+    sets = [("all interior chains", interior),
+            ("wave slots 0-3 (interior)", interior & (slot < 4)), ("wave slots 4-7 (interior)", interior & (slot >= 4)),
+            ("groups 0-7 (interior)", interior & (group < 8)), ("groups 8-23", interior & (group >= 8) & (group < 24)), ("groups 24-31 (interior)", interior & (group >= 24)),
+            ("chain 0 of a channel", chain == 0), ("last chain of a channel", chain == 255)]
+    for name, sel in sets:
+        x = t[sel]
+        d = np.diff(x, axis=1)
+        lines.append("%-34s %7.2f | %8.2f %8.2f %8.2f %8.2f | %8.2f %8.2f %8.2f %8.2f" % ((name, np.median(x[:, 0])) + tuple(np.median(x[:, 1:], 0)) + tuple(np.median(d, 0))))
+    d = np.diff(t[interior], axis=1)
+    lines.append("launch: last kernel entry %.2f, last end %.2f (the launch lasts until then)" % (t[:, 0].max(), t[:, 4].max()))
+    lines.append("per frame, interior chains (median): head phase / (head frames + 1 row) %.3f   body phase / (frames - head frames - 0.5) %.3f"
+                 % (np.median(d[:, 1]) / (nhead + 0.5), np.median(d[:, 2]) / (-(-frames // 256) - nhead - 0.5)))
+    text = "\n".join(lines)
+    print(text)
+    for i, a in enumerate(sys.argv):
+        if a == "--out" and i + 1 < len(sys.argv):
+            with open(sys.argv[i + 1], "w") as f:
+                f.write(text + "\n")
 
 
 if __name__ == "__main__":
