@@ -8,17 +8,16 @@
 //                    composition, ( a2 a1, a2 b1 + b2, max( c2, a2 c1 + b2 ) ), identity ( 1, 0, -inf ): a scan
 //   stage 2          y_L = a_A y_L + ( 1 - a_A ) y_1: affine maps ( a2 a1, a2 b1 + b2 ): a scan
 // Each lane owns a run of consecutive frames.  k_comp_sum1 reduces every run to one map (fp64), scans the maps across the wavefront
-// (__shfl_up) and the block (LDS) and leaves the block's total; k_comp_carry scans the block totals (one small block) into the state at
+// (__shfl_up) and the block (LDS) and leaves the block's total; k_scan_carry scans the block totals (one small block) into the state at
 // every block's first frame; k_comp_replay1 scans the block again, hands every lane the state at its run's first frame and REPLAYS the
-// run with the reference's own fp32 operations in the reference's order, writing y_1 and summarising stage 2 on the way; k_comp_carry
+// run with the reference's own fp32 operations in the reference's order, writing y_1 and summarising stage 2 on the way; k_scan_carry
 // again; k_comp_replay2 replays stage 2 and writes c = 10^( -y_L / 20 ).  k_gain_apply multiplies every channel by c.
 // Only the state a run starts from comes out of the fp64 scan (rounded to fp32 once); everything else is the sequential fp32 loop.
 // Every composition runs in a fixed order and there are no atomics: two calls agree bit for bit, and c does not depend on how many
 // channels are scaled.  log10, exp and 10^x are evaluated in fp64 and rounded to fp32 once (what glibc's expf / powf do): the fp32
 // device functions are 1 ... 2 ulp off, and one ulp of a_R = 0.9998 is 3e-4 of the release time.
-#include "flanhip_internal.h"
-
-#include <algorithm>
+// The geometry, block_scan, load4 / store4, lane_run and k_scan_carry are run_scan.h's; the maps and everything per frame are this file's.
+#include "run_scan.h"
 
 namespace flanhip {
 
@@ -26,21 +25,11 @@ namespace {
 
 thread_local int t_comp_run = 0;          // flanhip_compress_debug_run: frames per lane forced for the calling thread (0: the library's choice)
 
-constexpr int COMP_THREADS = 256;
-constexpr int COMP_WAVES = COMP_THREADS / 64;
-constexpr int COMP_RUN = 16;              // frames per lane: 4096 per block, 703 blocks for a minute at 48 kHz
-constexpr int COMP_MAX_RUN = 64;
 constexpr int64_t COMP_MAX_FRAMES = int64_t( 1 ) << 36;
 constexpr int64_t COMP_MAX_CHANNELS = 1 << 20;
 constexpr int VOL_MAX_PARTIALS = 1024;    // set_volume: the blocks of k_absmax_partial
 constexpr size_t VOL_PARTIAL_OFF = 256;   // word 0 of the workspace: the maximum; the partial maxima start here
 constexpr size_t VOL_WS_BYTES = 8192;
-
-int comp_run()
-	{
-	const int forced = t_comp_run;
-	return forced > 0 ? std::min( forced, COMP_MAX_RUN ) : COMP_RUN;
-	}
 
 struct Map1 { double a, b, c; };          // y -> max( c, a y + b ), a >= 0
 struct Map2 { double a, b; };             // y -> a y + b
@@ -55,9 +44,8 @@ struct CompLayout
 bool comp_layout( int64_t n, CompLayout * l )
 	{
 	if( n <= 0 || n > COMP_MAX_FRAMES ) return false;
-	l->run = comp_run();
-	const int64_t per_block = int64_t( COMP_THREADS ) * l->run;
-	l->blocks = ( n + per_block - 1 ) / per_block;
+	l->run = scan_run( t_comp_run );
+	l->blocks = scan_blocks( n, l->run );
 	l->npad = ( n + 3 ) / 4 * 4;
 	const size_t row = sizeof( float ) * size_t( l->npad );
 	l->xl = 0; l->ar = row; l->aa = 2 * row; l->y1 = 3 * row; l->gain = 4 * row;
@@ -67,16 +55,6 @@ bool comp_layout( int64_t n, CompLayout * l )
 	l->carry2 = l->tot2 + sizeof( Map2 ) * size_t( l->blocks );
 	l->total = l->carry2 + sizeof( double ) * size_t( l->blocks );
 	return true;
-	}
-
-// AudioBuffer::get_max_sample_magnitude() with default arguments scans frames [0, end): end = clamp( Frame( time_to_frame( get_length() ) ),
-// 0, N - 1 ) in fp32 (AudioBuffer.cpp:401-430), as conv.hip's normalize does
-int64_t volume_end( int64_t n, float sr )
-	{
-	const float length = float( n ) / sr;
-	const float f = length * sr;
-	const int64_t e = f >= 9.0e18f ? n : int64_t( f );
-	return std::clamp<int64_t>( e, 0, n - 1 );
 	}
 
 // ---- the maps -------------------------------------------------------------------------------------------------------------------
@@ -99,77 +77,16 @@ __device__ __forceinline__ Map2 shfl_up( const Map2 & m, int off ) { return Map2
 __device__ __forceinline__ void set_identity( Map1 & m ) { m = identity1(); }
 __device__ __forceinline__ void set_identity( Map2 & m ) { m = identity2(); }
 
-// Scan of one map per thread over the block, in thread order: excl = the maps of all earlier threads composed, total = the block's.
-// Every thread of the block calls it.
-template<typename M>
-__device__ __forceinline__ void block_scan( const M & mine, M * s_tot, M & excl, M & total )
-	{
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	M inc = mine;
-	#pragma unroll
-	for( int off = 1; off < 64; off <<= 1 )
-		{
-		const M o = shfl_up( inc, off );
-		if( lane >= off ) inc = then( o, inc );
-		}
-	if( lane == 63 ) s_tot[wave] = inc;
-	__syncthreads();
-	M prev = shfl_up( inc, 1 );
-	if( lane == 0 ) set_identity( prev );
-	M pre; set_identity( pre );
-	for( int w = 0; w < wave; ++w ) pre = then( pre, s_tot[w] );
-	excl = then( pre, prev );
-	total = s_tot[0];
-	#pragma unroll
-	for( int w = 1; w < COMP_WAVES; ++w ) total = then( total, s_tot[w] );
-	__syncthreads();
-	}
-
-// four consecutive floats from frame f (a multiple of 4 when VEC: the workspace rows are 16-byte aligned and padded to a multiple of 4)
-template<bool VEC>
-__device__ __forceinline__ void load4( const float * p, int64_t f, int64_t n, float ( &v )[4] )
-	{
-	if constexpr( VEC )
-		{
-		const float4 q = *reinterpret_cast<const float4*>( p + f );
-		v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-		}
-	else
-		{
-		#pragma unroll
-		for( int k = 0; k < 4; ++k ) v[k] = f + k < n ? p[f + k] : 0.0f;
-		}
-	}
-// the first `valid` of four values to frame f on.  VEC: all four (a run is whole quads then, so valid < 4 only where the quad ends in the
-// row's padding); otherwise nothing past the run: those frames are the next lane's
-template<bool VEC>
-__device__ __forceinline__ void store4( float * p, int64_t f, int valid, const float ( &v )[4] )
-	{
-	if constexpr( VEC ) *reinterpret_cast<float4*>( p + f ) = make_float4( v[0], v[1], v[2], v[3] );
-	else
-		{
-		#pragma unroll
-		for( int k = 0; k < 4; ++k ) if( k < valid ) p[f + k] = v[k];
-		}
-	}
-
-// the run of the calling thread: frames [f0, f0 + len)
-__device__ __forceinline__ void lane_run( int64_t n, int run, int64_t & f0, int & len )
-	{
-	f0 = ( int64_t( blockIdx.x ) * COMP_THREADS + threadIdx.x ) * run;
-	len = int( std::min<int64_t>( std::max<int64_t>( n - f0, 0 ), run ) );
-	}
-
 // stage 1 of a run as one map: step f is ( a_R, ( 1 - a_R ) x_L, x_L ), the fp32 values the replay uses, composed in fp64
 template<bool VEC>
-__device__ __forceinline__ Map1 summarise1( const float * xl, const float * ar, int64_t n, int64_t f0, int len )
+__device__ __forceinline__ Map1 summarise1( const float * xl, const float * ar, int64_t f0, int len )
 	{
 	Map1 m = identity1();
 	for( int i = 0; i < len; i += 4 )
 		{
 		float x[4], a[4];
-		load4<VEC>( xl, f0 + i, n, x );
-		load4<VEC>( ar, f0 + i, n, a );
+		load4<VEC>( xl, f0 + i, len - i, x );
+		load4<VEC>( ar, f0 + i, len - i, a );
 		#pragma unroll
 		for( int k = 0; k < 4; ++k )
 			if( i + k < len )
@@ -180,14 +97,14 @@ __device__ __forceinline__ Map1 summarise1( const float * xl, const float * ar, 
 
 // stage 2 of a run as one map: step f is ( a_A, ( 1 - a_A ) y_1 )
 template<bool VEC>
-__device__ __forceinline__ Map2 summarise2( const float * y1, const float * aa, int64_t n, int64_t f0, int len )
+__device__ __forceinline__ Map2 summarise2( const float * y1, const float * aa, int64_t f0, int len )
 	{
 	Map2 m = identity2();
 	for( int i = 0; i < len; i += 4 )
 		{
 		float y[4], a[4];
-		load4<VEC>( y1, f0 + i, n, y );
-		load4<VEC>( aa, f0 + i, n, a );
+		load4<VEC>( y1, f0 + i, len - i, y );
+		load4<VEC>( aa, f0 + i, len - i, a );
 		#pragma unroll
 		for( int k = 0; k < 4; ++k )
 			if( i + k < len )
@@ -222,10 +139,10 @@ __device__ __forceinline__ float gain_computer( float x_G, float threshold, floa
 	}
 
 // one frame per thread: :211-215 (the SIGNED maximum over the sidechain's channels, from 0; a NaN sample is never taken), :264-269, :242
-__global__ __launch_bounds__( COMP_THREADS ) void k_comp_level( const float * __restrict__ side, int64_t side_ch, int64_t side_n, int64_t n, float sr,
+__global__ __launch_bounds__( SCAN_THREADS ) void k_comp_level( const float * __restrict__ side, int64_t side_ch, int64_t side_n, int64_t n, float sr,
 	CompParams p, float * __restrict__ xl, float * __restrict__ ar, float * __restrict__ aa )
 	{
-	const int64_t f = int64_t( blockIdx.x ) * COMP_THREADS + threadIdx.x;
+	const int64_t f = int64_t( blockIdx.x ) * SCAN_THREADS + threadIdx.x;
 	if( f >= n ) return;
 	float x = 0.0f;
 	for( int64_t c = 0; c < side_ch; ++c )
@@ -241,54 +158,36 @@ __global__ __launch_bounds__( COMP_THREADS ) void k_comp_level( const float * __
 	}
 
 template<bool VEC>
-__global__ __launch_bounds__( COMP_THREADS ) void k_comp_sum1( const float * __restrict__ xl, const float * __restrict__ ar, int64_t n, int run,
+__global__ __launch_bounds__( SCAN_THREADS ) void k_comp_sum1( const float * __restrict__ xl, const float * __restrict__ ar, int64_t n, int run,
 	Map1 * __restrict__ tot )
 	{
-	__shared__ Map1 s_tot[COMP_WAVES];
+	__shared__ Map1 s_tot[SCAN_WAVES];
 	int64_t f0; int len;
 	lane_run( n, run, f0, len );
 	Map1 excl, total;
-	block_scan( summarise1<VEC>( xl, ar, n, f0, len ), s_tot, excl, total );
+	block_scan( summarise1<VEC>( xl, ar, f0, len ), s_tot, excl, total );
 	if( threadIdx.x == 0 ) tot[blockIdx.x] = total;
-	}
-
-// One block: the state at the first frame of every block of the scan, from the block totals and the state 0 before frame 0 (:258-259)
-template<typename M>
-__global__ __launch_bounds__( COMP_THREADS ) void k_comp_carry( const M * __restrict__ tot, int64_t blocks, double * __restrict__ carry )
-	{
-	__shared__ M s_tot[COMP_WAVES];
-	double state = 0.0;
-	for( int64_t base = 0; base < blocks; base += COMP_THREADS )
-		{
-		const int64_t b = base + threadIdx.x;
-		M mine; set_identity( mine );
-		if( b < blocks ) mine = tot[b];
-		M excl, total;
-		block_scan( mine, s_tot, excl, total );
-		if( b < blocks ) carry[b] = apply( excl, state );
-		state = apply( total, state );
-		}
 	}
 
 // Stage 1 replayed (:250 in fp32, std::max( a, b ) = a < b ? b : a), y_1 written, stage 2 summarised
 template<bool VEC>
-__global__ __launch_bounds__( COMP_THREADS ) void k_comp_replay1( const float * __restrict__ xl, const float * __restrict__ ar,
+__global__ __launch_bounds__( SCAN_THREADS ) void k_comp_replay1( const float * __restrict__ xl, const float * __restrict__ ar,
 	const float * __restrict__ aa, int64_t n, int run, const double * __restrict__ carry1, float * __restrict__ y1_out, Map2 * __restrict__ tot2 )
 	{
-	__shared__ Map1 s_tot1[COMP_WAVES];
-	__shared__ Map2 s_tot2[COMP_WAVES];
+	__shared__ Map1 s_tot1[SCAN_WAVES];
+	__shared__ Map2 s_tot2[SCAN_WAVES];
 	int64_t f0; int len;
 	lane_run( n, run, f0, len );
 	Map1 excl, total;
-	block_scan( summarise1<VEC>( xl, ar, n, f0, len ), s_tot1, excl, total );
+	block_scan( summarise1<VEC>( xl, ar, f0, len ), s_tot1, excl, total );
 	float y_1 = float( apply( excl, carry1[blockIdx.x] ) );
 	Map2 m2 = identity2();
 	for( int i = 0; i < len; i += 4 )
 		{
 		float x[4], a[4], A[4], y[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-		load4<VEC>( xl, f0 + i, n, x );
-		load4<VEC>( ar, f0 + i, n, a );
-		load4<VEC>( aa, f0 + i, n, A );
+		load4<VEC>( xl, f0 + i, len - i, x );
+		load4<VEC>( ar, f0 + i, len - i, a );
+		load4<VEC>( aa, f0 + i, len - i, A );
 		#pragma unroll
 		for( int k = 0; k < 4; ++k )
 			if( i + k < len )
@@ -307,20 +206,20 @@ __global__ __launch_bounds__( COMP_THREADS ) void k_comp_replay1( const float * 
 
 // Stage 2 replayed (:251 in fp32) and :272: c = pow( 10.0f, -y_L / 20.0f )
 template<bool VEC>
-__global__ __launch_bounds__( COMP_THREADS ) void k_comp_replay2( const float * __restrict__ y1, const float * __restrict__ aa, int64_t n, int run,
+__global__ __launch_bounds__( SCAN_THREADS ) void k_comp_replay2( const float * __restrict__ y1, const float * __restrict__ aa, int64_t n, int run,
 	const double * __restrict__ carry2, float * __restrict__ gain )
 	{
-	__shared__ Map2 s_tot[COMP_WAVES];
+	__shared__ Map2 s_tot[SCAN_WAVES];
 	int64_t f0; int len;
 	lane_run( n, run, f0, len );
 	Map2 excl, total;
-	block_scan( summarise2<VEC>( y1, aa, n, f0, len ), s_tot, excl, total );
+	block_scan( summarise2<VEC>( y1, aa, f0, len ), s_tot, excl, total );
 	float y_L = float( apply( excl, carry2[blockIdx.x] ) );
 	for( int i = 0; i < len; i += 4 )
 		{
 		float y[4], A[4], c[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-		load4<VEC>( y1, f0 + i, n, y );
-		load4<VEC>( aa, f0 + i, n, A );
+		load4<VEC>( y1, f0 + i, len - i, y );
+		load4<VEC>( aa, f0 + i, len - i, A );
 		#pragma unroll
 		for( int k = 0; k < 4; ++k )
 			if( i + k < len )
@@ -376,6 +275,16 @@ __global__ __launch_bounds__( 256 ) void k_gain_apply( const float * in, float *
 		}
 	}
 
+// the block's maximum of one value per thread (256 threads), in thread 0
+__device__ __forceinline__ float block_max( float mx, float * s_red )
+	{
+	#pragma unroll
+	for( int off = 32; off > 0; off >>= 1 ) mx = fmaxf( mx, __shfl_xor( mx, off ) );
+	if( ( threadIdx.x & 63 ) == 0 ) s_red[threadIdx.x >> 6] = mx;
+	__syncthreads();
+	return fmaxf( fmaxf( s_red[0], s_red[1] ), fmaxf( s_red[2], s_red[3] ) );
+	}
+
 // max |x| over frames [0, end) of every channel: one partial maximum per block (NaN skipped, as std::max( m, |x| ) skips it), no atomics
 __global__ __launch_bounds__( 256 ) void k_absmax_partial( const float * __restrict__ in, int64_t ch, int64_t n, int64_t end, float * __restrict__ partial )
 	{
@@ -383,11 +292,8 @@ __global__ __launch_bounds__( 256 ) void k_absmax_partial( const float * __restr
 	float mx = 0.0f;
 	for( int64_t f = int64_t( blockIdx.x ) * 256 + threadIdx.x; f < end; f += int64_t( gridDim.x ) * 256 )
 		for( int64_t c = 0; c < ch; ++c ) mx = fmaxf( mx, fabsf( in[c * n + f] ) );
-	#pragma unroll
-	for( int off = 32; off > 0; off >>= 1 ) mx = fmaxf( mx, __shfl_xor( mx, off ) );
-	if( ( threadIdx.x & 63 ) == 0 ) s_red[threadIdx.x >> 6] = mx;
-	__syncthreads();
-	if( threadIdx.x == 0 ) partial[blockIdx.x] = fmaxf( fmaxf( s_red[0], s_red[1] ), fmaxf( s_red[2], s_red[3] ) );
+	mx = block_max( mx, s_red );
+	if( threadIdx.x == 0 ) partial[blockIdx.x] = mx;
 	}
 
 __global__ __launch_bounds__( 256 ) void k_absmax_final( const float * __restrict__ partial, int count, float * __restrict__ d_max )
@@ -395,16 +301,11 @@ __global__ __launch_bounds__( 256 ) void k_absmax_final( const float * __restric
 	__shared__ float s_red[4];
 	float mx = 0.0f;
 	for( int i = threadIdx.x; i < count; i += 256 ) mx = fmaxf( mx, partial[i] );
-	#pragma unroll
-	for( int off = 32; off > 0; off >>= 1 ) mx = fmaxf( mx, __shfl_xor( mx, off ) );
-	if( ( threadIdx.x & 63 ) == 0 ) s_red[threadIdx.x >> 6] = mx;
-	__syncthreads();
-	if( threadIdx.x == 0 ) *d_max = fmaxf( fmaxf( s_red[0], s_red[1] ), fmaxf( s_red[2], s_red[3] ) );
+	mx = block_max( mx, s_red );
+	if( threadIdx.x == 0 ) *d_max = mx;
 	}
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------------
-bool aligned16( const void * p ) { return ( reinterpret_cast<uintptr_t>( p ) & 15 ) == 0; }
-
 int launch_gain_apply( const float * d_in, int64_t ch, int64_t n, const float * d_curve, float scalar, const float * d_max, float * d_out, hipStream_t s )
 	{
 	const bool vec = n % 4 == 0 && aligned16( d_in ) && aligned16( d_out ) && aligned16( d_curve );
@@ -448,15 +349,15 @@ int launch_compress( const CompArgs & a, void * d_ws, hipStream_t s )
 	Map2 * tot2 = ws_at<Map2>( d_ws, l.tot2 );
 	double * carry1 = ws_at<double>( d_ws, l.carry1 ), * carry2 = ws_at<double>( d_ws, l.carry2 );
 	const int64_t n = a.n;
-	// one launch of COMP_THREADS threads per block; a scan kernel comes as its { 16-byte loads, plain } pair
-	auto go = [&]( auto kernel, int64_t blocks, auto... args ) { return launch_kernel( "launch_compress", kernel, blocks, COMP_THREADS, 0, s, args... ); };
+	// one launch of SCAN_THREADS threads per block; a scan kernel comes as its { 16-byte loads, plain } pair
+	auto go = [&]( auto kernel, int64_t blocks, auto... args ) { return launch_kernel( "launch_compress", kernel, blocks, SCAN_THREADS, 0, s, args... ); };
 	const bool vec = l.run % 4 == 0 && aligned16( d_ws );        // every run then starts on a 16-byte boundary of the padded rows
-	if( int rc = go( k_comp_level, ( n + COMP_THREADS - 1 ) / COMP_THREADS, a.side, a.side_ch, a.side_n, n, a.sr, a.p, xl, ar, aa ) ) return rc;
-	if( int rc = vec ? go( k_comp_sum1<true>, l.blocks, xl, ar, n, l.run, tot1 ) : go( k_comp_sum1<false>, l.blocks, xl, ar, n, l.run, tot1 ) ) return rc;
-	if( int rc = go( k_comp_carry<Map1>, 1, tot1, l.blocks, carry1 ) ) return rc;
-	if( int rc = vec ? go( k_comp_replay1<true>, l.blocks, xl, ar, aa, n, l.run, carry1, y1, tot2 ) : go( k_comp_replay1<false>, l.blocks, xl, ar, aa, n, l.run, carry1, y1, tot2 ) ) return rc;
-	if( int rc = go( k_comp_carry<Map2>, 1, tot2, l.blocks, carry2 ) ) return rc;
-	if( int rc = vec ? go( k_comp_replay2<true>, l.blocks, y1, aa, n, l.run, carry2, gain ) : go( k_comp_replay2<false>, l.blocks, y1, aa, n, l.run, carry2, gain ) ) return rc;
+	if( int rc = go( k_comp_level, ( n + SCAN_THREADS - 1 ) / SCAN_THREADS, a.side, a.side_ch, a.side_n, n, a.sr, a.p, xl, ar, aa ) ) return rc;
+	if( int rc = scan_pair( vec, [&]( auto V ) { return go( k_comp_sum1<V.value>, l.blocks, xl, ar, n, l.run, tot1 ); } ) ) return rc;
+	if( int rc = go( k_scan_carry<Map1, double>, 1, tot1, l.blocks, carry1 ) ) return rc;
+	if( int rc = scan_pair( vec, [&]( auto V ) { return go( k_comp_replay1<V.value>, l.blocks, xl, ar, aa, n, l.run, carry1, y1, tot2 ); } ) ) return rc;
+	if( int rc = go( k_scan_carry<Map2, double>, 1, tot2, l.blocks, carry2 ) ) return rc;
+	if( int rc = scan_pair( vec, [&]( auto V ) { return go( k_comp_replay2<V.value>, l.blocks, y1, aa, n, l.run, carry2, gain ); } ) ) return rc;
 	if( a.gain_out ) FLANHIP_CHECK( hipMemcpyAsync( a.gain_out, gain, sizeof( float ) * size_t( n ), hipMemcpyDeviceToDevice, s ) );
 	return launch_gain_apply( a.audio, a.ch, n, gain, 0.0f, nullptr, a.out, s );
 	}
@@ -557,7 +458,7 @@ int flanhip_audio_set_volume_dev( const float * d_audio, int64_t num_channels, i
 	static_assert( VOL_PARTIAL_OFF + sizeof( float ) * VOL_MAX_PARTIALS <= VOL_WS_BYTES, "the partial maxima fit" );
 	float * d_max = ws_at<float>( d_workspace, 0 );
 	float * partial = ws_at<float>( d_workspace, VOL_PARTIAL_OFF );
-	const int64_t end = volume_end( num_frames, sample_rate );
+	const int64_t end = max_magnitude_end( num_frames, sample_rate );
 	const int blocks = int( std::clamp<int64_t>( ( end + 255 ) / 256, 1, VOL_MAX_PARTIALS ) );
 	if( int rc = launch_kernel( __func__, k_absmax_partial, blocks, 256, 0, s, d_audio, num_channels, num_frames, end, partial ) ) return rc;
 	if( int rc = launch_kernel( __func__, k_absmax_final, 1, 256, 0, s, partial, blocks, d_max ) ) return rc;

@@ -76,16 +76,6 @@ bool conv_shape( int64_t ch, int64_t n, int64_t irch, int64_t m, ConvShape * s )
 	return ch * s->J < ( int64_t( 1 ) << 24 ) && s->ir_used * s->K < ( int64_t( 1 ) << 24 ) && delay_blocks < ( int64_t( 1 ) << 24 );
 	}
 
-// AudioBuffer::get_max_sample_magnitude() with default arguments scans frames [0, end): end = clamp( Frame( time_to_frame( get_length() ) ),
-// 0, N - 1 ), the fp32 expressions of AudioBuffer.cpp:401-430 (get_length() = N / sr, time_to_frame( t ) = t * sr)
-int64_t conv_norm_end( int64_t nout, float sr )
-	{
-	const float length = float( nout ) / sr;
-	const float f = length * sr;
-	const int64_t e = f >= 9.0e18f ? nout : int64_t( f );
-	return std::clamp<int64_t>( e, 0, nout - 1 );
-	}
-
 // rfft of 2P = 2C real points per block: src rows of `len` samples; block b -> row b / parts, partition j = b % parts; the 2C samples
 // start at j C - shift and only the first `lim` of them are taken (the rest are zeros), as are samples outside [0, len).
 // dst[( row dst_parts + j ) (C+1) + k], k = 0 .. C.
@@ -309,7 +299,7 @@ int launch_convolve( const float * d_x, int64_t ch, int64_t n, const float * d_h
 	std::shared_ptr<const PlanRef> plan;
 	if( int rc = get_plan( 2 * sh.P, 2 * sh.P, &plan ) ) return rc;      // tw [P] and tw2 [P+1] of a 2P-point real transform
 	const int64_t nout = n + m;
-	const int64_t end = conv_norm_end( nout, sr );
+	const int64_t end = max_magnitude_end( nout, sr );
 	if( int rc = launch_conv_ffts_any( false, sh, d_x, ch, n, d_h, m, d_ws, d_out, normalize, end, plan->plan, s ) ) return rc;
 	if( normalize ) FLANHIP_CHECK( hipMemsetAsync( ws_at<char>( d_ws, sh.word_off ), 0, CONV_MAX_BYTES, s ) );
 	const int B = sh.P + 1;

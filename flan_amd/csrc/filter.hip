@@ -12,17 +12,16 @@
 //                    (:19-30, :119-120); skipped for a scalar cutoff, whose g is computed on the host
 //   per section      k_filt_sum reduces every lane's run of consecutive frames to one map (fp64, from the fp32 step values the replay
 //                    uses), scans the maps across the wavefront (__shfl_up) and the block (LDS) and leaves the block's total;
-//                    k_filt_carry (one block per channel) scans the block totals into the state at every block's first frame, from the
+//                    k_scan_carry (one block per channel) scans the block totals into the state at every block's first frame, from the
 //                    state 0 before frame 0; k_filt_replay scans the block again, hands every lane the state at its run's first frame --
 //                    rounded to fp32 once -- and REPLAYS the run with the reference's own fp32 operations in the reference's order.
 // Launch boundaries order everything: no block waits for another, no flags, no atomics.  Every composition runs in a fixed order: two
 // calls agree bit for bit, and a channel's output does not depend on the channels filtered with it.  A lane reads its run before it writes
 // it and reads no other lane's, so a section runs in place: `out` is the working row from the second section on, and may be the input.
 // tan is the fp64 function of the fp32 product rounded to fp32 once (compress.hip's rule for exp / log10 / pow).
-// The scan helpers restate compress.hip's (which keeps them private) for maps of two and of six numbers.
-#include "flanhip_internal.h"
-
-#include <algorithm>
+// The geometry, block_scan, load4 / store4, lane_run and k_scan_carry are run_scan.h's, shared with compress.hip; the maps of two and of
+// six numbers and everything per frame are this file's.
+#include "run_scan.h"
 
 namespace flanhip {
 
@@ -30,20 +29,10 @@ namespace {
 
 thread_local int t_filt_run = 0;          // flanhip_filter_debug_run: frames per lane forced for the calling thread (0: the library's choice)
 
-constexpr int FILT_THREADS = 256;
-constexpr int FILT_WAVES = FILT_THREADS / 64;
-constexpr int FILT_RUN = 16;              // frames per lane: 4096 per block, 703 blocks per channel for a minute at 48 kHz
-constexpr int FILT_MAX_RUN = 64;
 constexpr int FILT_MAX_ORDER = 65535;
 constexpr int64_t FILT_MAX_FRAMES = int64_t( 1 ) << 36;
 constexpr int64_t FILT_MAX_CHANNELS = 1 << 20;
 constexpr int64_t FILT_MAX_GRID = ( int64_t( 1 ) << 31 ) - 1;      // blocks x channels of one launch
-
-int filt_run()
-	{
-	const int forced = t_filt_run;
-	return forced > 0 ? std::min( forced, FILT_MAX_RUN ) : FILT_RUN;
-	}
 
 // What the device code is told about a section.  Butterworth and repeat differ only in the list they make of these.
 struct FilterSection
@@ -70,9 +59,8 @@ struct FiltLayout
 bool filt_layout( int64_t ch, int64_t n, FiltLayout * l )
 	{
 	if( ch <= 0 || n <= 0 || ch > FILT_MAX_CHANNELS || n > FILT_MAX_FRAMES ) return false;
-	l->run = filt_run();
-	const int64_t per_block = int64_t( FILT_THREADS ) * l->run;
-	l->blocks = ( n + per_block - 1 ) / per_block;
+	l->run = scan_run( t_filt_run );
+	l->blocks = scan_blocks( n, l->run );
 	if( l->blocks > FILT_MAX_GRID / ch ) return false;
 	const size_t units = size_t( ch ) * size_t( l->blocks );
 	l->g = 0;
@@ -160,70 +148,6 @@ __device__ __forceinline__ Map2 shfl_up( const Map2 & m, int off )
 	return Map2{ __shfl_up( m.a11, off ), __shfl_up( m.a12, off ), __shfl_up( m.a21, off ), __shfl_up( m.a22, off ), __shfl_up( m.b1, off ), __shfl_up( m.b2, off ) };
 	}
 
-// Scan of one map per thread over the block, in thread order: excl = the maps of all earlier threads composed, total = the block's.
-// Every thread of the block calls it.
-template<typename M>
-__device__ __forceinline__ void block_scan( const M & mine, M * s_tot, M & excl, M & total )
-	{
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	M inc = mine;
-	#pragma unroll
-	for( int off = 1; off < 64; off <<= 1 )
-		{
-		const M o = shfl_up( inc, off );
-		if( lane >= off ) inc = then( o, inc );
-		}
-	if( lane == 63 ) s_tot[wave] = inc;
-	__syncthreads();
-	M prev = shfl_up( inc, 1 );
-	if( lane == 0 ) set_identity( prev );
-	M pre; set_identity( pre );
-	for( int w = 0; w < wave; ++w ) pre = then( pre, s_tot[w] );
-	excl = then( pre, prev );
-	total = s_tot[0];
-	#pragma unroll
-	for( int w = 1; w < FILT_WAVES; ++w ) total = then( total, s_tot[w] );
-	__syncthreads();
-	}
-
-// the first `valid` of four consecutive floats from frame f of a row (VEC: all four: f a multiple of 4, the row 16-byte aligned and a run
-// whole quads); otherwise nothing past the run is read: those frames are the next lane's, which may be writing them when dst is src
-template<bool VEC>
-__device__ __forceinline__ void load4( const float * p, int64_t f, int valid, float ( &v )[4] )
-	{
-	if constexpr( VEC )
-		{
-		const float4 q = *reinterpret_cast<const float4*>( p + f );
-		v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-		}
-	else
-		{
-		#pragma unroll
-		for( int k = 0; k < 4; ++k ) v[k] = k < valid ? p[f + k] : 0.0f;
-		}
-	}
-// the first `valid` of four values to frame f on.  VEC: all four (a run is whole quads then); otherwise nothing past the run: those
-// frames are the next lane's
-template<bool VEC>
-__device__ __forceinline__ void store4( float * p, int64_t f, int valid, const float ( &v )[4] )
-	{
-	if constexpr( VEC ) *reinterpret_cast<float4*>( p + f ) = make_float4( v[0], v[1], v[2], v[3] );
-	else
-		{
-		#pragma unroll
-		for( int k = 0; k < 4; ++k ) if( k < valid ) p[f + k] = v[k];
-		}
-	}
-
-// the block's channel and the run of the calling thread in it: frames [f0, f0 + len).  The grid is blocks x channels, flattened
-__device__ __forceinline__ void lane_run( int64_t n, int run, int64_t blocks, int64_t & channel, int64_t & f0, int & len )
-	{
-	channel = int64_t( blockIdx.x ) / blocks;
-	const int64_t block = int64_t( blockIdx.x ) - channel * blocks;
-	f0 = ( block * FILT_THREADS + threadIdx.x ) * run;
-	len = int( std::min<int64_t>( std::max<int64_t>( n - f0, 0 ), run ) );
-	}
-
 // a run of a section as one map: the steps composed in frame order.  g: the row of k_filt_coef, or null for the scalar g_c
 template<int POLES, bool VEC>
 __device__ __forceinline__ typename MapOf<POLES>::type summarise( const float * x_row, const float * g_row, float g_c, float R, int64_t f0, int len )
@@ -248,18 +172,18 @@ __device__ __forceinline__ typename MapOf<POLES>::type summarise( const float * 
 
 // ---- kernels ----------------------------------------------------------------------------------------------------------------------
 // one frame per thread
-__global__ __launch_bounds__( FILT_THREADS ) void k_filt_coef( const float * __restrict__ cutoff, int64_t n, float T_half, float nyquist, float * __restrict__ g )
+__global__ __launch_bounds__( SCAN_THREADS ) void k_filt_coef( const float * __restrict__ cutoff, int64_t n, float T_half, float nyquist, float * __restrict__ g )
 	{
-	const int64_t f = int64_t( blockIdx.x ) * FILT_THREADS + threadIdx.x;
+	const int64_t f = int64_t( blockIdx.x ) * SCAN_THREADS + threadIdx.x;
 	if( f < n ) g[f] = filt_g( cutoff[f], T_half, nyquist );
 	}
 
 template<int POLES, bool VEC>
-__global__ __launch_bounds__( FILT_THREADS ) void k_filt_sum( const float * __restrict__ src, int64_t n, int run, int64_t blocks,
+__global__ __launch_bounds__( SCAN_THREADS ) void k_filt_sum( const float * __restrict__ src, int64_t n, int run, int64_t blocks,
 	const float * __restrict__ g_row, float g_c, FilterSection sec, typename MapOf<POLES>::type * __restrict__ tot )
 	{
 	using M = typename MapOf<POLES>::type;
-	__shared__ M s_tot[FILT_WAVES];
+	__shared__ M s_tot[SCAN_WAVES];
 	int64_t channel, f0; int len;
 	lane_run( n, run, blocks, channel, f0, len );
 	M excl, total;
@@ -267,34 +191,14 @@ __global__ __launch_bounds__( FILT_THREADS ) void k_filt_sum( const float * __re
 	if( threadIdx.x == 0 ) tot[blockIdx.x] = total;
 	}
 
-// One block per channel: the state at the first frame of every block of the scan, from the block totals and the state 0 before frame 0
-template<typename M>
-__global__ __launch_bounds__( FILT_THREADS ) void k_filt_carry( const M * __restrict__ tot, int64_t blocks, State * __restrict__ carry )
-	{
-	__shared__ M s_tot[FILT_WAVES];
-	tot += int64_t( blockIdx.x ) * blocks;
-	carry += int64_t( blockIdx.x ) * blocks;
-	State state{ 0.0, 0.0 };
-	for( int64_t base = 0; base < blocks; base += FILT_THREADS )
-		{
-		const int64_t b = base + threadIdx.x;
-		M mine; set_identity( mine );
-		if( b < blocks ) mine = tot[b];
-		M excl, total;
-		block_scan( mine, s_tot, excl, total );
-		if( b < blocks ) carry[b] = apply( excl, state );
-		state = apply( total, state );
-		}
-	}
-
 // The section replayed in fp32 from the carried-in state, its tapped output written.  dst may be src: a lane has read its run when it
 // writes it, and reads no other
 template<int POLES, bool VEC>
-__global__ __launch_bounds__( FILT_THREADS ) void k_filt_replay( const float * src, float * dst, int64_t n, int run, int64_t blocks,
+__global__ __launch_bounds__( SCAN_THREADS ) void k_filt_replay( const float * src, float * dst, int64_t n, int run, int64_t blocks,
 	const float * __restrict__ g_row, float g_c, FilterSection sec, const State * __restrict__ carry )
 	{
 	using M = typename MapOf<POLES>::type;
-	__shared__ M s_tot[FILT_WAVES];
+	__shared__ M s_tot[SCAN_WAVES];
 	int64_t channel, f0; int len;
 	lane_run( n, run, blocks, channel, f0, len );
 	const float * x_row = src + channel * n;
@@ -316,8 +220,6 @@ __global__ __launch_bounds__( FILT_THREADS ) void k_filt_replay( const float * s
 	}
 
 // ---- launchers --------------------------------------------------------------------------------------------------------------------
-bool aligned16( const void * p ) { return ( reinterpret_cast<uintptr_t>( p ) & 15 ) == 0; }
-
 struct FiltArgs
 	{
 	const float * audio; int64_t ch, n; float sr;
@@ -377,14 +279,14 @@ int launch_filter( const FiltArgs & a, void * d_ws, hipStream_t s )
 		else if( a.out != a.audio ) FLANHIP_CHECK( hipMemcpyAsync( a.out, a.audio, bytes, hipMemcpyDeviceToDevice, s ) );
 		return FLANHIP_OK;
 		}
-	auto go = [&]( auto kernel, int64_t blocks, auto... args ) { return launch_kernel( "launch_filter", kernel, blocks, FILT_THREADS, 0, s, args... ); };
+	auto go = [&]( auto kernel, int64_t blocks, auto... args ) { return launch_kernel( "launch_filter", kernel, blocks, SCAN_THREADS, 0, s, args... ); };
 	const float T_half = acosf( -1.0f ) / a.sr, nyquist = a.sr / 2.0f;        // :57
 	const float * g_row = nullptr;
 	float g_c = 0.0f;
 	if( a.cutoff )
 		{
 		float * g = ws_at<float>( d_ws, l.g );
-		if( int rc = go( k_filt_coef, ( n + FILT_THREADS - 1 ) / FILT_THREADS, a.cutoff, n, T_half, nyquist, g ) ) return rc;
+		if( int rc = go( k_filt_coef, ( n + SCAN_THREADS - 1 ) / SCAN_THREADS, a.cutoff, n, T_half, nyquist, g ) ) return rc;
 		g_row = g;
 		}
 	else g_c = filt_g( a.cutoff_c, T_half, nyquist );
@@ -399,15 +301,15 @@ int launch_filter( const FiltArgs & a, void * d_ws, hipStream_t s )
 		{
 		if( sec.poles == 1 )
 			{
-			if( int rc = vec ? go( k_filt_sum<1, true>, grid, src, n, l.run, l.blocks, g_row, g_c, sec, tot1 ) : go( k_filt_sum<1, false>, grid, src, n, l.run, l.blocks, g_row, g_c, sec, tot1 ) ) return rc;
-			if( int rc = go( k_filt_carry<Map1>, a.ch, tot1, l.blocks, carry ) ) return rc;
-			if( int rc = vec ? go( k_filt_replay<1, true>, grid, src, a.out, n, l.run, l.blocks, g_row, g_c, sec, carry ) : go( k_filt_replay<1, false>, grid, src, a.out, n, l.run, l.blocks, g_row, g_c, sec, carry ) ) return rc;
+			if( int rc = scan_pair( vec, [&]( auto V ) { return go( k_filt_sum<1, V.value>, grid, src, n, l.run, l.blocks, g_row, g_c, sec, tot1 ); } ) ) return rc;
+			if( int rc = go( k_scan_carry<Map1, State>, a.ch, tot1, l.blocks, carry ) ) return rc;
+			if( int rc = scan_pair( vec, [&]( auto V ) { return go( k_filt_replay<1, V.value>, grid, src, a.out, n, l.run, l.blocks, g_row, g_c, sec, carry ); } ) ) return rc;
 			}
 		else
 			{
-			if( int rc = vec ? go( k_filt_sum<2, true>, grid, src, n, l.run, l.blocks, g_row, g_c, sec, tot2 ) : go( k_filt_sum<2, false>, grid, src, n, l.run, l.blocks, g_row, g_c, sec, tot2 ) ) return rc;
-			if( int rc = go( k_filt_carry<Map2>, a.ch, tot2, l.blocks, carry ) ) return rc;
-			if( int rc = vec ? go( k_filt_replay<2, true>, grid, src, a.out, n, l.run, l.blocks, g_row, g_c, sec, carry ) : go( k_filt_replay<2, false>, grid, src, a.out, n, l.run, l.blocks, g_row, g_c, sec, carry ) ) return rc;
+			if( int rc = scan_pair( vec, [&]( auto V ) { return go( k_filt_sum<2, V.value>, grid, src, n, l.run, l.blocks, g_row, g_c, sec, tot2 ); } ) ) return rc;
+			if( int rc = go( k_scan_carry<Map2, State>, a.ch, tot2, l.blocks, carry ) ) return rc;
+			if( int rc = scan_pair( vec, [&]( auto V ) { return go( k_filt_replay<2, V.value>, grid, src, a.out, n, l.run, l.blocks, g_row, g_c, sec, carry ); } ) ) return rc;
 			}
 		src = a.out;
 		}

@@ -1,6 +1,7 @@
 // flanhip_internal.h -- host-side plumbing shared by the C-ABI translation units.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -47,6 +48,16 @@ template<typename T> T * ws_at( void * d_ws, size_t offset ) { return reinterpre
 
 inline bool is_pow2( int64_t n ) { return n > 0 && ( n & ( n - 1 ) ) == 0; }
 inline int ilog2( int64_t n ) { int l = 0; while( ( int64_t( 1 ) << l ) < n ) ++l; return l; }
+// AudioBuffer::get_max_sample_magnitude() with default arguments scans frames [0, end) of n: end = clamp( Frame( time_to_frame( get_length() ) ),
+// 0, n - 1 ), the fp32 expressions of AudioBuffer.cpp:401-430 (get_length() = n / sr, time_to_frame( t ) = t * sr): what set_volume and
+// convolve's normalize look at
+inline int64_t max_magnitude_end( int64_t n, float sr )
+	{
+	const float length = float( n ) / sr;
+	const float f = length * sr;
+	const int64_t e = f >= 9.0e18f ? n : int64_t( f );
+	return std::clamp<int64_t>( e, 0, n - 1 );
+	}
 inline bool cancelled( volatile int * c ) { return c && *c != 0; }
 // cancellation inside a launch (core.hip): the calling thread's cancel word on the current device (kernels poll it; nullptr if it cannot be had),
 // and a wait for a stream that polls `poll( user )` and raises the word when it says so (FLANHIP_ERR_CANCELLED then)
