@@ -9,8 +9,9 @@
 // lanes' demodulated values (shuffles) and, at the tile's two ends, one extra bin that lanes 0 and 63 walk alongside their own.
 //
 // Synthesis.  Per bin the reference accumulates phase increments in fp64 and folds them (phase_vocoder.cpp:55-61); a chain of frames
-// starts from its carry: k_spv_chain_sums sums every chain (folded like the reference), k_spv_scan turns the sums into carries, and
-// k_spv_synthesize walks each chain from its carry, one block per chain, and reduces the bins of 32 frames at a time through LDS.
+// starts from its carry: k_spv_chain_sums sums every chain (its total and its highest prefix sum), k_spv_scan turns them into the
+// phases the reference holds at the chains' starts, and k_spv_synthesize walks each chain from its carry, one block per chain, and
+// reduces the bins of 32 frames at a time through LDS.
 //
 // All indices are 64-bit: the reference's int32 (f b) % L turns negative past f b >= 2^31 (AudioSPV.cpp:38), here the twiddle index is
 // (f b) mod L as intended.  num_bins < 2 is refused (the reference reads bin 1 of a one-bin frame, AudioSPV.cpp:67).
@@ -274,6 +275,7 @@ struct SpvSyn
 	{
 	const flanhip_MF * spv;   // [ch][n][N]
 	double * carry;           // [ch][chains][N]: chain sums, then carries
+	double * peak;            // [ch][chains][N]: the highest prefix sum of each chain
 	float * out;              // [ch][n]
 	int64_t n, C, chains;
 	int N;
@@ -288,7 +290,20 @@ __device__ __forceinline__ double spv_advance( double ph, float f, float ar )
 	return ph < FLANHIP_FOLD_FAST_LIMIT ? fold_phase_fast( ph ) : fold_phase_any( ph );
 	}
 
-// one thread per (channel, chain, bin): the chain's own folded sum, started from 0
+// What a chain does to the phase that enters it.  The reference folds only a phase above pi2, by the FLOAT pi2 (each fold moves the
+// angle by 1.7e-7 rad), and never a negative one; which multiple of pi2 it holds is therefore part of its result, and so is the
+// number of folds.  With U_i the chain's unfolded prefix sums, a phase p that enters has been folded floor( ( p + max_i U_i ) / pi2 )
+// times by the chain's end if p + max_i U_i > pi2, and not at all otherwise: a chain is summed up by its total and its highest prefix
+// sum, and the scan applies them to the true carry.  (Folding each chain's sum on its own, as if it started from 0, folds where the
+// reference does not: a phase that wanders on both sides of 0, a repitched analysis for one, then sinks by one pi2 after another.)
+// The unfolded sums are exact to well below the float( phase ) the cosine takes while they stay under 2^21 rad (ulp 4.7e-10).  Above --
+// a chain held near 1e9 Hz, one MF of 1e20 Hz, where the reference's own addition rounds the running phase to whole radians, or a
+// frequency that is not finite -- what comes out depends on the phase that went in: such a chain hands the scan SPV_REWALK instead of
+// a total, and the scan walks its frames from the carry like the reference.  +inf is free for that: no other total reaches it.
+#define SPV_SUM_LIMIT 0x1p21
+#define SPV_REWALK __builtin_inf()
+
+// one thread per (channel, chain, bin): the chain's unfolded total (or SPV_REWALK) and its highest prefix sum
 __global__ __launch_bounds__( 256 ) void k_spv_chain_sums( SpvSyn p, int64_t ch )
 	{
 	const int64_t t = int64_t( blockIdx.x ) * blockDim.x + threadIdx.x;
@@ -299,12 +314,21 @@ __global__ __launch_bounds__( 256 ) void k_spv_chain_sums( SpvSyn p, int64_t ch 
 	if( chain == p.chains - 1 ) return;                                   // the last chain's sum is nobody's carry
 	const int64_t f0 = chain * p.C, f1 = std::min( f0 + p.C, p.n );
 	const flanhip_MF * col = p.spv + ( c * p.n ) * int64_t( p.N ) + b;
-	double s = 0.0;
-	for( int64_t f = f0; f < f1; ++f ) s = spv_advance( s, col[f * p.N].f, p.ar );
-	p.carry[t] = s;
+	double u = 0.0, top = 0.0;
+	bool exact = true;
+	for( int64_t f = f0; f < f1; ++f )
+		{
+		const float pd = col[f * p.N].f / p.ar * FLANHIP_PI2_F;
+		u = u + double( pd );
+		exact = exact && __builtin_fabs( u ) < SPV_SUM_LIMIT;              // false for a NaN as well
+		top = u > top ? u : top;
+		}
+	p.carry[t] = exact ? u : SPV_REWALK;
+	p.peak[t] = top;
 	}
 
-// one thread per (channel, bin): carries in place, carry[0] = 0, carry[k+1] = fold( carry[k] + sum[k] )
+// one thread per (channel, bin): carries in place, carry[0] = 0, carry[k+1] = carry[k] + sum[k] less the folds the reference made on the
+// way, or chain k walked from carry[k]
 __global__ __launch_bounds__( 256 ) void k_spv_scan( SpvSyn p, int64_t ch )
 	{
 	const int64_t t = int64_t( blockIdx.x ) * blockDim.x + threadIdx.x;
@@ -312,20 +336,39 @@ __global__ __launch_bounds__( 256 ) void k_spv_scan( SpvSyn p, int64_t ch )
 	const int b = int( t % p.N );
 	const int64_t c = t / p.N;
 	double * col = p.carry + c * p.chains * p.N + b;
+	const double * pk = p.peak + c * p.chains * p.N + b;
 	// the loads do not depend on the carry: 16 of them in flight at a time, then the dependent adds (a 1-channel scan walks ~2000 chains)
 	double carry = 0.0;
 	for( int64_t k0 = 0; k0 < p.chains; k0 += 16 )
 		{
-		double s[16];
+		double s[16], top[16];
 		#pragma unroll
-		for( int i = 0; i < 16; ++i ) s[i] = k0 + i < p.chains - 1 ? col[( k0 + i ) * p.N] : 0.0;   // the last chain's sum is never written
+		for( int i = 0; i < 16; ++i )
+			{
+			const bool have = k0 + i < p.chains - 1;                          // the last chain's sum is never written
+			s[i] = have ? col[( k0 + i ) * p.N] : 0.0;
+			top[i] = have ? pk[( k0 + i ) * p.N] : 0.0;
+			}
 		#pragma unroll
 		for( int i = 0; i < 16; ++i )
 			{
 			if( k0 + i >= p.chains ) break;
 			col[( k0 + i ) * p.N] = carry;
-			const double v = carry + s[i];
-			carry = v < FLANHIP_FOLD_FAST_LIMIT ? fold_phase_fast( v ) : fold_phase_any( v );
+			if( s[i] == SPV_REWALK )
+				{
+				const flanhip_MF * mf = p.spv + ( c * p.n ) * int64_t( p.N ) + b;
+				const int64_t f0 = ( k0 + i ) * p.C, f1 = std::min( f0 + p.C, p.n );
+				for( int64_t f = f0; f < f1; ++f ) carry = spv_advance( carry, mf[f * p.N].f, p.ar );
+				continue;
+				}
+			const double high = carry + top[i];
+			double q = 0.0;
+			if( high > FLANHIP_PI2_D )
+				{
+				q = __builtin_floor( high / FLANHIP_PI2_D );
+				if( __builtin_fma( -q, FLANHIP_PI2_D, high ) < 0.0 ) q -= 1.0;
+				}
+			carry = __builtin_fma( -q, FLANHIP_PI2_D, carry + s[i] );
 			}
 		}
 	}
@@ -465,7 +508,7 @@ size_t spv_ws_bytes( int64_t ch, int64_t n, int N )
 	{
 	const int64_t C = spv_synthesis_chain( ch, n );
 	const int64_t chains = ( n + C - 1 ) / C;
-	return sizeof( double ) * size_t( ch ) * size_t( chains ) * size_t( N );
+	return 2 * sizeof( double ) * size_t( ch ) * size_t( chains ) * size_t( N );      // totals / carries, and peaks
 	}
 
 int launch_spv_synthesize( const flanhip_MF * d_spv, int64_t ch, int64_t n, int N, float sr, float * d_out, void * d_ws, hipStream_t s )
@@ -478,6 +521,7 @@ int launch_spv_synthesize( const flanhip_MF * d_spv, int64_t ch, int64_t n, int 
 	p.n = n; p.N = N; p.ar = sr;
 	p.C = spv_synthesis_chain( ch, n );
 	p.chains = ( n + p.C - 1 ) / p.C;
+	p.peak = p.carry + ch * p.chains * int64_t( N );
 	const int64_t blocks = ch * p.chains;
 	if( p.chains > 1 )
 		{

@@ -44,7 +44,7 @@ def test_workspace_bytes_without_a_device():
     assert fa.spv_synthesize_workspace_bytes(1, 0, 64, 48000.0) == 0
     # the debug cut changes the chain count, and the size with it
     with fa.spv_chain_length(10):
-        assert fa.spv_synthesize_workspace_bytes(1, 1000, 64, 48000.0) == 8 * 100 * 64
+        assert fa.spv_synthesize_workspace_bytes(1, 1000, 64, 48000.0) == 2 * 8 * 100 * 64          # a total and a peak per chain and bin
 
 
 def test_twiddles_are_the_restatements_to_the_bit():
