@@ -152,6 +152,9 @@ _SIGS = {
     "flanhip_filter_1pole": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _f32, _i32, _i32, _vp, _vp]),
     "flanhip_filter_1pole_dev": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _f32, _i32, _i32, _vp, _vp, _vp]),
     "flanhip_filter_debug_run": (None, [_i32]),
+    "flanhip_filter2_workspace_bytes": (C.c_size_t, [_i64, _i64]),
+    "flanhip_filter2": (C.c_int, [_vp, _i64, _i64, _f32] + [_vp, _f32] * 3 + [_i32, _i32, _vp, _vp]),
+    "flanhip_filter2_dev": (C.c_int, [_vp, _i64, _i64, _f32] + [_vp, _f32] * 3 + [_i32, _i32, _vp, _vp, _vp]),
 }
 
 EXPORTS = sorted(_SIGS)
@@ -932,3 +935,47 @@ class filter_run_forced:
     def __exit__(self, *exc):
         lib.flanhip_filter_debug_run(0)
         return False
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Audio::filter_2pole_lowpass / _bandpass / _highpass / _notch, filter_2pole_lowshelf / _bandshelf / _highshelf and filter_1pole_lowshelf /
+# _highshelf.  Cutoff, damping and gain are each a float (the scalar) or an array of n floats (a curve)
+# ---------------------------------------------------------------------------------------------------------------
+
+(FILTER2_1POLE_LOWSHELF, FILTER2_1POLE_HIGHSHELF, FILTER2_LOW, FILTER2_BAND, FILTER2_HIGH, FILTER2_NOTCH, FILTER2_LOWSHELF, FILTER2_BANDSHELF,
+ FILTER2_HIGHSHELF) = range(9)
+
+
+def filter2_workspace_bytes(ch, n):
+    return int(lib.flanhip_filter2_workspace_bytes(ch, n))
+
+
+def _filter2_params(values, n, pointer):
+    """the six (curve, scalar) arguments in the header's order; curves are kept alive by the second return value"""
+    args, keep = [], []
+    for v in values:
+        if isinstance(v, (int, float, np.floating)):
+            args += [None, float(v)]
+        else:
+            if pointer is _ptr:
+                v = np.ascontiguousarray(v, np.float32)
+                assert v.shape == (n,), v.shape
+            keep.append(v)
+            args += [pointer(v), 0.0]
+    return args, keep
+
+
+def filter2(audio, sample_rate, cutoff, damping=1.0, gain=0.0, kind=FILTER2_LOW, order=1):
+    """the nine filters of the FILTER2_* kinds.  audio float32 [ch][n] -> float32 [ch][n]."""
+    audio = np.ascontiguousarray(audio, np.float32)
+    ch, n = audio.shape
+    args, keep = _filter2_params((cutoff, damping, gain), n, _ptr)
+    out = np.empty_like(audio)
+    check(lib.flanhip_filter2(_ptr(audio), ch, n, sample_rate, *args, kind, order, _ptr(out), None))
+    return out
+
+
+def filter2_dev(d_audio, ch, n, sample_rate, cutoff, damping, gain, kind, order, d_out, d_ws, stream=None):
+    """flanhip_filter2_dev: cutoff, damping and gain are floats or device arrays of n floats; d_out may be d_audio (not for FILTER2_NOTCH)"""
+    args, keep = _filter2_params((cutoff, damping, gain), n, _dp)
+    check(lib.flanhip_filter2_dev(_dp(d_audio), ch, n, sample_rate, *args, kind, order, _dp(d_out), _dp(d_ws), _vp(stream or 0)))

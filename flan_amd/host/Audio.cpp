@@ -1,7 +1,7 @@
 // Audio.cpp -- construction and conversions of flan::Audio over the C ABI
 // (reference: src/flan/Audio/AudioConstructors.cpp, Conversions/AudioPV.cpp:12-84, Audio/AudioConversions.cpp:14-56,
 // Audio/AudioCombination.cpp:299-352, Audio/AudioTemporal.cpp:236-299, Audio/AudioVolume.cpp:5-67, 190-278,
-// Audio/AudioFilter.cpp:280-425).
+// Audio/AudioFilter.cpp:280-758).
 #include "flan/Audio.h"
 
 #include <algorithm>
@@ -25,16 +25,42 @@ struct DeviceCurve
 	const float * ptr() const { return block ? static_cast<const float*>( block->ptr ) : nullptr; }
 	};
 
-DeviceCurve upload_curve( const Function<Second, float> & fn, Frame n, float scale )
+// time_of( x ): the time frame x is sampled at
+template<typename TimeOf>
+DeviceCurve upload_curve_at( const Function<Second, float> & fn, Frame n, TimeOf time_of )
 	{
 	DeviceCurve c;
 	if( fn.is_constant() ) { c.scalar = fn.get_constant(); return c; }
 	detail::StagingVector<float> sampled( size_t( std::max( n, 0 ) ) );
-	detail::for_each_index( 0, n, fn.get_execution_policy(), [&]( int x ){ sampled[size_t( x )] = fn( Second( x * scale ) ); } );
+	detail::for_each_index( 0, n, fn.get_execution_policy(), [&]( int x ){ sampled[size_t( x )] = fn( time_of( x ) ); } );
 	c.block = detail::DeviceBlock::allocate( sizeof( float ) * sampled.size() );
 	c.ok = c.block && detail::upload_from_host( c.block->ptr, sampled.data(), sizeof( float ) * sampled.size() );
 	if( c.block && !c.ok ) std::cerr << "flan: upload of a sampled Function failed: " << flanhip_last_error() << std::endl;
 	return c;
+	}
+
+DeviceCurve upload_curve( const Function<Second, float> & fn, Frame n, float scale )
+	{
+	return upload_curve_at( fn, n, [scale]( int x ){ return Second( x * scale ); } );
+	}
+
+// One cascade of flanhip_filter2_dev over `me` with its three arguments already on the device (or scalars): a fresh device block
+Audio filter2_cascade( const Audio & me, const DeviceCurve & cutoff, const DeviceCurve & damping, const DeviceCurve & gain, int kind, uint16_t order,
+	const char * who )
+	{
+	if( me.is_null() ) return Audio::create_null();
+	const size_t ws_bytes = flanhip_filter2_workspace_bytes( me.get_num_channels(), me.get_num_frames() );
+	if( ws_bytes == 0 ) return Audio::create_null();
+	const float * d_x = me.device_data();
+	if( !d_x ) return Audio::create_null();
+	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( me.get_num_channels() ) * size_t( me.get_num_frames() ) );
+	auto ws = detail::DeviceBlock::allocate( ws_bytes );
+	if( !cutoff.ok || !damping.ok || !gain.ok || !block || !ws ) return Audio::create_null();
+	const int rc = flanhip_filter2_dev( d_x, me.get_num_channels(), me.get_num_frames(), me.get_sample_rate(), cutoff.ptr(), cutoff.scalar,
+		damping.ptr(), damping.scalar, gain.ptr(), gain.scalar, kind, int( order ), static_cast<float*>( block->ptr ), ws->ptr, nullptr );
+	if( !detail::report( rc, who ) ) return Audio::create_null();
+	if( !detail::report( flanhip_stream_synchronize( nullptr ), who ) ) return Audio::create_null();                 // the workspace and the curves go back idle
+	return AudioBuffer::adopt_device( me.get_format(), std::move( block ) );
 	}
 
 // One cascade of flanhip_filter_1pole_dev over `me` with a cutoff already on the device (or a scalar): a fresh device block
@@ -367,6 +393,86 @@ Audio Audio::filter_1pole_repeat_high( const Function<Second, Frequency> & cutof
 	{
 	if( is_null() || !device_data() ) return Audio::create_null();
 	return filter_cascade( *this, upload_curve( cutoff, get_num_frames(), frame_to_time( 1 ) ), FLANHIP_FILTER_REPEAT_HIGH, repeats, "filter_1pole_repeat_high" );
+	}
+
+// :533-535: cutoff and damping through sample_function_over_domain, at f * ( 1.0f / sr ); the clamp and everything after it are the device's
+static Audio filter_2pole( const Audio & me, const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping, int kind,
+	uint16_t order, const char * who )
+	{
+	if( me.is_null() || !me.device_data() ) return Audio::create_null();     // :590; without a device nothing is sampled
+	const float step = me.frame_to_time( 1 );
+	return filter2_cascade( me, upload_curve( cutoff, me.get_num_frames(), step ), upload_curve( damping, me.get_num_frames(), step ), DeviceCurve(),
+		kind, order, who );
+	}
+
+Audio Audio::filter_2pole_lowpass( const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping, uint16_t order ) const
+	{
+	return filter_2pole( *this, cutoff, damping, FLANHIP_FILTER2_LOW, order, "filter_2pole_lowpass" );
+	}
+
+Audio Audio::filter_2pole_bandpass( const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping, uint16_t order ) const
+	{
+	return filter_2pole( *this, cutoff, damping, FLANHIP_FILTER2_BAND, order, "filter_2pole_bandpass" );
+	}
+
+Audio Audio::filter_2pole_highpass( const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping, uint16_t order ) const
+	{
+	return filter_2pole( *this, cutoff, damping, FLANHIP_FILTER2_HIGH, order, "filter_2pole_highpass" );
+	}
+
+Audio Audio::filter_2pole_notch( const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping, uint16_t order ) const
+	{
+	return filter_2pole( *this, cutoff, damping, FLANHIP_FILTER2_NOTCH, order, "filter_2pole_notch" );
+	}
+
+// :646-654: the gain through sample_function_over_domain, at f * ( 1.0f / sr ), but cutoff and damping at frame_to_time( f ) = f / sr -- not
+// always the same float.  gain / 2.0f and -gain are exact and are the device's
+static Audio filter_2pole_shelf( const Audio & me, const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping,
+	const Function<Second, Decibel> & gain, int kind, uint16_t order, const char * who )
+	{
+	if( me.is_null() || !me.device_data() ) return Audio::create_null();     // :716
+	const Frame n = me.get_num_frames();
+	auto at = [&me]( int x ){ return me.frame_to_time( fFrame( x ) ); };
+	return filter2_cascade( me, upload_curve_at( cutoff, n, at ), upload_curve_at( damping, n, at ), upload_curve( gain, n, 1.0f / me.get_sample_rate() ),
+		kind, order, who );
+	}
+
+Audio Audio::filter_2pole_lowshelf( const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping,
+	const Function<Second, Decibel> & gain, uint16_t order ) const
+	{
+	return filter_2pole_shelf( *this, cutoff, damping, gain, FLANHIP_FILTER2_LOWSHELF, order, "filter_2pole_lowshelf" );
+	}
+
+Audio Audio::filter_2pole_bandshelf( const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping,
+	const Function<Second, Decibel> & gain, uint16_t order ) const
+	{
+	return filter_2pole_shelf( *this, cutoff, damping, gain, FLANHIP_FILTER2_BANDSHELF, order, "filter_2pole_bandshelf" );
+	}
+
+Audio Audio::filter_2pole_highshelf( const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping,
+	const Function<Second, Decibel> & gain, uint16_t order ) const
+	{
+	return filter_2pole_shelf( *this, cutoff, damping, gain, FLANHIP_FILTER2_HIGHSHELF, order, "filter_2pole_highshelf" );
+	}
+
+// :452-454, :498: cutoff and gain through sample_function_over_domain; the tilt of gain or -gain and the final amp( gain / 2 ) are the device's
+static Audio filter_1pole_shelf( const Audio & me, const Function<Second, Frequency> & cutoff, const Function<Second, Decibel> & gain, int kind,
+	uint16_t order, const char * who )
+	{
+	if( me.is_null() || !me.device_data() ) return Audio::create_null();     // :496, :508
+	const float step = 1.0f / me.get_sample_rate();
+	return filter2_cascade( me, upload_curve( cutoff, me.get_num_frames(), step ), DeviceCurve(), upload_curve( gain, me.get_num_frames(), step ),
+		kind, order, who );
+	}
+
+Audio Audio::filter_1pole_lowshelf( const Function<Second, Frequency> & cutoff, const Function<Second, Decibel> & gain, uint16_t order ) const
+	{
+	return filter_1pole_shelf( *this, cutoff, gain, FLANHIP_FILTER2_1POLE_LOWSHELF, order, "filter_1pole_lowshelf" );
+	}
+
+Audio Audio::filter_1pole_highshelf( const Function<Second, Frequency> & cutoff, const Function<Second, Decibel> & gain, uint16_t order ) const
+	{
+	return filter_1pole_shelf( *this, cutoff, gain, FLANHIP_FILTER2_1POLE_HIGHSHELF, order, "filter_1pole_highshelf" );
 	}
 
 } // namespace flan

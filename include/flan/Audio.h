@@ -100,6 +100,42 @@ public:
 	Audio filter_1pole_repeat_low( const Function<Second, Frequency> & cutoff, const uint16_t repeats ) const;
 	/** The same 1-pole high-pass `repeats` times over (:318-324).  No repeats give silence. */
 	Audio filter_1pole_repeat_high( const Function<Second, Frequency> & cutoff, const uint16_t repeats ) const;
+	/** The Butterworth low shelf: the tilt of `gain` times amp( gain / 2 ) (Audio/AudioFilter.cpp:431-500; The Art of VA Filter Design, 10.2),
+	 *  on the device (flanhip_filter2_dev).  cutoff and gain are sampled once per frame at f * ( 1.0f / sample rate ); a constant
+	 *  samples nothing.  The cutoff is clamped to [1, sample rate / 2] BEFORE it is scaled by M = amp( gain / ( 2 order ) ).  Kept quirks: the
+	 *  2-pole sections run with R = Re( pole ) / w, negative and tiny, so from order 2 on the filter is mildly unstable (order 4 puts out
+	 *  x 1000); order 0 is a copy times amp( gain / 2 ).  A null *this gives a null Audio.  The result stays device-resident. */
+	Audio filter_1pole_lowshelf( const Function<Second, Frequency> & cutoff, const Function<Second, Decibel> & gain, uint16_t order = 1 ) const;
+	/** The Butterworth high shelf (:502-512): the tilt of -gain times amp( gain / 2 ).  The quirks of filter_1pole_lowshelf. */
+	Audio filter_1pole_highshelf( const Function<Second, Frequency> & cutoff, const Function<Second, Decibel> & gain, uint16_t order = 1 ) const;
+
+	/** The resonant low-pass of order N: a Butterworth filter whose every pole is split in two by the damping (:520-592; 10.4), N
+	 *  state-variable sections with a per-frame cutoff and damping, each a scan over the frames (flanhip_filter2_dev).  cutoff
+	 *  and damping are sampled once per frame at f * ( 1.0f / sample rate ); a constant samples nothing.  The cutoff is clamped to [1, sample
+	 *  rate / 2], the damping is not.  Kept quirks: a damping above 1 at a frame makes acos( damping ) NaN, so every ODD order, order 1 included,
+	 *  puts out NaN from that frame on (even orders are fine); order 0 is a copy.  A null *this gives a null Audio.  The result stays
+	 *  device-resident until read. */
+	Audio filter_2pole_lowpass( const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping, uint16_t order = 1 ) const;
+	/** The band-pass (:594-602): every section's bp * 2 * R with the section's own R.  The quirks of filter_2pole_lowpass. */
+	Audio filter_2pole_bandpass( const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping, uint16_t order = 1 ) const;
+	/** The high-pass (:604-612).  The quirks of filter_2pole_lowpass. */
+	Audio filter_2pole_highpass( const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping, uint16_t order = 1 ) const;
+	/** The input minus the band-pass, ( 0 + ( -band ) ) + x per sample (:614-624).  The quirks of filter_2pole_lowpass, and order 0 is
+	 *  SILENCE: the band-pass of order 0 is a copy. */
+	Audio filter_2pole_notch( const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping, uint16_t order = 1 ) const;
+	/** The resonant low shelf (:709-724; 10.4): M = amp( ( gain / 2 ) / ( 2 order ) ), the sections of filter_2pole_lowpass at cutoff * M, each
+	 *  putting out lp / M^4 + band / M^2 + hp.  gain is sampled at f * ( 1.0f / sample rate ), but cutoff and damping at frame_to_time( f ) =
+	 *  f / sample rate (:648-654) -- not always the same float.  Kept quirks: the cutoff is NOT clamped; a damping above 1 makes odd orders NaN
+	 *  from that frame on; order 0 is a copy.  A null *this gives a null Audio.  The result stays device-resident. */
+	Audio filter_2pole_lowshelf( const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping,
+		const Function<Second, Decibel> & gain, uint16_t order = 1 ) const;
+	/** The band shelf (:726-740): M = amp( -gain / ( 2 order ) ), the cutoff as it is and the damping times M, each section putting out
+	 *  lp + band / M^2 + hp.  The quirks of filter_2pole_lowshelf, and damping * M can pass 1 where the damping does not: odd orders go NaN. */
+	Audio filter_2pole_bandshelf( const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping,
+		const Function<Second, Decibel> & gain, uint16_t order = 1 ) const;
+	/** The high shelf (:742-758): as the low shelf, each section putting out lp + band * M^2 + hp * M^4.  The quirks of filter_2pole_lowshelf. */
+	Audio filter_2pole_highshelf( const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping,
+		const Function<Second, Decibel> & gain, uint16_t order = 1 ) const;
 
 	// the older camelCase spellings BASELINE.json's north_star uses
 	PV convertToPV( Frame window_size = 2048, Frame hop = 128, Frame dft_size = 4096, flan_CANCEL_ARG ) const;

@@ -594,6 +594,55 @@ int flanhip_filter_1pole_dev(const float * d_audio, int64_t num_channels, int64_
  * choice, 16).  Results do not depend on it beyond rounding. */
 void flanhip_filter_debug_run(int frames);
 
+/* ---- Audio::filter_2pole_lowpass / _bandpass / _highpass / _notch (Audio/AudioFilter.cpp:520-624), filter_2pole_lowshelf / _bandshelf /
+ * _highshelf (:631-758) and filter_1pole_lowshelf / _highshelf (:431-512): cascades of the same two TPT sections whose cutoff, damping
+ * and output mix change every frame, every section a scan (flan_amd/csrc/filter.hip) ---------------------------- */
+/* audio, out: float[ch][n].  cutoff, damping and gain are each a curve of n floats or, with a NULL curve, the scalar.  Damping is not
+ * looked at by the 1-pole kinds, gain not by kinds 2 ... 5.  Everything is fp32, one rounding per operation, in the reference's order; each
+ * transcendental (acos, cos, sin, sqrt, pow, hypot, tan) is the fp64 function of the fp32 argument rounded to fp32 once; complex products
+ * and quotients are the textbook forms, ( ac - bd, ad + bc ) and ( ac + bd, bc - ad ) / ( cc + dd ).  T_half = pi / sr, amp( d ) =
+ * pow( 10, d / 20 ), clamp( c ) = std::clamp( c, 1, sr / 2 ) by two comparisons, pole_i = ( cos theta_i, sin theta_i ) with
+ * flanhip_filter_1pole's theta_i, and EVERY section prewarps its own cutoff without a clamp: g = ( tan( T_half w ) / T_half ) T_half.
+ *   LOW, BAND, HIGH   per frame w = clamp( cutoff ), R = damping (NOT clamped), alpha = acos( R ) / N.  For odd N one state-variable
+ *                     section ( w, cos( alpha ) ) FIRST; then per pole above the axis TWO sections, p1 = pole_i w scaler and p2 = pole_i w /
+ *                     scaler, each with w_k = |p| and R_k = -Re( p ) / |p|; scaler = pow( R + sqrt( R R - 1 ), 1 / N ) (real) where R > 1,
+ *                     else exp( -i alpha ).  Order N is N sections; all tap lp (LOW), bp 2 R_k (BAND) or hp (HIGH) (:520-582).
+ *                     R > 1 at a frame makes alpha NaN: every ODD order puts out NaN from that frame on; even orders are fine.
+ *   NOTCH             ( 0 + ( -band ) ) + audio per sample (:614-624); order 0 is therefore SILENCE.
+ *   LOWSHELF, HIGHSHELF   M = amp( ( gain / 2 ) / ( 2 N ) ), M2 = M M, w = cutoff M (NOT clamped), R = damping, the sections of LOW; each puts out
+ *                     ( lp / ( M2 M2 ) + b / M2 ) + hp (LOWSHELF) or ( lp + b M2 ) + ( hp M2 ) M2 (HIGHSHELF), b = bp 2 R_k (:709-758).
+ *   BANDSHELF         M = amp( -gain / ( 2 N ) ), w = cutoff, R = damping M -- which can pass 1: odd orders then go NaN --, output
+ *                     ( lp + b / M2 ) + hp (:726-740).
+ *   1POLE_LOWSHELF, 1POLE_HIGHSHELF   the tilt (:431-488) of gain (LOW) or -gain (HIGH): M = amp( gain / ( 2 N ) ), w = M clamp( cutoff ); for
+ *                     odd N a 1-pole section first, lp M + ( x - lp ) / M; then per pole a 2-pole section with R = Re( pole_i ) / w --
+ *                     NEGATIVE and tiny: from order 2 on the reference is mildly unstable, and that is kept -- and output
+ *                     ( lp / M2 + bp 2 R ) + hp M2.  Then every sample times amp( gain / 2 ), one fp32 product (:490-512).
+ * Order 0 is a copy (NOTCH: silence; the 1-pole shelves: the copy times amp( gain / 2 )).  Deterministic (two calls agree bit for bit); a
+ * channel's output does not depend on the channels filtered with it.  out may be the audio for every kind except NOTCH, which reads the
+ * input after the cascade: flanhip_filter2_dev with d_out == d_audio and NOTCH is FLANHIP_ERR_INVALID_ARG.  Otherwise the refusals are
+ * flanhip_filter_1pole's, before any device call; flanhip_filter_debug_run sets the run length here too. */
+#define FLANHIP_FILTER2_1POLE_LOWSHELF  0   /* AudioFilter.cpp:431-500 */
+#define FLANHIP_FILTER2_1POLE_HIGHSHELF 1   /* :502-512 */
+#define FLANHIP_FILTER2_LOW             2   /* :520-592 */
+#define FLANHIP_FILTER2_BAND            3   /* :594-602 */
+#define FLANHIP_FILTER2_HIGH            4   /* :604-612 */
+#define FLANHIP_FILTER2_NOTCH           5   /* :614-624 */
+#define FLANHIP_FILTER2_LOWSHELF        6   /* :631-724 */
+#define FLANHIP_FILTER2_BANDSHELF       7   /* :726-740 */
+#define FLANHIP_FILTER2_HIGHSHELF       8   /* :742-758 */
+/* bytes of device workspace flanhip_filter2_dev needs (pure host arithmetic; 0 for arguments it refuses): the rows g, R and m of one
+ * section, n floats each (n rounded up to 4), rewritten for every section, then flanhip_filter_1pole's 64 bytes per channel and block:
+ * 12 * roundup( n, 4 ) + 64 * ch * ceil( n / ( 256 * run ) ).  Need not be cleared. */
+size_t flanhip_filter2_workspace_bytes(int64_t num_channels, int64_t num_frames);
+int flanhip_filter2(const float * audio, int64_t num_channels, int64_t num_frames, float sample_rate,
+                    const float * cutoff_curve, float cutoff, const float * damping_curve, float damping,
+                    const float * gain_curve, float gain, int kind, int order,
+                    float * out, volatile int * cancel);
+int flanhip_filter2_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, float sample_rate,
+                        const float * d_cutoff, float cutoff, const float * d_damping, float damping,
+                        const float * d_gain, float gain, int kind, int order,
+                        float * d_out, void * d_workspace, void * stream);
+
 /* ---- Audio::resample (Audio/AudioConversions.cpp:14-30, r8brain CDSPResampler with default parameters) --------- */
 /* AudioConversions.cpp:22: out frames = Frame( float(num_frames) * ( dst_rate / src_rate ) ) */
 int64_t flanhip_resample_out_frames(int64_t num_frames, float src_rate, float dst_rate);
