@@ -155,6 +155,15 @@ _SIGS = {
     "flanhip_filter2_workspace_bytes": (C.c_size_t, [_i64, _i64]),
     "flanhip_filter2": (C.c_int, [_vp, _i64, _i64, _f32] + [_vp, _f32] * 3 + [_i32, _i32, _vp, _vp]),
     "flanhip_filter2_dev": (C.c_int, [_vp, _i64, _i64, _f32] + [_vp, _f32] * 3 + [_i32, _i32, _vp, _vp, _vp]),
+    "flanhip_halfband_poles": (None, [_vp, _vp]),
+    "flanhip_halfband_workspace_bytes": (C.c_size_t, [_i64, _i64]),
+    "flanhip_halfband_debug_run": (None, [_i32]),
+    "flanhip_hilbert": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _vp, _vp]),
+    "flanhip_hilbert_dev": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
+    "flanhip_halfband_modulate": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _f32, _vp, _f32, _vp, _vp, _vp]),
+    "flanhip_halfband_modulate_dev": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _f32, _vp, _f32, _vp, _vp, _vp, _vp]),
+    "flanhip_halfband_multiply": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _i64, _i64, _f32, _vp, _vp]),
+    "flanhip_halfband_multiply_dev": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _i64, _i64, _f32, _vp, _vp, _vp]),
 }
 
 EXPORTS = sorted(_SIGS)
@@ -979,3 +988,88 @@ def filter2_dev(d_audio, ch, n, sample_rate, cutoff, damping, gain, kind, order,
     """flanhip_filter2_dev: cutoff, damping and gain are floats or device arrays of n floats; d_out may be d_audio (not for FILTER2_NOTCH)"""
     args, keep = _filter2_params((cutoff, damping, gain), n, _dp)
     check(lib.flanhip_filter2_dev(_dp(d_audio), ch, n, sample_rate, *args, kind, order, _dp(d_out), _dp(d_ws), _vp(stream or 0)))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# hilbert_phase_diff_network, Audio::halfband_modulate, the modulation of Audio::shift_frequency and Audio::halfband_multiply.  The
+# modulator's re and im are each a float (the scalar) or an array of n floats (a curve); a phase curve stands for both
+# ---------------------------------------------------------------------------------------------------------------
+
+def halfband_poles():
+    """( first, second ): the poles of the two cascades in rad/s, float32 [10] each"""
+    first, second = np.empty(10, np.float32), np.empty(10, np.float32)
+    lib.flanhip_halfband_poles(_ptr(first), _ptr(second))
+    return first, second
+
+
+def halfband_workspace_bytes(ch, n):
+    return int(lib.flanhip_halfband_workspace_bytes(ch, n))
+
+
+def hilbert(audio, sample_rate):
+    """hilbert_phase_diff_network.  audio float32 [ch][n] -> ( first, second ), float32 [ch][n] each"""
+    audio = np.ascontiguousarray(audio, np.float32)
+    ch, n = audio.shape
+    first, second = np.empty_like(audio), np.empty_like(audio)
+    check(lib.flanhip_hilbert(_ptr(audio), ch, n, sample_rate, _ptr(first), _ptr(second), None))
+    return first, second
+
+
+def hilbert_dev(d_audio, ch, n, sample_rate, d_first, d_second, d_ws, stream=None):
+    """flanhip_hilbert_dev: d_first or d_second may be d_audio"""
+    check(lib.flanhip_hilbert_dev(_dp(d_audio), ch, n, sample_rate, _dp(d_first), _dp(d_second), _dp(d_ws), _vp(stream or 0)))
+
+
+def _halfband_modulator(re, im, phase, n, pointer):
+    """the five modulator arguments in the header's order; curves are kept alive by the second return value"""
+    args, keep = _filter2_params((re, im), n, pointer)
+    if phase is None:
+        return args + [None], keep
+    if pointer is _ptr:
+        phase = np.ascontiguousarray(phase, np.float32)
+        assert phase.shape == (n,), phase.shape
+    return args + [pointer(phase)], keep + [phase]
+
+
+def halfband_modulate(audio, sample_rate, re=1.0, im=0.0, phase=None):
+    """Audio::halfband_modulate: first * re - second * im.  audio float32 [ch][n] -> float32 [ch][n]"""
+    audio = np.ascontiguousarray(audio, np.float32)
+    ch, n = audio.shape
+    args, keep = _halfband_modulator(re, im, phase, n, _ptr)
+    out = np.empty_like(audio)
+    check(lib.flanhip_halfband_modulate(_ptr(audio), ch, n, sample_rate, *args, _ptr(out), None))
+    return out
+
+
+def halfband_modulate_dev(d_audio, ch, n, sample_rate, re, im, phase, d_out, d_ws, stream=None):
+    """flanhip_halfband_modulate_dev: re and im are floats or device arrays of n floats, phase None or a device array; d_out may be d_audio"""
+    args, keep = _halfband_modulator(re, im, phase, n, _dp)
+    check(lib.flanhip_halfband_modulate_dev(_dp(d_audio), ch, n, sample_rate, *args, _dp(d_out), _dp(d_ws), _vp(stream or 0)))
+
+
+def halfband_multiply(a, sample_rate_a, b, sample_rate_b):
+    """the network and the product of Audio::halfband_multiply.  a float32 [ch_a][n_a], b float32 [ch_b][n_b] -> float32 [min ch][min n]"""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    out = np.empty((min(a.shape[0], b.shape[0]), min(a.shape[1], b.shape[1])), np.float32)
+    check(lib.flanhip_halfband_multiply(_ptr(a), a.shape[0], a.shape[1], sample_rate_a, _ptr(b), b.shape[0], b.shape[1], sample_rate_b, _ptr(out), None))
+    return out
+
+
+def halfband_multiply_dev(d_a, ch_a, n_a, sample_rate_a, d_b, ch_b, n_b, sample_rate_b, d_out, d_ws, stream=None):
+    """flanhip_halfband_multiply_dev: d_out float32 [min ch][min n]; the workspace is sized for the output's shape"""
+    check(lib.flanhip_halfband_multiply_dev(_dp(d_a), ch_a, n_a, sample_rate_a, _dp(d_b), ch_b, n_b, sample_rate_b, _dp(d_out), _dp(d_ws), _vp(stream or 0)))
+
+
+class halfband_run_forced:
+    """with fa.halfband_run_forced(4): ...   -- the frames one lane replays in this thread's halfband calls, back to the library's choice afterwards"""
+
+    def __init__(self, frames):
+        self.frames = frames
+
+    def __enter__(self):
+        lib.flanhip_halfband_debug_run(self.frames)
+        return self
+
+    def __exit__(self, *exc):
+        lib.flanhip_halfband_debug_run(0)
+        return False

@@ -1,7 +1,7 @@
 // Audio.cpp -- construction and conversions of flan::Audio over the C ABI
 // (reference: src/flan/Audio/AudioConstructors.cpp, Conversions/AudioPV.cpp:12-84, Audio/AudioConversions.cpp:14-56,
 // Audio/AudioCombination.cpp:299-352, Audio/AudioTemporal.cpp:236-299, Audio/AudioVolume.cpp:5-67, 190-278,
-// Audio/AudioFilter.cpp:280-758).
+// Audio/AudioFilter.cpp:280-758, 1045-1263).
 #include "flan/Audio.h"
 
 #include <algorithm>
@@ -78,6 +78,34 @@ Audio filter_cascade( const Audio & me, const DeviceCurve & cutoff, int kind, ui
 		kind, int( order ), static_cast<float*>( block->ptr ), ws->ptr, nullptr );
 	if( !detail::report( rc, who ) ) return Audio::create_null();
 	if( !detail::report( flanhip_stream_synchronize( nullptr ), who ) ) return Audio::create_null();                 // the workspace and the curve go back idle
+	return AudioBuffer::adopt_device( me.get_format(), std::move( block ) );
+	}
+
+// host values as a curve on the device
+DeviceCurve upload_values( const detail::StagingVector<float> & values )
+	{
+	DeviceCurve c;
+	c.block = detail::DeviceBlock::allocate( sizeof( float ) * values.size() );
+	c.ok = c.block && detail::upload_from_host( c.block->ptr, values.data(), sizeof( float ) * values.size() );
+	if( c.block && !c.ok ) std::cerr << "flan: upload of a curve failed: " << flanhip_last_error() << std::endl;
+	return c;
+	}
+
+// flanhip_halfband_modulate_dev over `me` with the modulator already on the device (re and im, or the phase that stands for both)
+Audio halfband_modulated( const Audio & me, const DeviceCurve & re, const DeviceCurve & im, const DeviceCurve * phase, const char * who )
+	{
+	if( me.is_null() ) return Audio::create_null();
+	const size_t ws_bytes = flanhip_halfband_workspace_bytes( me.get_num_channels(), me.get_num_frames() );
+	if( ws_bytes == 0 ) return Audio::create_null();
+	const float * d_x = me.device_data();
+	if( !d_x ) return Audio::create_null();
+	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( me.get_num_channels() ) * size_t( me.get_num_frames() ) );
+	auto ws = detail::DeviceBlock::allocate( ws_bytes );
+	if( !re.ok || !im.ok || ( phase && ( !phase->ok || !phase->ptr() ) ) || !block || !ws ) return Audio::create_null();
+	const int rc = flanhip_halfband_modulate_dev( d_x, me.get_num_channels(), me.get_num_frames(), me.get_sample_rate(), re.ptr(), re.scalar,
+		im.ptr(), im.scalar, phase ? phase->ptr() : nullptr, static_cast<float*>( block->ptr ), ws->ptr, nullptr );
+	if( !detail::report( rc, who ) ) return Audio::create_null();
+	if( !detail::report( flanhip_stream_synchronize( nullptr ), who ) ) return Audio::create_null();                 // the workspace and the curves go back idle
 	return AudioBuffer::adopt_device( me.get_format(), std::move( block ) );
 	}
 
@@ -473,6 +501,100 @@ Audio Audio::filter_1pole_lowshelf( const Function<Second, Frequency> & cutoff, 
 Audio Audio::filter_1pole_highshelf( const Function<Second, Frequency> & cutoff, const Function<Second, Decibel> & gain, uint16_t order ) const
 	{
 	return filter_1pole_shelf( *this, cutoff, gain, FLANHIP_FILTER2_1POLE_HIGHSHELF, order, "filter_1pole_highshelf" );
+	}
+
+// :1168: the modulator through sample_function_over_domain, at f * ( 1.0f / sr ); the network and the product are the device's
+Audio Audio::halfband_modulate( const Function<Second, std::complex<float>> & modulator ) const
+	{
+	if( is_null() || !device_data() ) return Audio::create_null();     // :1166; without a device nothing is sampled
+	DeviceCurve re, im;
+	if( modulator.is_constant() ) { re.scalar = modulator.get_constant().real(); im.scalar = modulator.get_constant().imag(); }
+	else
+		{
+		const Frame n = get_num_frames();
+		const float step = 1.0f / get_sample_rate();
+		detail::StagingVector<float> res( static_cast<size_t>( n ) ), ims( static_cast<size_t>( n ) );
+		detail::for_each_index( 0, n, modulator.get_execution_policy(), [&]( int x )
+			{
+			const std::complex<float> m = modulator( Second( x * step ) );
+			res[size_t( x )] = m.real(); ims[size_t( x )] = m.imag();
+			} );
+		re = upload_values( res ); im = upload_values( ims );
+		}
+	return halfband_modulated( *this, re, im, nullptr, "halfband_modulate" );
+	}
+
+Audio Audio::shift_frequency( const Function<Second, Frequency> & shift, const Frequency low_cutoff ) const
+	{
+	if( is_null() || !device_data() ) return Audio::create_null();     // :1193; without a device nothing is sampled
+	const Frame n = get_num_frames();
+	const float sr = get_sample_rate(), step = 1.0f / sr;
+	const Frequency high_cutoff = sr / 2 - 1000;                       // :1195
+	// :1203, :1211, :1223: the frame a time sampled at f * ( 1.0f / sr ) is read back as, in fp32; n reads the last frame
+	auto frame_of = [&]( Frame f ){ return std::clamp( Frame( std::round( time_to_frame( Second( f * step ) ) ) ), Frame( 0 ), n - 1 ); };
+	// :1218-1219: shift * pi2 / sr summed one frame after the other from 0.0f, exclusive
+	detail::StagingVector<float> phase( static_cast<size_t>( n ) );
+	DeviceCurve lp, hp;
+	if( shift.is_constant() )
+		{
+		const Frequency s = shift.get_constant();
+		lp.scalar = s > 0 ? high_cutoff - s : high_cutoff;             // :1204-1207
+		hp.scalar = s < 0 ? low_cutoff - s : low_cutoff;               // :1212-1215
+		const float inc = s * pi2 / sr;
+		float sum = 0.0f;
+		for( Frame f = 0; f < n; ++f ) { phase[size_t( f )] = sum; sum = sum + inc; }
+		}
+	else
+		{
+		detail::StagingVector<float> sampled( static_cast<size_t>( n ) ), lps( static_cast<size_t>( n ) ), hps( static_cast<size_t>( n ) );
+		detail::for_each_index( 0, n, shift.get_execution_policy(), [&]( int x ){ sampled[size_t( x )] = shift( Second( x * step ) ); } );
+		for( Frame f = 0; f < n; ++f )
+			{
+			const Frequency s = sampled[size_t( frame_of( f ) )];
+			lps[size_t( f )] = s > 0 ? high_cutoff - s : high_cutoff;
+			hps[size_t( f )] = s < 0 ? low_cutoff - s : low_cutoff;
+			}
+		float sum = 0.0f;
+		for( Frame f = 0; f < n; ++f ) { phase[size_t( f )] = sum; sum = sum + sampled[size_t( f )] * pi2 / sr; }
+		lp = upload_values( lps ); hp = upload_values( hps );
+		}
+	detail::StagingVector<float> read( static_cast<size_t>( n ) );     // :1223-1225: the modulator reads the phase through the same round trip
+	for( Frame f = 0; f < n; ++f ) read[size_t( f )] = phase[size_t( frame_of( f ) )];
+	const DeviceCurve d_phase = upload_values( read );
+	const Audio antialiased = filter_cascade( filter_cascade( *this, lp, FLANHIP_FILTER_BUTTERWORTH_LOW, 8, "shift_frequency" ), hp,
+		FLANHIP_FILTER_BUTTERWORTH_HIGH, 8, "shift_frequency" );
+	if( antialiased.is_null() ) return Audio::create_null();
+	return halfband_modulated( antialiased, DeviceCurve(), DeviceCurve(), &d_phase, "shift_frequency" );
+	}
+
+Audio Audio::halfband_multiply( const Audio & modulator ) const
+	{
+	if( is_null() || modulator.is_null() || !device_data() ) return Audio::create_null();     // :1233; the reference dereferences a null modulator
+	auto bandpass_antialias = []( const Audio & a )                    // :1235-1240
+		{
+		DeviceCurve low, high;
+		low.scalar = 30;
+		high.scalar = a.get_sample_rate() / 2 - 2000;
+		return filter_cascade( filter_cascade( a, high, FLANHIP_FILTER_BUTTERWORTH_LOW, 8, "halfband_multiply" ), low,
+			FLANHIP_FILTER_BUTTERWORTH_HIGH, 8, "halfband_multiply" );
+		};
+	const Audio a = bandpass_antialias( *this ), b = bandpass_antialias( modulator );
+	if( a.is_null() || b.is_null() ) return Audio::create_null();
+	AudioBuffer::Format f = get_format();                              // :1245-1247
+	f.num_channels = std::min( get_num_channels(), modulator.get_num_channels() );
+	f.num_frames = std::min( get_num_frames(), modulator.get_num_frames() );
+	const size_t ws_bytes = flanhip_halfband_workspace_bytes( f.num_channels, f.num_frames );
+	if( ws_bytes == 0 ) return Audio::create_null();
+	const float * d_a = a.device_data(), * d_b = b.device_data();
+	if( !d_a || !d_b ) return Audio::create_null();
+	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( f.num_channels ) * size_t( f.num_frames ) );
+	auto ws = detail::DeviceBlock::allocate( ws_bytes );
+	if( !block || !ws ) return Audio::create_null();
+	const int rc = flanhip_halfband_multiply_dev( d_a, a.get_num_channels(), a.get_num_frames(), a.get_sample_rate(), d_b, b.get_num_channels(),
+		b.get_num_frames(), b.get_sample_rate(), static_cast<float*>( block->ptr ), ws->ptr, nullptr );
+	if( !detail::report( rc, "halfband_multiply" ) ) return Audio::create_null();
+	if( !detail::report( flanhip_stream_synchronize( nullptr ), "halfband_multiply" ) ) return Audio::create_null();     // the workspace goes back idle
+	return AudioBuffer::adopt_device( f, std::move( block ) );
 	}
 
 } // namespace flan

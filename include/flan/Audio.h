@@ -1,6 +1,7 @@
 // flan/Audio.h -- the Audio side of the phase-vocoder path (mirrors the reference's src/flan/Audio/Audio.h:25-176 for
 // construction and conversions; every method is const and returns a fresh object, invalid input gives a null object).
 #pragma once
+#include <complex>
 #include <cstdint>
 #include <vector>
 
@@ -136,6 +137,31 @@ public:
 	/** The high shelf (:742-758): as the low shelf, each section putting out lp + band * M^2 + hp * M^4.  The quirks of filter_2pole_lowshelf. */
 	Audio filter_2pole_highshelf( const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping,
 		const Function<Second, Decibel> & gain, uint16_t order = 1 ) const;
+
+	// ---- single sideband ----
+	/** The signal's positive spectrum alone -- an approximate Hilbert transform by a phase-difference network -- times a complex modulator, real
+	 *  part (Audio/AudioFilter.cpp:1162-1186): spectral convolution with one sideband, so a complex sinusoid shifts every frequency.  The
+	 *  network (:1045-1160) is two cascades of ten 1-pole all-pass sections whose outputs are 90 degrees apart from 50 Hz to 15 kHz; both
+	 *  cascades and the product run in one pass on the device (flanhip_halfband_modulate_dev).  Per frame
+	 *  out = first * re - second * im, three fp32 roundings.  Kept quirks: the poles come from phase_diff_network_pole_design( 20, 5, 22000 )
+	 *  whatever the sample rate and are used as they are, no prewarp and no clamp; the FIRST cascade has the odd-indexed poles of the design;
+	 *  nothing is anti-aliased.  modulator is sampled once per frame at f * ( 1.0f / sample rate ); a constant samples nothing.  A null *this
+	 *  gives a null Audio.  The result stays device-resident until read. */
+	Audio halfband_modulate( const Function<Second, std::complex<float>> & modulator ) const;
+	/** The Bode frequency shifter (:1188-1227): every frequency moved by shift( t ) Hz, up or down.  First filter_1pole_lowpass( 8 ) at sample
+	 *  rate / 2 - 1000 less a positive shift and filter_1pole_highpass( 8 ) at low_cutoff plus a negative one, so that nothing is moved past
+	 *  Nyquist or below 0; then halfband_modulate with exp( i phase ).  shift is sampled once per frame (a constant samples nothing).  Kept
+	 *  quirks: phase is the SEQUENTIAL fp32 running sum of shift * pi2 / sample rate from 0.0f and loses precision over long signals as the
+	 *  reference's does; the filters' cutoffs and the modulator read the sampled shift through frame -> time -> frame in fp32, which is the
+	 *  identity below four million frames and off by one for some frames above; an index that lands on the frame count reads the last frame
+	 *  (the reference reads out of bounds there).  A null *this gives a null Audio.  The result stays device-resident until read. */
+	Audio shift_frequency( const Function<Second, Frequency> & shift, Frequency low_cutoff = 30 ) const;    // Audio.h:855
+	/** halfband_modulate with another Audio as the modulator (:1229-1263): each operand through filter_1pole_lowpass( its sample rate / 2 -
+	 *  2000, 8 ).filter_1pole_highpass( 30, 8 ) and the network at ITS OWN sample rate -- the modulator is not resampled --, then
+	 *  out = a_first * b_first - a_second * b_second over the channels and frames both have (flanhip_halfband_multiply_dev: four cascades
+	 *  and the product in one pass).  The result has this Audio's sample rate.  A null *this or a null modulator (which the reference
+	 *  dereferences) gives a null Audio.  The result stays device-resident until read. */
+	Audio halfband_multiply( const Audio & modulator ) const;
 
 	// the older camelCase spellings BASELINE.json's north_star uses
 	PV convertToPV( Frame window_size = 2048, Frame hop = 128, Frame dft_size = 4096, flan_CANCEL_ARG ) const;

@@ -643,6 +643,55 @@ int flanhip_filter2_dev(const float * d_audio, int64_t num_channels, int64_t num
                         const float * d_gain, float gain, int kind, int order,
                         float * d_out, void * d_workspace, void * stream);
 
+/* ---- hilbert_phase_diff_network (Audio/AudioFilter.cpp:1045-1160) and the single-sideband methods over it: Audio::halfband_modulate
+ * (:1162-1186), the modulation of Audio::shift_frequency (:1188-1227) and Audio::halfband_multiply (:1229-1263).  The network is two
+ * cascades of ten 1-pole all-pass sections with constant poles; a cascade is one linear system with a constant 10 x 10 lower-triangular
+ * matrix, scanned over the frames in one pass (flan_amd/csrc/halfband.hip) ------------------------------------------ */
+/* :1109-1150, phase_diff_network_pole_design( 20, 5, 22000 ): the poles in rad/s, computed in fp64 and each rounded to fp32.  `first` has
+ * the poles of the FIRST output's cascade, the odd-indexed ones of the design (the reference returns them "backwards"), `second` the
+ * even-indexed ones.  They do not depend on the sample rate.  Host only. */
+void flanhip_halfband_poles(float first[10], float second[10]);
+/* bytes of device workspace the three _dev calls below need (pure host arithmetic; 0 for arguments it refuses): 15 packed triangular
+ * matrices of 55 doubles for each of four cascades, then per channel and block of 256 runs the four cascades' totals and carried states,
+ * ten doubles each: 26400 + 640 * ch * ceil( n / ( 256 * run ) ); ch and n are the OUTPUT's.  Sized for the calling thread's
+ * flanhip_halfband_debug_run setting.  Need not be cleared. */
+size_t flanhip_halfband_workspace_bytes(int64_t num_channels, int64_t num_frames);
+/* test hook: the frames one lane replays in the calling thread's halfband calls, 1 ... 64 (larger values are taken as 64; 0: the library's
+ * choice, 16).  Results do not depend on it beyond rounding. */
+void flanhip_halfband_debug_run(int frames);
+/* :1045-1072, :1152-1160: audio, first, second: float[ch][n].  Per channel and frame the sample goes through a cascade's sections in order,
+ * each process_sample_and_mix( x, p_i, { 1, -1 }, false ) (:61-80): NO prewarp and NO clamp, the pole in rad/s is w.  In fp32, one rounding
+ * per operation: T_half = pi / sr (pi = acosf( -1 )), g = p_i T_half, G = g / ( 1 + g ), v = G ( x - s ), lp = v + s, s = lp + v,
+ * y = lp - ( x - lp ), s from 0.  Every lane replays a run of frames with these operations from a state carried in by an fp64 scan (rounded
+ * to fp32 once).  first or second may be the audio.  Deterministic (two calls agree bit for bit); a channel's output does not depend on the
+ * channels beside it.  Null audio / outputs (and, for _dev, workspace), non-positive sizes and sample_rate <= 0 are
+ * FLANHIP_ERR_INVALID_ARG, before any device call.  `cancel` is polled before the upload and before the launch. */
+int flanhip_hilbert(const float * audio, int64_t num_channels, int64_t num_frames, float sample_rate,
+                    float * first, float * second, volatile int * cancel);
+int flanhip_hilbert_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, float sample_rate,
+                        float * d_first, float * d_second, void * d_workspace, void * stream);
+/* :1162-1186: out[c][f] = first[c][f] * re[f] - second[c][f] * im[f], two fp32 products and one fp32 difference, no fused multiply-add;
+ * the network's outputs never go to memory.  re and im are each a curve of n floats or, with a NULL curve, the scalar.  A non-NULL phase
+ * curve (n floats, radians) stands for both: re = cos( phase ), im = sin( phase ), the fp64 functions of the fp32 phase rounded to fp32 once
+ * (:1225, std::exp( complex( 0, phase ) )).  out may be the audio.  The refusals of flanhip_hilbert. */
+int flanhip_halfband_modulate(const float * audio, int64_t num_channels, int64_t num_frames, float sample_rate,
+                              const float * re_curve, float re, const float * im_curve, float im, const float * phase_curve,
+                              float * out, volatile int * cancel);
+int flanhip_halfband_modulate_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, float sample_rate,
+                                  const float * d_re, float re, const float * d_im, float im, const float * d_phase,
+                                  float * d_out, void * d_workspace, void * stream);
+/* :1242-1260: a: float[ch_a][n_a], b: float[ch_b][n_b], out: float[min ch][min n].  Each operand goes through the network with ITS OWN
+ * sample rate; out[c][f] = a_first * b_first - a_second * b_second, as above, over the first min ch channels and min n frames of both (the
+ * network is causal: later frames do not reach earlier ones).  Four cascades in the same four launches; none of their outputs goes to
+ * memory.  The band-pass before the network (:1235-1240) is not part of this call: Audio::halfband_multiply runs it with
+ * flanhip_filter_1pole_dev.  The refusals of flanhip_hilbert, for both operands. */
+int flanhip_halfband_multiply(const float * a, int64_t channels_a, int64_t frames_a, float sample_rate_a,
+                              const float * b, int64_t channels_b, int64_t frames_b, float sample_rate_b,
+                              float * out, volatile int * cancel);
+int flanhip_halfband_multiply_dev(const float * d_a, int64_t channels_a, int64_t frames_a, float sample_rate_a,
+                                  const float * d_b, int64_t channels_b, int64_t frames_b, float sample_rate_b,
+                                  float * d_out, void * d_workspace, void * stream);
+
 /* ---- Audio::resample (Audio/AudioConversions.cpp:14-30, r8brain CDSPResampler with default parameters) --------- */
 /* AudioConversions.cpp:22: out frames = Frame( float(num_frames) * ( dst_rate / src_rate ) ) */
 int64_t flanhip_resample_out_frames(int64_t num_frames, float src_rate, float dst_rate);
