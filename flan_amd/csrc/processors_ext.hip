@@ -49,19 +49,12 @@ __global__ __launch_bounds__( 256 ) void k_combine_amplitudes( const MFd * in, i
 // ---------------------------------------------------------------------------------------------------------------------
 // resonate
 // ---------------------------------------------------------------------------------------------------------------------
-// PV.cpp:617,:631 for a sampled decay grid: decay_t = pow( clamp( decay, 0, 1 ), seconds per frame ), correctly rounded
-// (evaluated in double, rounded once).
-__global__ __launch_bounds__( 256 ) void k_decay_pow( const float * decay, int64_t count, float seconds_per_frame, float * decay_t )
-	{
-	const int64_t idx = int64_t( blockIdx.x ) * blockDim.x + threadIdx.x;
-	if( idx >= count ) return;
-	decay_t[idx] = float( pow( double( clamp01( decay[idx] ) ), double( seconds_per_frame ) ) );
-	}
-
 constexpr int kResTB = 16, kResTF = 128;                                            // k_resonate tile: 16 bins x 128 frames (3 x 8.5 KB of LDS)
-// PV.cpp:619-638.  grid = ( ceil(bins/16), channels ).  decay_t: float[Fo][bins] or nullptr + constant.  column_scan over
-// the OUTPUT's frames with ( m, f, decay_t ) in and ( m, f ) out.
-__global__ __launch_bounds__( 256 ) void k_resonate( const MFd * in, int64_t F, int bins, int64_t Fo, const float * decay_t, float decay_t_const, MFd * out )
+// PV.cpp:619-638.  grid = ( ceil(bins/16), channels ).  decay: the sampled grid float[Fo][bins], or nullptr + the constant's decay_t.
+// column_scan over the OUTPUT's frames with ( m, f, decay_t ) in and ( m, f ) out.  For a sampled grid decay_t = pow( clamp( decay, 0, 1 ),
+// seconds per frame ) (:617, :631), correctly rounded (evaluated in double, rounded once), is taken where the tile is loaded, by all 256
+// threads: no second grid between two launches.
+__global__ __launch_bounds__( 256 ) void k_resonate( const MFd * in, int64_t F, int bins, int64_t Fo, const float * decay, float seconds_per_frame, float decay_t_const, MFd * out )
 	{
 	__shared__ __attribute__(( aligned( 16 ) )) float lds[column_scan_lds_floats( kResTF, kResTB, 3 )];
 	const int strip = xcd_contiguous_strip( blockIdx.x, ( bins + kResTB - 1 ) / kResTB );
@@ -80,7 +73,7 @@ __global__ __launch_bounds__( 256 ) void k_resonate( const MFd * in, int64_t F, 
 			MFd mf = { __builtin_nanf( "" ), 0.0f };                                  // no input frame: `m > decayed` is false (:633)
 			if( valid && f < F ) mf = ip[f * bins];
 			v[0] = mf.m; v[1] = mf.f;
-			v[2] = ( valid && decay_t ) ? decay_t[f * bins + bin] : decay_t_const;
+			v[2] = ( valid && decay ) ? float( pow( double( clamp01( decay[f * bins + bin] ) ), double( seconds_per_frame ) ) ) : decay_t_const;
 			if( f == 0 ) { v[0] = __builtin_nanf( "" ); v[2] = 1.0f; }
 			},
 		[&]( int64_t f, float ( &v )[3] )
@@ -437,24 +430,15 @@ int flanhip_resonate_dev( const flanhip_MF * d_pv, int64_t ch, int64_t F, int bi
 	FLANHIP_REQUIRE( hop >= 1 && Fo >= F, FLANHIP_ERR_INVALID_ARG, "bad hop / output length" );
 	hipStream_t s = (hipStream_t) stream;
 	const float seconds_per_frame = 1.0f / ( sr / float( hop ) );                     // frame_to_time( 1 ), PV.cpp:626
-	float * d_decay_t = nullptr;
 	float decay_t_const = 0.0f;
-	if( d_decay )
-		{
-		const int64_t count = Fo * bins;
-		FLANHIP_CHECK( hipMallocAsync( reinterpret_cast<void**>( &d_decay_t ), sizeof( float ) * size_t( count ), s ) );
-		hipLaunchKernelGGL( k_decay_pow, dim3( blocks_for( count, 256 ) ), dim3( 256 ), 0, s, d_decay, count, seconds_per_frame, d_decay_t );
-		FLANHIP_CHECK( hipGetLastError() );
-		}
-	else
+	if( !d_decay )
 		{
 		const float d = decay_const < 0.0f ? 0.0f : ( 1.0f < decay_const ? 1.0f : decay_const );   // :617
 		decay_t_const = std::pow( d, seconds_per_frame );                             // :631, the platform's powf like the reference
 		}
 	hipLaunchKernelGGL( k_resonate, dim3( xcd_grid( ( bins + kResTB - 1 ) / kResTB ), (unsigned) ch ), dim3( 256 ), 0, s, (const MFd*) d_pv, F, bins, Fo,
-		(const float*) d_decay_t, decay_t_const, (MFd*) d_out );
+		d_decay, seconds_per_frame, decay_t_const, (MFd*) d_out );
 	FLANHIP_CHECK( hipGetLastError() );
-	if( d_decay_t ) FLANHIP_CHECK( hipFreeAsync( d_decay_t, s ) );
 	return FLANHIP_OK;
 	}
 

@@ -1,0 +1,100 @@
+"""tests/pv_methods_reference.py against tests/cpp/pv_methods_test.cpp, without a device: what the driver's callables give through the host
+calls flan_amd/host/PV.cpp makes (PV::sample_function_over_domain, Function::sample, the per-frame loops of stretch_spline and the
+harmonic scaler) equals the table's NumPy restatement bit for bit -- so a case that fails on the device is the layer's doing, not a
+callable that the two sides read differently -- and the table is whole: unique names, every method of include/flan/PV.h held."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import pv_methods_reference as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "tests", "cpp", "pv_methods_test")
+
+
+def build_driver():
+    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "flan_amd", "host")], check=True)
+    src = os.path.join(ROOT, "tests", "cpp", "pv_methods_test.cpp")
+    deps = [src, os.path.join(ROOT, "flan_amd", "libflan_host.so")]
+    if not os.path.exists(BIN) or any(os.path.getmtime(d) > os.path.getmtime(BIN) for d in deps):
+        subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), src, "-o", BIN,
+                        "-L" + os.path.join(ROOT, "flan_amd"), "-lflan_host", "-lflanhip",
+                        "-Wl,-rpath," + os.path.join(ROOT, "flan_amd"), "-lpthread"], check=True)
+
+
+def run_driver(*args, timeout=300):
+    env = dict(os.environ, LD_LIBRARY_PATH=os.path.join(ROOT, "flan_amd") + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
+    return subprocess.run([BIN] + list(args), capture_output=True, text=True, env=env, timeout=timeout)
+
+
+def sample_only(out_dir):
+    """{ name: array } of everything --sample-only dumps"""
+    r = run_driver("--sample-only", str(out_dir))
+    assert r.returncode == 0 and "PASSED" in r.stdout, r.stdout + r.stderr
+    return {name[:-4]: R.read_dump(os.path.join(str(out_dir), name)) for name in sorted(os.listdir(str(out_dir))) if name.endswith(".bin")}
+
+
+@pytest.fixture(scope="module")
+def dumps(tmp_path_factory):
+    build_driver()
+    return sample_only(tmp_path_factory.mktemp("pv_methods_samples"))
+
+
+@pytest.fixture(scope="module")
+def table():
+    return R.sample_table()
+
+
+def test_driver_dumps_what_the_table_lists(dumps, table):
+    assert sorted(dumps) == sorted(table)
+
+
+@pytest.mark.parametrize("name", sorted(R.sample_table()))
+def test_callable_sampled_alike(dumps, table, name):
+    got, want = dumps[name], np.ascontiguousarray(table[name]).reshape(-1)
+    assert got.dtype == want.dtype and got.shape == want.shape, (got.dtype, got.shape, want.dtype, want.shape)
+    if name.startswith("dist.default."):
+        # 0.5f * ( 1.0f + cos( pi * t ) ) in double, rounded to float on both sides: libm's cos against NumPy's, at most 1 float32 ulp
+        ulps = np.abs(got.view(np.int32).astype(np.int64) - want.view(np.int32).astype(np.int64))
+        assert ulps.max() <= 1, ulps.max()
+    else:
+        assert np.array_equal(got.view(np.int32), want.view(np.int32)), int((got.view(np.int32) != want.view(np.int32)).sum())
+
+
+def test_inputs_are_what_the_table_promises():
+    ins = R.inputs()
+    for name, fmt in R.FORMATS.items():
+        assert ins[name].shape == (fmt.channels, fmt.frames, fmt.bins, 2) and ins[name].dtype == np.float32
+    big = R.FORMATS["BIG"]
+    assert big.frames * big.bins * 4 >= 4 << 20                              # function_grid_to_device: 4 slabs
+    assert (big.channels * big.frames * big.bins * 8) >> 22 == 2             # map_rows_to_device: 2 slabs
+    for name in ("A", "X"):                                                  # the callables reach what their cases are for
+        fmt = R.FORMATS[name]
+        amount, decay, n = R.grid(fmt, "amt"), R.grid(fmt, "dc", R.resonate_frames(fmt, 0.0301)), R.per_frame_bins(fmt, "nl")
+        assert amount.min() < 0 and amount.max() > 1 and decay.min() < 0 and decay.max() > 1
+        assert n.min() < 0 and n.max() > fmt.frames and n.max() > fmt.bins
+        back = R.grid(fmt, "mt_back")
+        assert (np.diff(back, axis=0) < 0).any() and (np.diff(back, axis=0) > 0).any()
+        last = R.grid(fmt, "mt_lastmax")
+        assert last.argmax() == last.size - 1
+        steps = R.spline_values(fmt, "sp")
+        assert steps.min() < 0 and ((steps > 0) & (steps < 1)).any() and steps.max() == 40 and (steps != np.trunc(steps)).any()
+
+
+def test_case_names_are_unique():
+    names = [c.name for c in R.CASES]
+    assert len(names) == len(set(names))
+
+
+def test_every_method_of_the_header_has_a_case():
+    with open(os.path.join(ROOT, "include", "flan", "PV.h")) as fh:
+        text = fh.read()
+    text = text[text.index("PV modify("):]
+    declared = re.findall(r"^\s*(?:static\s+)?(?:PV|std::vector<PV>)\s+(\w+)\(", text, re.M)
+    assert declared[0] == "modify" and declared[-1] == "join"
+    assert sorted(set(declared)) == sorted(R.METHODS)
+    held = {c.method for c in R.CASES}
+    assert not [m for m in R.METHODS if m not in held]
