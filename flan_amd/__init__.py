@@ -155,6 +155,10 @@ _SIGS = {
     "flanhip_filter2_workspace_bytes": (C.c_size_t, [_i64, _i64]),
     "flanhip_filter2": (C.c_int, [_vp, _i64, _i64, _f32] + [_vp, _f32] * 3 + [_i32, _i32, _vp, _vp]),
     "flanhip_filter2_dev": (C.c_int, [_vp, _i64, _i64, _f32] + [_vp, _f32] * 3 + [_i32, _i32, _vp, _vp, _vp]),
+    "flanhip_filter_comb_workspace_bytes": (C.c_size_t, [_i64, _i64]),
+    "flanhip_filter_comb_debug_local": (None, [_i32]),
+    "flanhip_filter_comb": (C.c_int, [_vp, _i64, _i64, _f32] + [_vp, _f32] * 3 + [_i32, _vp, _vp]),
+    "flanhip_filter_comb_dev": (C.c_int, [_vp, _i64, _i64, _f32] + [_vp, _f32] * 3 + [_i32, _vp, _vp, _vp]),
     "flanhip_halfband_poles": (None, [_vp, _vp]),
     "flanhip_halfband_workspace_bytes": (C.c_size_t, [_i64, _i64]),
     "flanhip_halfband_debug_run": (None, [_i32]),
@@ -988,6 +992,47 @@ def filter2_dev(d_audio, ch, n, sample_rate, cutoff, damping, gain, kind, order,
     """flanhip_filter2_dev: cutoff, damping and gain are floats or device arrays of n floats; d_out may be d_audio (not for FILTER2_NOTCH)"""
     args, keep = _filter2_params((cutoff, damping, gain), n, _dp)
     check(lib.flanhip_filter2_dev(_dp(d_audio), ch, n, sample_rate, *args, kind, order, _dp(d_out), _dp(d_ws), _vp(stream or 0)))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Audio::filter_comb.  Cutoff, feedback and wet_dry are each a float (the scalar) or an array of n floats (a curve)
+# ---------------------------------------------------------------------------------------------------------------
+
+def filter_comb_workspace_bytes(ch, n):
+    return int(lib.flanhip_filter_comb_workspace_bytes(ch, n))
+
+
+def filter_comb(audio, sample_rate, cutoff, feedback=0.0, wet_dry=0.5, invert=False, cancel=None):
+    """Audio::filter_comb.  audio float32 [ch][n] -> float32 [ch][n].  cancel: None or a ctypes.c_int the call polls"""
+    audio = np.ascontiguousarray(audio, np.float32)
+    ch, n = audio.shape
+    args, keep = _filter2_params((cutoff, feedback, wet_dry), n, _ptr)
+    out = np.empty_like(audio)
+    check(lib.flanhip_filter_comb(_ptr(audio), ch, n, sample_rate, *args, int(bool(invert)), _ptr(out),
+                                  None if cancel is None else C.cast(C.byref(cancel), _vp)))
+    return out
+
+
+class filter_comb_local_forced:
+    """with fa.filter_comb_local_forced(-1): ...   -- the rounds this thread's comb calls run tile-local in LDS first (negative: none),
+    back to the library's choice afterwards"""
+
+    def __init__(self, rounds):
+        self.rounds = rounds
+
+    def __enter__(self):
+        lib.flanhip_filter_comb_debug_local(self.rounds)
+        return self
+
+    def __exit__(self, *exc):
+        lib.flanhip_filter_comb_debug_local(0)
+        return False
+
+
+def filter_comb_dev(d_audio, ch, n, sample_rate, cutoff, feedback, wet_dry, invert, d_out, d_ws, stream=None):
+    """flanhip_filter_comb_dev: cutoff, feedback and wet_dry are floats or device arrays of n floats; d_out may be d_audio"""
+    args, keep = _filter2_params((cutoff, feedback, wet_dry), n, _dp)
+    check(lib.flanhip_filter_comb_dev(_dp(d_audio), ch, n, sample_rate, *args, int(bool(invert)), _dp(d_out), _dp(d_ws), _vp(stream or 0)))
 
 
 # ---------------------------------------------------------------------------------------------------------------

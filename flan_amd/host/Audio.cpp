@@ -1,7 +1,7 @@
 // Audio.cpp -- construction and conversions of flan::Audio over the C ABI
 // (reference: src/flan/Audio/AudioConstructors.cpp, Conversions/AudioPV.cpp:12-84, Audio/AudioConversions.cpp:14-56,
 // Audio/AudioCombination.cpp:299-352, Audio/AudioTemporal.cpp:236-299, Audio/AudioVolume.cpp:5-67, 190-278,
-// Audio/AudioFilter.cpp:280-758, 1045-1263).
+// Audio/AudioFilter.cpp:280-758, 988-1263).
 #include "flan/Audio.h"
 
 #include <algorithm>
@@ -501,6 +501,27 @@ Audio Audio::filter_1pole_lowshelf( const Function<Second, Frequency> & cutoff, 
 Audio Audio::filter_1pole_highshelf( const Function<Second, Frequency> & cutoff, const Function<Second, Decibel> & gain, uint16_t order ) const
 	{
 	return filter_1pole_shelf( *this, cutoff, gain, FLANHIP_FILTER2_1POLE_HIGHSHELF, order, "filter_1pole_highshelf" );
+	}
+
+// :1008-1011: cutoff, feedback and wet_dry through sample_function_over_domain, at f * ( 1.0f / sr ); the clamp, the links and the recurrence
+// are the device's
+Audio Audio::filter_comb( const Function<Second, Frequency> & cutoff, const Function<Second, float> & feedback, const Function<Second, float> & wet_dry,
+	bool invert ) const
+	{
+	if( is_null() || !device_data() ) return Audio::create_null();     // :995; without a device nothing is sampled
+	const size_t ws_bytes = flanhip_filter_comb_workspace_bytes( get_num_channels(), get_num_frames() );
+	if( ws_bytes == 0 ) return Audio::create_null();
+	const float step = 1.0f / get_sample_rate();
+	const DeviceCurve c = upload_curve( cutoff, get_num_frames(), step ), k = upload_curve( feedback, get_num_frames(), step ),
+		a = upload_curve( wet_dry, get_num_frames(), step );
+	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( get_num_channels() ) * size_t( get_num_frames() ) );
+	auto ws = detail::DeviceBlock::allocate( ws_bytes );
+	if( !c.ok || !k.ok || !a.ok || !block || !ws ) return Audio::create_null();
+	const int rc = flanhip_filter_comb_dev( device_data(), get_num_channels(), get_num_frames(), get_sample_rate(), c.ptr(), c.scalar, k.ptr(), k.scalar,
+		a.ptr(), a.scalar, invert ? 1 : 0, static_cast<float*>( block->ptr ), ws->ptr, nullptr );
+	if( !detail::report( rc, "filter_comb" ) ) return Audio::create_null();
+	if( !detail::report( flanhip_stream_synchronize( nullptr ), "filter_comb" ) ) return Audio::create_null();         // the workspace and the curves go back idle
+	return AudioBuffer::adopt_device( get_format(), std::move( block ) );
 	}
 
 // :1168: the modulator through sample_function_over_domain, at f * ( 1.0f / sr ); the network and the product are the device's

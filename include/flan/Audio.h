@@ -138,6 +138,18 @@ public:
 	Audio filter_2pole_highshelf( const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping,
 		const Function<Second, Decibel> & gain, uint16_t order = 1 ) const;
 
+	/** The feedback comb (Audio/AudioFilter.cpp:988-1043; The Art of VA Filter Design, 11.5-11.6): u[n] = x[n] + feedback f u[p], out =
+	 *  wet_dry u[n] + ( 1 - wet_dry ) f u[p], f = invert ? -1 : 1, with the delay of half a period of the cutoff, p = trunc( n - sample rate /
+	 *  ( 2 cutoff ) ), changing every frame; on the device the links are followed by pointer jumping in fp64 (flanhip_filter_comb_dev; DESIGN.md
+	 *  4.18).  cutoff, feedback and wet_dry are sampled once per frame at f * ( 1.0f / sample rate ); a constant samples nothing.  The cutoff
+	 *  is clamped to [1, sample rate / 2], the feedback is not.  Kept quirks: the delay is truncated toward zero, so a read from between frame
+	 *  -1 and frame 0 reads frame 0, and a fractional delay d is n - trunc( n - d ) frames; a read outside the signal reads 0; a NaN cutoff
+	 *  at a frame reads 0 there.  The result is within 1 fp32 ulp of the exact recurrence, not bit-identical to the reference's fp32 loop
+	 *  unless the feedback is 0.  A feedback above 1 in magnitude is promised only while its product along a chain of reads stays in fp64's
+	 *  range.  A null *this gives a null Audio.  The result stays device-resident until read. */
+	Audio filter_comb( const Function<Second, Frequency> & cutoff, const Function<Second, float> & feedback = 0, const Function<Second, float> & wet_dry = .5,
+		bool invert = false ) const;
+
 	// ---- single sideband ----
 	/** The signal's positive spectrum alone -- an approximate Hilbert transform by a phase-difference network -- times a complex modulator, real
 	 *  part (Audio/AudioFilter.cpp:1162-1186): spectral convolution with one sideband, so a complex sinusoid shifts every frequency.  The

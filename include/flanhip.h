@@ -643,6 +643,55 @@ int flanhip_filter2_dev(const float * d_audio, int64_t num_channels, int64_t num
                         const float * d_gain, float gain, int kind, int order,
                         float * d_out, void * d_workspace, void * stream);
 
+/* ---- Audio::filter_comb (Audio/AudioFilter.cpp:988-1043): the feedback comb whose delay changes every frame, a linear recurrence over a
+ * forest of frames resolved by pointer jumping (flan_amd/csrc/comb.hip) -------------------------------------------- */
+/* audio, out: float[ch][n]; out may be the audio.  cutoff, feedback and wet_dry are each a curve of n floats (the reference samples each
+ * Function once per frame, :1008-1011) or, with a NULL curve, the scalar.  Everything is fp32, one rounding per operation, in the reference's
+ * order; f = invert ? -1 : 1 (:1006):
+ *   per frame n      w = std::clamp( cutoff, 1, sr / 2 ) (two comparisons: a NaN stays NaN), delay = 1 / ( 2 w ), d = delay sr (an fp32
+ *                    product, AudioBuffer.cpp:406-409), t = float( n ) - d, p = (int) t truncated TOWARD ZERO (:1031-1032);
+ *                    u_nmt = ( p < 0 || p >= n_frames ) ? 0 : u[p] (:1016-1020); shared by all channels
+ *   state            u[n] = x[n] + ( k f ) u_nmt, k the feedback, NOT clamped (:1035)
+ *   output           y[n] = a u[n] + ( ( 1 - a ) f ) u_nmt, a = wet_dry (:1038)
+ * Kept: a t in ( -1, 0 ) truncates to 0 and reads u[0]; p == n (only n = 0 with d < 1) reads u[0] before it is written, which is 0; a
+ * fractional d gives the delay n - trunc( n - d ); a NaN cutoff makes the cast undefined (INT_MIN on x86, which reads 0) and is DEFINED here
+ * as no link.  So frame n hangs on frame p(n) if 0 <= p(n) < n and on nothing otherwise.
+ * The reference's loop is sequential; here the links are followed by pointer jumping in fp64: with u[n] = X[n] + C[n] u[P[n]], from X = x,
+ * C = k f, P = p, a round does X[n] += C[n] X[q], C[n] *= C[q], P[n] = P[q] for q = P[n], and ceil( log2 n ) rounds leave X = u, exact to
+ * about 1e-15; u is rounded to fp32 ONCE and the output line runs in the reference's fp32 operations.  The result is within 1 fp32 ulp of
+ * the exact u, closer than the reference's own loop, and not bit-identical to it except where the feedback is 0 or no frame has a link.
+ * Deterministic (two calls agree bit for bit); a channel's output does not depend on the channels filtered with it.  _dev reads nothing
+ * back and does not synchronise: it launches every round it may need (a scalar cutoff: ceil( log2 ceil( n / max( trunc d, 1 ) ) ) + 1 of
+ * them), and a round whose predecessor left no live link returns at once.  The first rounds, an odd number k of them up to 9, run
+ * tile-local in LDS in one launch: a tile of 2048 frames owns the later ones and computes the earlier ones as a halo, which must hold the
+ * 2^k - 1 nearest ancestors of every frame it owns: ( 2^k - 1 ) ceil( d ) frames with a scalar cutoff, as many rounds as 1024 frames of
+ * halo allow.  With a cutoff curve, whose delays the host does not know, and from 2^24 frames on the level is not used.  A tile checks
+ * its halo on the device; if one fails (only a forced count can), every round runs globally as if the launch had not been: the same bits
+ * either way, one pass wasted.
+ * Limits.  |feedback| <= 1 is the contract: C is a product of feedbacks along a path, and with |feedback| > 1 over more than about a
+ * thousand links it overflows fp64 and inf * 0 gives NaN where the reference had overflowed already or, on silence, had stayed 0; above 1
+ * results are promised only while that product stays in fp64's range.  Where the reference's u is not finite, u here is not finite
+ * either, inf or NaN unspecified; frames that do not descend from such a frame are unaffected.
+ * Null audio / out (and, for _dev, workspace), non-positive sizes and sample_rate <= 0 are FLANHIP_ERR_INVALID_ARG, before any device call;
+ * num_frames >= 2^31 (the links are int32) or num_channels > 2^20 is FLANHIP_ERR_UNSUPPORTED.  `cancel` is polled before the upload, before
+ * the first launch and between the rounds. */
+/* bytes of device workspace flanhip_filter_comb_dev needs (pure host arithmetic; 0 for arguments it refuses): 64 int32 words (word r < 32
+ * set: round r had live links to follow; word 32 set: a tile of the LDS level failed; word 33, left by the last launch: the rounds the
+ * result went through), then the planes X[2][ch][n] of doubles, the rows C[2][n] of doubles and the rows P[2][n] of int32, a round
+ * reading one of each pair and writing the other: 256 + 16 * ch * n + 24 * n.  Need not be cleared. */
+size_t flanhip_filter_comb_workspace_bytes(int64_t num_channels, int64_t num_frames);
+/* test and A/B hook: the rounds the calling thread's comb calls run tile-local in LDS first: 0 the library's choice, negative none,
+ * positive that many (taken down to an odd number, 9 at most, behind a halo of 1024 frames).  No output bit depends on it. */
+void flanhip_filter_comb_debug_local(int rounds);
+int flanhip_filter_comb(const float * audio, int64_t num_channels, int64_t num_frames, float sample_rate,
+                        const float * cutoff_curve, float cutoff, const float * feedback_curve, float feedback,
+                        const float * wet_dry_curve, float wet_dry, int invert,
+                        float * out, volatile int * cancel);
+int flanhip_filter_comb_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, float sample_rate,
+                            const float * d_cutoff, float cutoff, const float * d_feedback, float feedback,
+                            const float * d_wet_dry, float wet_dry, int invert,
+                            float * d_out, void * d_workspace, void * stream);
+
 /* ---- hilbert_phase_diff_network (Audio/AudioFilter.cpp:1045-1160) and the single-sideband methods over it: Audio::halfband_modulate
  * (:1162-1186), the modulation of Audio::shift_frequency (:1188-1227) and Audio::halfband_multiply (:1229-1263).  The network is two
  * cascades of ten 1-pole all-pass sections with constant poles; a cascade is one linear system with a constant 10 x 10 lower-triangular
