@@ -159,6 +159,10 @@ _SIGS = {
     "flanhip_filter_comb_debug_local": (None, [_i32]),
     "flanhip_filter_comb": (C.c_int, [_vp, _i64, _i64, _f32] + [_vp, _f32] * 3 + [_i32, _vp, _vp]),
     "flanhip_filter_comb_dev": (C.c_int, [_vp, _i64, _i64, _f32] + [_vp, _f32] * 3 + [_i32, _vp, _vp, _vp]),
+    "flanhip_multinotch_workspace_bytes": (C.c_size_t, [_i64, _i64, _i32, _i32]),
+    "flanhip_multinotch_debug_run": (None, [_i32]),
+    "flanhip_multinotch": (C.c_int, [_vp, _i64, _i64, _f32] + [_vp, _f32] * 4 + [_i32, _i32, _i32, _vp, _vp]),
+    "flanhip_multinotch_dev": (C.c_int, [_vp, _i64, _i64, _f32] + [_vp, _f32] * 4 + [_i32, _i32, _i32, _vp, _vp, _vp]),
     "flanhip_halfband_poles": (None, [_vp, _vp]),
     "flanhip_halfband_workspace_bytes": (C.c_size_t, [_i64, _i64]),
     "flanhip_halfband_debug_run": (None, [_i32]),
@@ -1033,6 +1037,50 @@ def filter_comb_dev(d_audio, ch, n, sample_rate, cutoff, feedback, wet_dry, inve
     """flanhip_filter_comb_dev: cutoff, feedback and wet_dry are floats or device arrays of n floats; d_out may be d_audio"""
     args, keep = _filter2_params((cutoff, feedback, wet_dry), n, _dp)
     check(lib.flanhip_filter_comb_dev(_dp(d_audio), ch, n, sample_rate, *args, int(bool(invert)), _dp(d_out), _dp(d_ws), _vp(stream or 0)))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Audio::filter_1pole_multinotch / filter_2pole_multinotch (use_saturator == false).  Cutoff, damping, feedback and wet_dry are each a float
+# (the scalar) or an array of n floats (a curve); the 1-pole kind does not look at damping
+# ---------------------------------------------------------------------------------------------------------------
+
+MULTINOTCH_1POLE, MULTINOTCH_2POLE = range(2)
+
+
+def multinotch_workspace_bytes(ch, n, kind, order):
+    return int(lib.flanhip_multinotch_workspace_bytes(ch, n, kind, order))
+
+
+def multinotch(audio, sample_rate, cutoff, damping=1.0, feedback=0.0, wet_dry=0.5, kind=MULTINOTCH_1POLE, order=1, invert=False, cancel=None):
+    """the multinotch of a MULTINOTCH_* kind.  audio float32 [ch][n] -> float32 [ch][n].  cancel: None or a ctypes.c_int the call polls"""
+    audio = np.ascontiguousarray(audio, np.float32)
+    ch, n = audio.shape
+    args, keep = _filter2_params((cutoff, damping, feedback, wet_dry), n, _ptr)
+    out = np.empty_like(audio)
+    check(lib.flanhip_multinotch(_ptr(audio), ch, n, sample_rate, *args, kind, order, int(bool(invert)), _ptr(out),
+                                 None if cancel is None else C.cast(C.byref(cancel), _vp)))
+    return out
+
+
+def multinotch_dev(d_audio, ch, n, sample_rate, cutoff, damping, feedback, wet_dry, kind, order, invert, d_out, d_ws, stream=None):
+    """flanhip_multinotch_dev: the four parameters are floats or device arrays of n floats; d_out may be d_audio"""
+    args, keep = _filter2_params((cutoff, damping, feedback, wet_dry), n, _dp)
+    check(lib.flanhip_multinotch_dev(_dp(d_audio), ch, n, sample_rate, *args, kind, order, int(bool(invert)), _dp(d_out), _dp(d_ws), _vp(stream or 0)))
+
+
+class multinotch_run_forced:
+    """with fa.multinotch_run_forced(4): ...   -- the frames per team of this thread's multinotch calls, back to the library's choice afterwards"""
+
+    def __init__(self, frames):
+        self.frames = frames
+
+    def __enter__(self):
+        lib.flanhip_multinotch_debug_run(self.frames)
+        return self
+
+    def __exit__(self, *exc):
+        lib.flanhip_multinotch_debug_run(0)
+        return False
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -524,6 +524,51 @@ Audio Audio::filter_comb( const Function<Second, Frequency> & cutoff, const Func
 	return AudioBuffer::adopt_device( get_format(), std::move( block ) );
 	}
 
+// :813-815, :830-831, :912-915, :978: every parameter once per frame at f * ( 1.0f / sr ), as filter_comb samples; the clamp, the prewarp and the
+// scan are the device's.  What the device form does not offer is refused here, before anything is sampled or uploaded
+static Audio multinotch( const Audio & me, const char * name, int kind, uint16_t order, const Function<Second, Frequency> & cutoff,
+	const Function<Second, float> * damping, const Function<Second, float> & feedback, bool invert, const Function<Second, float> & wet_dry, bool use_saturator )
+	{
+	if( me.is_null() ) return Audio::create_null();                    // :811, :910
+	if( use_saturator )
+		{
+		std::cerr << "flan: " << name << ": use_saturator is not offered on the device (a Newton iteration per frame, not linear in the state)" << std::endl;
+		return Audio::create_null();
+		}
+	const size_t ws_bytes = flanhip_multinotch_workspace_bytes( me.get_num_channels(), me.get_num_frames(), kind, order );
+	if( ws_bytes == 0 )
+		{
+		std::cerr << "flan: " << name << " refused order " << order << " on " << me.get_num_channels() << " x " << me.get_num_frames()
+		          << ": the order is 1 ... " << ( kind == FLANHIP_MULTINOTCH_1POLE ? 16 : 8 ) << std::endl;
+		return Audio::create_null();
+		}
+	if( !me.device_data() ) return Audio::create_null();               // without a device nothing is sampled
+	const Frame n = me.get_num_frames();
+	const float step = 1.0f / me.get_sample_rate();
+	const DeviceCurve c = upload_curve( cutoff, n, step ), R = damping ? upload_curve( *damping, n, step ) : DeviceCurve{},
+		k = upload_curve( feedback, n, step ), a = upload_curve( wet_dry, n, step );
+	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( me.get_num_channels() ) * size_t( n ) );
+	auto ws = detail::DeviceBlock::allocate( ws_bytes );
+	if( !c.ok || ( damping && !R.ok ) || !k.ok || !a.ok || !block || !ws ) return Audio::create_null();
+	const int rc = flanhip_multinotch_dev( me.device_data(), me.get_num_channels(), n, me.get_sample_rate(), c.ptr(), c.scalar, R.ptr(), R.scalar,
+		k.ptr(), k.scalar, a.ptr(), a.scalar, kind, order, invert ? 1 : 0, static_cast<float*>( block->ptr ), ws->ptr, nullptr );
+	if( !detail::report( rc, name ) ) return Audio::create_null();
+	if( !detail::report( flanhip_stream_synchronize( nullptr ), name ) ) return Audio::create_null();         // the workspace and the curves go back idle
+	return AudioBuffer::adopt_device( me.get_format(), std::move( block ) );
+	}
+
+Audio Audio::filter_1pole_multinotch( uint16_t order, const Function<Second, Frequency> & cutoff, const Function<Second, float> & feedback, bool invert,
+	const Function<Second, float> & wet_dry, bool use_saturator ) const
+	{
+	return multinotch( *this, "filter_1pole_multinotch", FLANHIP_MULTINOTCH_1POLE, order, cutoff, nullptr, feedback, invert, wet_dry, use_saturator );
+	}
+
+Audio Audio::filter_2pole_multinotch( uint16_t order, const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping,
+	const Function<Second, float> & feedback, bool invert, const Function<Second, float> & wet_dry, bool use_saturator ) const
+	{
+	return multinotch( *this, "filter_2pole_multinotch", FLANHIP_MULTINOTCH_2POLE, order, cutoff, &damping, feedback, invert, wet_dry, use_saturator );
+	}
+
 // :1168: the modulator through sample_function_over_domain, at f * ( 1.0f / sr ); the network and the product are the device's
 Audio Audio::halfband_modulate( const Function<Second, std::complex<float>> & modulator ) const
 	{

@@ -150,6 +150,22 @@ public:
 	Audio filter_comb( const Function<Second, Frequency> & cutoff, const Function<Second, float> & feedback = 0, const Function<Second, float> & wet_dry = .5,
 		bool invert = false ) const;
 
+	/** The 1-pole multinotch (Audio/AudioFilter.cpp:802-885; The Art of VA Filter Design, 11.2, 11.6): `order` 1-pole all-pass sections in a
+	 *  row with an instantaneous feedback path around them, x_bar = x + inv feedback allpass^order( x_bar ) solved in closed form per frame,
+	 *  out = wet_dry x_bar + ( 1 - wet_dry ) inv allpass^order( x_bar ), inv = invert ? -1 : 1: at wet_dry .5 a notch at every other multiple
+	 *  of pi of the cascade's phase.  On the device a frame is a dense map of the `order` states and the frames are a scan of such maps
+	 *  (flanhip_multinotch_dev); the result is within the reference's own fp32 rounding of the exact loop, not bit-identical
+	 *  to it.  cutoff, feedback and wet_dry are sampled once per frame at f * ( 1.0f / sample rate ); a constant samples nothing.  The cutoff
+	 *  is clamped to [1, sample rate / 2] and prewarped; the feedback is not clamped, | feedback | < 1 is the stable range.  NOT offered:
+	 *  use_saturator == true (a Newton iteration on tanh per frame, no scan), order 0 (undefined in the reference) and orders above 16: each
+	 *  gives a message and a null Audio.  A null *this gives a null Audio.  The result stays device-resident until read. */
+	Audio filter_1pole_multinotch( uint16_t order, const Function<Second, Frequency> & cutoff, const Function<Second, float> & feedback = 0, bool invert = false,
+		const Function<Second, float> & wet_dry = .5, bool use_saturator = false ) const;
+	/** The 2-pole multinotch (:887-986): as the 1-pole one with `order` state-variable sections, each putting out lp - 2 damping bp + hp, whose
+	 *  damping is sampled per frame like the rest and is not clamped.  Orders 1 ... 8 (16 states). */
+	Audio filter_2pole_multinotch( uint16_t order, const Function<Second, Frequency> & cutoff, const Function<Second, float> & damping,
+		const Function<Second, float> & feedback = 0, bool invert = false, const Function<Second, float> & wet_dry = .5, bool use_saturator = false ) const;
+
 	// ---- single sideband ----
 	/** The signal's positive spectrum alone -- an approximate Hilbert transform by a phase-difference network -- times a complex modulator, real
 	 *  part (Audio/AudioFilter.cpp:1162-1186): spectral convolution with one sideband, so a complex sinusoid shifts every frequency.  The

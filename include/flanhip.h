@@ -692,6 +692,58 @@ int flanhip_filter_comb_dev(const float * d_audio, int64_t num_channels, int64_t
                             const float * d_wet_dry, float wet_dry, int invert,
                             float * d_out, void * d_workspace, void * stream);
 
+/* ---- Audio::filter_1pole_multinotch (Audio/AudioFilter.cpp:802-885) and filter_2pole_multinotch (:887-986), use_saturator == false: an
+ * all-pass cascade coupled through an instantaneous feedback path, a scan of dense D x D state-space systems that change every frame
+ * (flan_amd/csrc/multinotch.hip) ------------------------------------------------------------------------------------ */
+/* audio, out: float[ch][n]; out may be the audio.  cutoff, damping, feedback and wet_dry are each a curve of n floats (one value per
+ * frame, as the reference samples or calls each Function, :813-815, :830-831, :912-915, :978) or, with a NULL curve, the scalar.  The
+ * 1-pole kind does not look at damping.  inv = invert ? -1 : 1 (:816), T_half = pi / sr (pi = acosf( -1 ), :818).  Per frame, shared by
+ * all channels: c = std::clamp( cutoff, 1, sr / 2 ) (two comparisons: a NaN stays NaN), w = tan( T_half c ) / T_half, g = w T_half
+ * (:814, :829, :833; the sections are then run with use_prewarp == false), k = feedback, R = damping, a = wet_dry.  Per channel and frame:
+ *   1POLE   G = ( g - 1 ) / ( g + 1 ), M = ( sum_{i < order} pow( G, i ) s[order-1-i] ) * ( 2 / ( 1 + g ) ) (:834-839),
+ *           x_bar = ( x + inv k M ) / ( 1 - inv k pow( G, order ) ) (:867); x_bar then runs through the `order` 1-pole sections in turn
+ *           (Gs = g / ( 1 + g ), v = Gs ( in - s ), lp = v + s, s = lp + v, :61-74), each putting out lp - ( in - lp ) (the mix { 1, -1 }, :874)
+ *   2POLE   d = 1 / ( 1 + 2 R g + g g ), G = d ( 1 - 2 R g + g g ), M = sum_{i < order} pow( G, i ) ( g s2 - s1 )[order-1-i] (:934-939),
+ *           x_bar = ( x + inv k 4 R d M ) / ( 1 - inv k pow( G, order ) ) (:967); the sections are the state-variable ones (:164-182) with
+ *           the frame's g and R, each putting out ( lp - bp 2 R ) + hp (the mix { 1, -1, 1 }, :974)
+ *   then    y_bar = inv * the last section's output, y = a x_bar + ( 1 - a ) y_bar (:876-878, :976-979); every state starts at 0.
+ * The reference's arithmetic is kept: pow with an integer exponent is the DOUBLE function, so M += pow * s is a double product and a
+ * double sum rounded to float at every term, and the denominator is a double, the quotient rounded to float once; everything else is
+ * fp32, one rounding per operation, left to right (inv * k first, the 2-pole numerator ((((inv k) 4) R) d) M).  tan is the fp64 function of the fp32
+ * product rounded to fp32 once; pow( G, order ) is the fp64 function; the powers of the sum are i fp64 products, i fp64 ulps from pow.
+ * Damping and feedback are NOT clamped.
+ * The reference's loop is sequential; here a frame is the linear map s' = A s + b x of the D = order (1POLE) or 2 order (2POLE) states,
+ * runs of frames are reduced in fp64 to dense pairs ( A, r ) that a team of lanes holds by columns, the pairs are scanned, and every run
+ * is REPLAYED with the operations above from a start state rounded to fp32 once.  Deterministic (two calls agree bit for bit); a
+ * channel's output does not depend on the channels filtered with it.  _dev reads nothing back and does not synchronise.
+ * Limits.  |feedback| < 1 is the stable range.  Outside it results are promised only while the products of the frames' matrices stay in
+ * fp64's range.  Where the reference's output is not finite, the output here is not finite either, inf or NaN unspecified; a sample
+ * that is not finite reaches no earlier frame and no other channel.
+ * NOT offered: use_saturator == true (:842-864, :942-964), a Newton iteration on tanh per frame from the previous output, which is not
+ * linear in the state and so no scan; and order == 0, where the reference reads an uninitialised y_bar.
+ * Null audio / out (and, for _dev, workspace), non-positive sizes, sample_rate <= 0, an unknown kind and order <= 0 are
+ * FLANHIP_ERR_INVALID_ARG; D > 16 (1POLE order > 16, 2POLE order > 8), num_channels > 2^20 and num_frames > 2^36 are
+ * FLANHIP_ERR_UNSUPPORTED; all before any device call.  `cancel` is polled before the upload, before the first launch and between the launches. */
+#define FLANHIP_MULTINOTCH_1POLE 0   /* AudioFilter.cpp:802-885 */
+#define FLANHIP_MULTINOTCH_2POLE 1   /* :887-986 */
+/* bytes of device workspace flanhip_multinotch_dev needs (pure host arithmetic; 0 for arguments it refuses).  With DP = 4, 8 or 16, the
+ * least of them >= D, a block of 256 threads has 128 / DP teams of `run` frames each: the row of denominators (n doubles, n rounded up to
+ * 4) and the rows g, R, inv k and a (floats), then per channel and block a total of ( DP + 1 ) DP doubles and a carried state of DP:
+ * 24 * roundup( n, 4 ) + 8 * DP * ( DP + 2 ) * ch * ceil( n / ( ( 128 / DP ) * run ) ); run is 16 DP (a block is 2048 frames) unless the
+ * calling thread's flanhip_multinotch_debug_run setting says otherwise.  Need not be cleared. */
+size_t flanhip_multinotch_workspace_bytes(int64_t num_channels, int64_t num_frames, int kind, int order);
+/* test hook: the frames one team reduces and replays in the calling thread's multinotch calls, 1 ... 64 (larger values are taken as 64;
+ * 0: the library's choice, 16 DP = 64, 128 or 256).  Results do not depend on it beyond rounding. */
+void flanhip_multinotch_debug_run(int frames);
+int flanhip_multinotch(const float * audio, int64_t num_channels, int64_t num_frames, float sample_rate,
+                       const float * cutoff_curve, float cutoff, const float * damping_curve, float damping,
+                       const float * feedback_curve, float feedback, const float * wet_dry_curve, float wet_dry,
+                       int kind, int order, int invert, float * out, volatile int * cancel);
+int flanhip_multinotch_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, float sample_rate,
+                           const float * d_cutoff, float cutoff, const float * d_damping, float damping,
+                           const float * d_feedback, float feedback, const float * d_wet_dry, float wet_dry,
+                           int kind, int order, int invert, float * d_out, void * d_workspace, void * stream);
+
 /* ---- hilbert_phase_diff_network (Audio/AudioFilter.cpp:1045-1160) and the single-sideband methods over it: Audio::halfband_modulate
  * (:1162-1186), the modulation of Audio::shift_frequency (:1188-1227) and Audio::halfband_multiply (:1229-1263).  The network is two
  * cascades of ten 1-pole all-pass sections with constant poles; a cascade is one linear system with a constant 10 x 10 lower-triangular
