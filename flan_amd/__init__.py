@@ -172,6 +172,19 @@ _SIGS = {
     "flanhip_halfband_modulate_dev": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _f32, _vp, _f32, _vp, _vp, _vp, _vp]),
     "flanhip_halfband_multiply": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _i64, _i64, _f32, _vp, _vp]),
     "flanhip_halfband_multiply_dev": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _i64, _i64, _f32, _vp, _vp, _vp]),
+    "flanhip_spatial_ear": (C.c_int, [_vp, _vp, _i64, _i64, _f32, _vp, C.c_double, C.c_double, _f32, _i32, _vp, _vp]),
+    "flanhip_spatial_ear_dev": (C.c_int, [_vp, _vp, _i64, _i64, _f32, _vp, C.c_double, C.c_double, _f32, _i32, _vp, _vp]),
+    "flanhip_spatial_delay_dev": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "flanhip_spatial_itd_out_frames": (_i64, [_i64, _f32, _vp, _i64, _vp]),
+    "flanhip_spatial_itd_plan": (_i64, [_i64, _f32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "flanhip_spatial_itd_workspace_bytes": (C.c_size_t, [_i64, _i64, _f32, _vp, _i64]),
+    "flanhip_spatial_itd": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "flanhip_spatial_itd_dev": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "flanhip_audio_pan": (C.c_int, [_vp, _i64, _i64, _vp, _f32, _vp, _vp]),
+    "flanhip_audio_pan_dev": (C.c_int, [_vp, _i64, _i64, _vp, _f32, _vp, _vp]),
+    "flanhip_audio_to_stereo_dev": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "flanhip_audio_to_mono_dev": (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
+    "flanhip_audio_copy_rows_dev": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp]),
 }
 
 EXPORTS = sorted(_SIGS)
@@ -1166,3 +1179,122 @@ class halfband_run_forced:
     def __exit__(self, *exc):
         lib.flanhip_halfband_debug_run(0)
         return False
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Audio::stereo_spatialize, pan, convert_to_stereo / convert_to_mono, combine_channels / split_channels
+# ---------------------------------------------------------------------------------------------------------------
+
+SPATIAL_LEFT, SPATIAL_RIGHT, SPATIAL_BOTH = 1, 2, 3
+SPATIAL_GRANULARITY = 32
+
+
+def _spatial_position(positions, pointer):
+    """( pointer or None, x, y ): a pair is the constant position, an array [n][2] of doubles the sampled one"""
+    if isinstance(positions, np.ndarray) and positions.ndim == 2 or hasattr(positions, "data_ptr"):
+        return pointer(positions), 0.0, 0.0
+    return None, float(positions[0]), float(positions[1])
+
+
+def spatial_ear(audio, lowpassed, sample_rate, positions, head_width=0.18, ears=SPATIAL_BOTH):
+    """head_ild + falloff.  audio, lowpassed float32 [n]; positions float64 [n][2] or a pair -> float32 [1 or 2][n], the left ear first"""
+    audio, lowpassed = np.ascontiguousarray(audio, np.float32).reshape(-1), np.ascontiguousarray(lowpassed, np.float32).reshape(-1)
+    if isinstance(positions, np.ndarray) and positions.ndim == 2:
+        positions = np.ascontiguousarray(positions, np.float64)
+    p, x, y = _spatial_position(positions, _ptr)
+    out = np.empty((2 if ears == SPATIAL_BOTH else 1, audio.size), np.float32)
+    check(lib.flanhip_spatial_ear(_ptr(audio), _ptr(lowpassed), 1, audio.size, sample_rate, p, x, y, head_width, ears, _ptr(out), None))
+    return out
+
+
+def spatial_ear_dev(d_audio, d_lowpassed, n, sample_rate, positions, head_width, ears, d_out, stream=None):
+    p, x, y = _spatial_position(positions, _dp)
+    check(lib.flanhip_spatial_ear_dev(_dp(d_audio), _dp(d_lowpassed), 1, n, sample_rate, p, x, y, head_width, ears, _dp(d_out), _vp(stream or 0)))
+
+
+def spatial_delay_dev(d_audio, ears, n, delays, out_frames, out_stride, d_out, stream=None):
+    delays, out_frames = np.ascontiguousarray(delays, np.float32), np.ascontiguousarray(out_frames, np.int64)
+    check(lib.flanhip_spatial_delay_dev(_dp(d_audio), ears, n, _ptr(delays), _ptr(out_frames), out_stride, _dp(d_out), _vp(stream or 0)))
+
+
+def spatial_itd_out_frames(num_frames, sample_rate, distances):
+    """( output length, stretches ) from the distances at frames 0, 32, 64, ..."""
+    d = np.ascontiguousarray(distances, np.float64)
+    stretches = np.empty(d.size, np.float64)
+    nout = int(lib.flanhip_spatial_itd_out_frames(num_frames, sample_rate, _ptr(d), d.size, _ptr(stretches)))
+    if nout < 0:
+        check(nout)
+    return nout, stretches
+
+
+def spatial_itd_plan(num_frames, sample_rate, stretches):
+    """The block loop on the host: a dict of per-block arrays (offset, fracpos, ratio, filtpos, oversize, ideal, first_out, delivered,
+    buffered) and total_out."""
+    st = np.ascontiguousarray(stretches, np.float64)
+    total = _i64(0)
+    blocks = lib.flanhip_spatial_itd_plan(num_frames, sample_rate, _ptr(st), st.size, 0, None, None, None, None, None, None, None, None, None,
+                                          C.byref(total))
+    if blocks < 0:
+        check(int(blocks))
+    p = {"offset": np.empty(blocks, np.int64), "fracpos": np.empty(blocks, np.float64), "ratio": np.empty(blocks, np.float64),
+         "filtpos": np.empty(blocks, np.float64), "oversize": np.empty(blocks, np.int32), "ideal": np.empty(blocks, np.int32),
+         "first_out": np.empty(blocks, np.int64), "delivered": np.empty(blocks, np.int32), "buffered": np.empty(blocks, np.int32)}
+    got = lib.flanhip_spatial_itd_plan(num_frames, sample_rate, _ptr(st), st.size, blocks, _ptr(p["offset"]), _ptr(p["fracpos"]), _ptr(p["ratio"]),
+                                       _ptr(p["filtpos"]), _ptr(p["oversize"]), _ptr(p["ideal"]), _ptr(p["first_out"]), _ptr(p["delivered"]),
+                                       _ptr(p["buffered"]), C.byref(total))
+    assert got == blocks
+    p["total_out"] = int(total.value)
+    return p
+
+
+def spatial_itd_workspace_bytes(num_frames, sample_rate, stretches):
+    st = np.atleast_2d(np.ascontiguousarray(stretches, np.float64))
+    return int(lib.flanhip_spatial_itd_workspace_bytes(st.shape[0], num_frames, sample_rate, _ptr(st), st.shape[1]))
+
+
+def spatial_itd(audio, sample_rate, stretches, out_frames, out_stride=None):
+    """head_itd for a moving source.  audio float32 [ears][n], stretches float64 [ears][ceil( n / 32 )], out_frames one per ear ->
+    float32 [ears][out_stride] (out_stride: the longest ear unless given)"""
+    audio = np.atleast_2d(np.ascontiguousarray(audio, np.float32))
+    st = np.atleast_2d(np.ascontiguousarray(stretches, np.float64))
+    nout = np.ascontiguousarray(np.atleast_1d(out_frames), np.int64)
+    ears, n = audio.shape
+    stride = int(out_stride if out_stride is not None else max(int(nout.max()), 1))
+    out = np.empty((ears, stride), np.float32)
+    check(lib.flanhip_spatial_itd(_ptr(audio), ears, n, sample_rate, _ptr(st), st.shape[1], _ptr(nout), stride, _ptr(out), None))
+    return out
+
+
+def spatial_itd_dev(d_audio, ears, n, sample_rate, stretches, out_frames, out_stride, d_out, d_ws, stream=None):
+    st = np.atleast_2d(np.ascontiguousarray(stretches, np.float64))
+    nout = np.ascontiguousarray(np.atleast_1d(out_frames), np.int64)
+    check(lib.flanhip_spatial_itd_dev(_dp(d_audio), ears, n, sample_rate, _ptr(st), st.shape[1], _ptr(nout), out_stride, _dp(d_out), _dp(d_ws),
+                                      _vp(stream or 0)))
+
+
+def audio_pan(audio, pan):
+    """Audio::pan_in_place.  audio float32 [2][n]; pan a float or float32 [n] -> float32 [2][n]"""
+    audio = np.ascontiguousarray(audio, np.float32)
+    ch, n = audio.shape
+    curve = None if np.isscalar(pan) else np.ascontiguousarray(pan, np.float32)
+    out = np.empty_like(audio)
+    check(lib.flanhip_audio_pan(_ptr(audio), ch, n, None if curve is None else _ptr(curve), 0.0 if curve is not None else float(pan), _ptr(out), None))
+    return out
+
+
+def audio_pan_dev(d_audio, ch, n, pan, d_out, stream=None):
+    """pan: a float or a device array of n floats; d_out may be d_audio"""
+    scalar = isinstance(pan, (int, float))
+    check(lib.flanhip_audio_pan_dev(_dp(d_audio), ch, n, None if scalar else _dp(pan), float(pan) if scalar else 0.0, _dp(d_out), _vp(stream or 0)))
+
+
+def audio_to_stereo_dev(d_audio, n, d_out, stream=None):
+    check(lib.flanhip_audio_to_stereo_dev(_dp(d_audio), n, _dp(d_out), _vp(stream or 0)))
+
+
+def audio_to_mono_dev(d_audio, ch, n, d_out, stream=None):
+    check(lib.flanhip_audio_to_mono_dev(_dp(d_audio), ch, n, _dp(d_out), _vp(stream or 0)))
+
+
+def audio_copy_rows_dev(d_src, src_stride, rows, src_frames, d_dst, dst_stride, dst_frames, stream=None):
+    check(lib.flanhip_audio_copy_rows_dev(_dp(d_src), src_stride, rows, src_frames, _dp(d_dst), dst_stride, dst_frames, _vp(stream or 0)))

@@ -1,7 +1,7 @@
 // Audio.cpp -- construction and conversions of flan::Audio over the C ABI
 // (reference: src/flan/Audio/AudioConstructors.cpp, Conversions/AudioPV.cpp:12-84, Audio/AudioConversions.cpp:14-56,
 // Audio/AudioCombination.cpp:299-352, Audio/AudioTemporal.cpp:236-299, Audio/AudioVolume.cpp:5-67, 190-278,
-// Audio/AudioFilter.cpp:280-758, 988-1263).
+// Audio/AudioFilter.cpp:280-758, 988-1263, Audio/AudioConversions.cpp:58-104, Audio/AudioChannels.cpp, Audio/AudioSpatial.cpp).
 #include "flan/Audio.h"
 
 #include <algorithm>
@@ -661,6 +661,265 @@ Audio Audio::halfband_multiply( const Audio & modulator ) const
 	if( !detail::report( rc, "halfband_multiply" ) ) return Audio::create_null();
 	if( !detail::report( flanhip_stream_synchronize( nullptr ), "halfband_multiply" ) ) return Audio::create_null();     // the workspace goes back idle
 	return AudioBuffer::adopt_device( f, std::move( block ) );
+	}
+
+// ---- channels (Audio/AudioConversions.cpp:58-104, Audio/AudioChannels.cpp) --------------------------------------------------------------
+Audio Audio::convert_to_stereo() const
+	{
+	if( is_null() ) return Audio::create_null();                // AudioConversions.cpp:60
+	if( get_num_channels() == 2 ) return copy();                // :78-79
+	if( get_num_channels() != 1 )
+		{
+		std::cout << "I don't know how to convert that number of channels to stereo." << std::endl;     // :81
+		return create_empty_with_frames( get_num_frames(), 2, get_sample_rate() );                      // the zero-initialised `out` of :64
+		}
+	const float * d_x = device_data();
+	if( !d_x ) return Audio::create_null();
+	AudioBuffer::Format f = get_format();
+	f.num_channels = 2;
+	auto block = detail::DeviceBlock::allocate( sizeof( float ) * 2 * size_t( f.num_frames ) );
+	if( !block ) return Audio::create_null();
+	if( !detail::report( flanhip_audio_to_stereo_dev( d_x, f.num_frames, static_cast<float*>( block->ptr ), nullptr ), "convert_to_stereo" ) ) return Audio::create_null();
+	if( !detail::report( flanhip_stream_synchronize( nullptr ), "convert_to_stereo" ) ) return Audio::create_null();
+	return AudioBuffer::adopt_device( f, std::move( block ) );
+	}
+
+Audio Audio::convert_to_mono() const
+	{
+	if( is_null() ) return Audio::create_null();                // :89
+	const float * d_x = device_data();
+	if( !d_x ) return Audio::create_null();
+	AudioBuffer::Format f = get_format();
+	f.num_channels = 1;
+	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( f.num_frames ) );
+	if( !block ) return Audio::create_null();
+	if( !detail::report( flanhip_audio_to_mono_dev( d_x, get_num_channels(), f.num_frames, static_cast<float*>( block->ptr ), nullptr ), "convert_to_mono" ) )
+		return Audio::create_null();
+	if( !detail::report( flanhip_stream_synchronize( nullptr ), "convert_to_mono" ) ) return Audio::create_null();
+	return AudioBuffer::adopt_device( f, std::move( block ) );
+	}
+
+std::vector<Audio> Audio::split_channels() const
+	{
+	std::vector<Audio> channels;                                // AudioChannels.cpp:16-28
+	if( is_null() ) return channels;
+	const float * d_x = device_data();
+	AudioBuffer::Format f = get_format();
+	f.num_channels = 1;
+	for( Channel channel = 0; channel < get_num_channels(); ++channel )
+		{
+		auto block = d_x ? detail::DeviceBlock::allocate( sizeof( float ) * size_t( f.num_frames ) ) : nullptr;
+		const bool ok = block && detail::report( flanhip_audio_copy_rows_dev( d_x + size_t( channel ) * size_t( f.num_frames ), f.num_frames, 1, f.num_frames,
+			static_cast<float*>( block->ptr ), f.num_frames, f.num_frames, nullptr ), "split_channels" );
+		channels.emplace_back( ok ? Audio( AudioBuffer::adopt_device( f, std::move( block ) ) ) : Audio() );
+		}
+	if( d_x ) detail::report( flanhip_stream_synchronize( nullptr ), "split_channels" );
+	return channels;
+	}
+
+Audio Audio::combine_channels( const std::vector<const Audio *> & channels_unmatched )
+	{
+	if( channels_unmatched.empty() ) return Audio::create_null();                  // :35
+	for( const Audio * a : channels_unmatched ) if( !a || a->is_null() ) return Audio::create_null();
+	// match_sample_rates_or_return_null (AudioCombination.cpp:17-35): unless all rates are the highest one, every input is resampled to it
+	FrameRate max_sr = 0;
+	bool all_match = true;
+	for( const Audio * a : channels_unmatched ) max_sr = std::max( max_sr, a->get_sample_rate() );
+	for( const Audio * a : channels_unmatched ) if( a->get_sample_rate() != max_sr ) all_match = false;
+	std::vector<Audio> resampled;
+	std::vector<const Audio *> channels = channels_unmatched;
+	if( !all_match )
+		{
+		for( const Audio * a : channels_unmatched ) resampled.emplace_back( a->resample( max_sr ) );
+		for( size_t i = 0; i < resampled.size(); ++i )
+			{
+			if( resampled[i].is_null() ) return Audio::create_null();
+			channels[i] = &resampled[i];
+			}
+		}
+	AudioBuffer::Format f;                                                         // :41-46
+	f.sample_rate = channels[0]->get_sample_rate();
+	f.num_channels = 0; f.num_frames = 0;
+	for( const Audio * a : channels ) { f.num_channels += a->get_num_channels(); f.num_frames = std::max( f.num_frames, a->get_num_frames() ); }
+	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( f.num_channels ) * size_t( f.num_frames ) );
+	if( !block ) return Audio::create_null();
+	Channel current = 0;
+	for( const Audio * a : channels )                                              // :50-59; what lies behind a shorter input is zero (:48)
+		{
+		const float * d_a = a->device_data();
+		if( !d_a ) return Audio::create_null();
+		const int rc = flanhip_audio_copy_rows_dev( d_a, a->get_num_frames(), a->get_num_channels(), a->get_num_frames(),
+			static_cast<float*>( block->ptr ) + size_t( current ) * size_t( f.num_frames ), f.num_frames, f.num_frames, nullptr );
+		if( !detail::report( rc, "combine_channels" ) ) return Audio::create_null();
+		current += a->get_num_channels();
+		}
+	if( !detail::report( flanhip_stream_synchronize( nullptr ), "combine_channels" ) ) return Audio::create_null();
+	return AudioBuffer::adopt_device( f, std::move( block ) );
+	}
+
+Audio Audio::combine_channels( const std::vector<Audio> & channels )
+	{
+	std::vector<const Audio *> ptrs;                                               // :64-67
+	for( const Audio & a : channels ) ptrs.push_back( &a );
+	return combine_channels( ptrs );
+	}
+
+// ---- spatial (Audio/AudioSpatial.cpp) -------------------------------------------------------------------------------------------------------
+// pan_in_place's arithmetic (:27-38) over a stereo Audio into a fresh block; pan_amount through sample_function_over_domain, at f * ( 1.0f / sr )
+static Audio panned( const Audio & stereo, const Function<Second, float> & pan_amount )
+	{
+	const float * d_x = stereo.device_data();
+	if( !d_x ) return Audio();                                    // without a device nothing is sampled
+	const DeviceCurve p = upload_curve( pan_amount, stereo.get_num_frames(), 1.0f / stereo.get_sample_rate() );
+	auto block = detail::DeviceBlock::allocate( sizeof( float ) * 2 * size_t( stereo.get_num_frames() ) );
+	if( !p.ok || !block ) return Audio();
+	const int rc = flanhip_audio_pan_dev( d_x, 2, stereo.get_num_frames(), p.ptr(), p.scalar, static_cast<float*>( block->ptr ), nullptr );
+	if( !detail::report( rc, "pan" ) ) return Audio();
+	if( !detail::report( flanhip_stream_synchronize( nullptr ), "pan" ) ) return Audio();                   // the curve goes back idle
+	return AudioBuffer::adopt_device( stereo.get_format(), std::move( block ) );
+	}
+
+Audio Audio::pan( const Function<Second, float> & pan_amount ) const
+	{
+	if( is_null() ) return Audio::create_null();                // :11
+	if( get_num_channels() != 1 && get_num_channels() != 2 ) return Audio::create_null();     // :13-14
+	if( get_num_channels() == 2 ) { Audio out = panned( *this, pan_amount ); return out.is_null() ? Audio::create_null() : std::move( out ); }
+	const Audio stereo = convert_to_stereo();                   // :16
+	if( stereo.is_null() ) return Audio::create_null();
+	Audio out = panned( stereo, pan_amount );
+	return out.is_null() ? Audio::create_null() : std::move( out );
+	}
+
+Audio & Audio::pan_in_place( const Function<Second, float> & pan_amount )
+	{
+	if( is_null() ) { std::cout << "Null input" << std::endl; return *this; }      // :23
+	if( get_num_channels() != 2 ) return *this;                 // :25
+	Audio out = panned( *this, pan_amount );
+	if( !out.is_null() ) *this = std::move( out );
+	return *this;
+	}
+
+Audio Audio::widen( const Function<Second, float> & widen_amount ) const
+	{
+	return convert_to_mid_side().pan( widen_amount ).convert_to_left_right();      // :44
+	}
+
+Audio Audio::stereo_spatialize( const Function<Second, vec2> & position, Meter head_width, const Function<Second, float> & speed_limit ) const
+	{
+	if( get_num_channels() != 1 )
+		{
+		std::cout << "Audio::spacialize only operates on mono inputs." << std::endl;             // :231
+		return Audio::create_null();
+		}
+	if( is_null() ) return Audio::create_null();
+	const Frame n = get_num_frames();
+	const Frame granularity_frames = 32;                                           // :137
+	const float sr = get_sample_rate(), sound_mps = 343;                           // :7
+	if( !position.is_constant() && n <= granularity_frames )
+		{
+		std::cout << "Audio::stereo_spatialize: a moving source needs more than 32 frames, the result would have none." << std::endl;
+		return Audio();
+		}
+	const float * d_x = device_data();
+	if( !d_x ) return Audio::create_null();                                        // without a device nothing is sampled
+	// head_ild's low-pass (:128) is the same for both ears: once
+	DeviceCurve cutoff;
+	cutoff.scalar = 500;
+	const Audio lowpassed = filter_cascade( *this, cutoff, FLANHIP_FILTER_BUTTERWORTH_LOW, 1, "stereo_spatialize" );
+	if( lowpassed.is_null() ) return Audio::create_null();
+	auto shaped = detail::DeviceBlock::allocate( sizeof( float ) * 2 * size_t( n ) );
+	if( !shaped ) return Audio::create_null();
+	const vec2d ear_position[2] = { vec2d( 0, 1 * head_width / 2.0f ), vec2d( 0, -1 * head_width / 2.0f ) };    // :261, the left ear first
+	AudioBuffer::Format f = get_format();
+	f.num_channels = 2;
+	int64_t out_frames[2] = { 0, 0 };
+
+	if( position.is_constant() )
+		{
+		// :139-153: both ears a pure delay.  head_ild and falloff see one position (:263, the transform of a constant)
+		const vec2d p = vec2d( position.get_constant() );                          // :235
+		float delays[2];
+		for( int e = 0; e < 2; ++e )
+			{
+			const Meter dist = ( p - ear_position[e] ).mag();                      // :141-142
+			delays[e] = time_to_frame( dist / sound_mps );                         // :143
+			out_frames[e] = Frame( n + delays[e] );                                // :148
+			}
+		f.num_frames = Frame( std::max( out_frames[0], out_frames[1] ) );
+		if( !detail::report( flanhip_spatial_ear_dev( d_x, lowpassed.device_data(), 1, n, sr, nullptr, p.x(), p.y(), head_width, FLANHIP_SPATIAL_BOTH,
+				static_cast<float*>( shaped->ptr ), nullptr ), "stereo_spatialize" ) ) return Audio::create_null();
+		auto block = detail::DeviceBlock::allocate( sizeof( float ) * 2 * size_t( f.num_frames ) );
+		if( !block ) return Audio::create_null();
+		if( !detail::report( flanhip_spatial_delay_dev( static_cast<const float*>( shaped->ptr ), 2, n, delays, out_frames, f.num_frames,
+				static_cast<float*>( block->ptr ), nullptr ), "stereo_spatialize" ) ) return Audio::create_null();
+		if( !detail::report( flanhip_stream_synchronize( nullptr ), "stereo_spatialize" ) ) return Audio::create_null();
+		return AudioBuffer::adopt_device( f, std::move( block ) );                 // combine_channels( l, r ) (:280): the longer ear's length
+		}
+
+	// :235: the position once per frame, as doubles
+	detail::StagingVector<double> ps( 2 * size_t( n ) );
+	{
+	const float step = 1.0f / sr;
+	detail::for_each_index( 0, n, position.get_execution_policy(), [&]( int x )
+		{
+		const vec2 v = position( Second( x * step ) );
+		ps[2 * size_t( x )] = v.x(); ps[2 * size_t( x ) + 1] = v.y();
+		} );
+	}
+	// :238-257: the speed limiter.  It stays on the host: frame f needs the LIMITED frame f - 1, the step is not linear in it (a division by the
+	// movement's length), so no scan composes it; it is one pass over 16 n bytes
+	{
+	const float epsilon = 1;
+	const auto limit = speed_limit.sample( 0, n, 1.0f / sr );                      // :246
+	for( Frame frame = 1; frame < n; ++frame )
+		{
+		const vec2d previous( ps[2 * size_t( frame ) - 2], ps[2 * size_t( frame ) - 1] );
+		const vec2d movement = vec2d( ps[2 * size_t( frame )], ps[2 * size_t( frame ) + 1] ) - previous;
+		const Meter mag = movement.mag();
+		const float limit_here = limit.is_constant() ? limit.get_constant() : limit.get_vector()[size_t( frame )];
+		const float speed_limit_c = std::clamp( limit_here, 0.0f, sound_mps - epsilon ) / sr;        // :253
+		if( mag > speed_limit_c )
+			{
+			const vec2d limited = previous + movement / mag * speed_limit_c;       // :255
+			ps[2 * size_t( frame )] = limited.x(); ps[2 * size_t( frame ) + 1] = limited.y();
+			}
+		}
+	}
+	// :159-186 per ear: the distances at frames 0, 32, ... give the stretches and the output length
+	const int64_t count = ( int64_t( n ) + granularity_frames - 1 ) / granularity_frames;
+	const size_t chunks = size_t( count );
+	std::vector<double> distances( chunks ), stretches( 2 * chunks );
+	for( int e = 0; e < 2; ++e )
+		{
+		for( int64_t k = 0; k < count; ++k )
+			distances[size_t( k )] = ( vec2d( ps[2 * size_t( k ) * granularity_frames], ps[2 * size_t( k ) * granularity_frames + 1] ) - ear_position[e] ).mag();
+		out_frames[e] = flanhip_spatial_itd_out_frames( n, sr, distances.data(), count, stretches.data() + size_t( e ) * size_t( count ) );
+		if( out_frames[e] < 0 ) { detail::report( int( out_frames[e] ), "stereo_spatialize" ); return Audio::create_null(); }
+		}
+	f.num_frames = Frame( std::min<int64_t>( std::max( out_frames[0], out_frames[1] ), std::numeric_limits<Frame>::max() ) );
+	const size_t ws_bytes = flanhip_spatial_itd_workspace_bytes( 2, n, sr, stretches.data(), count );
+	if( f.num_frames <= 0 || ws_bytes == 0 )
+		{
+		std::cerr << "flan: stereo_spatialize refused " << n << " frames: ";
+		if( ws_bytes == 0 ) std::cerr << flanhip_last_error(); else std::cerr << "no output frames";
+		std::cerr << std::endl;
+		return Audio::create_null();
+		}
+	auto d_ps = detail::DeviceBlock::allocate( sizeof( double ) * ps.size() );
+	auto block = detail::DeviceBlock::allocate( sizeof( float ) * 2 * size_t( f.num_frames ) );
+	auto ws = detail::DeviceBlock::allocate( ws_bytes );
+	if( !d_ps || !block || !ws ) return Audio::create_null();
+	if( !detail::upload_from_host( d_ps->ptr, ps.data(), sizeof( double ) * ps.size() ) )
+		{
+		std::cerr << "flan: upload of the sampled positions failed: " << flanhip_last_error() << std::endl;
+		return Audio::create_null();
+		}
+	if( !detail::report( flanhip_spatial_ear_dev( d_x, lowpassed.device_data(), 1, n, sr, static_cast<const double*>( d_ps->ptr ), 0.0, 0.0, head_width,
+			FLANHIP_SPATIAL_BOTH, static_cast<float*>( shaped->ptr ), nullptr ), "stereo_spatialize" ) ) return Audio::create_null();
+	if( !detail::report( flanhip_spatial_itd_dev( static_cast<const float*>( shaped->ptr ), 2, n, sr, stretches.data(), count, out_frames, f.num_frames,
+			static_cast<float*>( block->ptr ), ws->ptr, nullptr ), "stereo_spatialize" ) ) return Audio::create_null();
+	if( !detail::report( flanhip_stream_synchronize( nullptr ), "stereo_spatialize" ) ) return Audio::create_null();     // the workspace and the positions go back idle
+	return AudioBuffer::adopt_device( f, std::move( block ) );                     // combine_channels( l, r ) (:280): the longer ear's length
 	}
 
 } // namespace flan

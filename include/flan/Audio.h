@@ -3,11 +3,14 @@
 #pragma once
 #include <complex>
 #include <cstdint>
+#include <limits>
+#include <type_traits>
 #include <vector>
 
 #include "flan/AudioBuffer.h"
 #include "flan/Function.h"
 #include "flan/defines.h"
+#include "flan/vec2.h"
 
 namespace flan {
 
@@ -190,6 +193,55 @@ public:
 	 *  and the product in one pass).  The result has this Audio's sample rate.  A null *this or a null modulator (which the reference
 	 *  dereferences) gives a null Audio.  The result stays device-resident until read. */
 	Audio halfband_multiply( const Audio & modulator ) const;
+
+	// ---- channels ----
+	/** Mono to stereo (Audio/AudioConversions.cpp:58-85): both channels the input / sqrt( 2.0f ), on the device (flanhip_audio_to_stereo_dev;
+	 *  DESIGN.md 4.20).  A stereo input is copied; any other channel count prints the reference's message and gives two silent channels, as
+	 *  the reference's zero-initialised output does.  A null *this gives a null Audio.  The result stays device-resident until read. */
+	Audio convert_to_stereo() const;
+	/** The mean over the channels (:87-104): the channels added in order in fp32, divided by their number (flanhip_audio_to_mono_dev). */
+	Audio convert_to_mono() const;
+	/** One mono Audio per channel (Audio/AudioChannels.cpp:13-29), device-to-device copies (flanhip_audio_copy_rows_dev).  A null *this gives
+	 *  an empty vector. */
+	std::vector<Audio> split_channels() const;
+	/** All channels of all inputs in order (:31-67): the longest input's length, zeros behind the shorter ones, device-to-device copies.
+	 *  Inputs of other sample rates are first resampled to the highest one (Audio::resample), all of them as the reference does.  No inputs,
+	 *  a null pointer or a null Audio among them (which the reference does not guard against) give a null Audio. */
+	static Audio combine_channels( const std::vector<const Audio *> & channels );
+	static Audio combine_channels( const std::vector<Audio> & channels );
+	template<typename ... Ts, typename = std::enable_if_t<( std::is_same_v<Ts, Audio> && ... )>>
+	static Audio combine_channels( const Ts & ... ins )
+		{
+		std::vector<const Audio *> p_ins;
+		( p_ins.push_back( &ins ), ... );
+		return combine_channels( p_ins );
+		}
+
+	// ---- spatial ----
+	/** Constant-power panning (Audio/AudioSpatial.cpp:9-40): channel 0 times sine2( p ), channel 1 times sine2( 1 - p ), p = pan_amount( t ) /
+	 *  2.0f + 0.5f, sine2( x ) = sqrt( 2 ) sin( pi / 4 x ) (Interpolator::sine2 with the double sin the reference's compiler picks), on the
+	 *  device (flanhip_audio_pan_dev).  pan_amount in [-1, 1] (at -1 channel 0 is silent, at 1 channel 1) is sampled once per frame at f * ( 1.0f / sample rate );
+	 *  a constant samples nothing.  A mono input is first convert_to_stereo(); more than two channels and a null *this give a null Audio.  The
+	 *  result stays device-resident until read. */
+	Audio pan( const Function<Second, float> & pan_amount ) const;
+	/** pan on *this (:21-40): anything but stereo is left as it is, a null *this prints "Null input".  Computes into a fresh block and takes
+	 *  it over. */
+	Audio & pan_in_place( const Function<Second, float> & pan_amount );
+	/** convert_to_mid_side().pan( widen_amount ).convert_to_left_right() (:42-45) */
+	Audio widen( const Function<Second, float> & widen_amount ) const;
+	/** A mono source moving in the plane, heard by two ears head_width apart on the y axis, the left one at +y (:88-281).  Per ear: the input
+	 *  blended with its filter_1pole_lowpass( 500, 1 ) by the angle between the source and the ear's axis (75 degrees off the nose), times
+	 *  1 / ( distance + 0.00001 ), then delayed by distance / 343 seconds -- a delay that follows the source, so the ear hears Doppler: the
+	 *  reference's WDL sinc resampler in feed mode, 32 taps, a new rate every 32 frames.  On the device (flanhip_spatial_ear_dev,
+	 *  flanhip_spatial_itd_dev); sampling the Functions, the speed limiter and the resampler's block plan are host work.
+	 *  position is sampled once per frame at f * ( 1.0f / sample rate ); unless it is a constant its speed is limited to clamp( speed_limit( t ),
+	 *  0, 342 ) metres per second, a sequential recurrence in fp64.  A constant position is a pure delay of Frame( n + delay ) frames in all
+	 *  (:139-153).  The result has two channels and the longer ear's length; the resampler is never flushed, so the last 17 to 33 input frames
+	 *  are not heard.  A non-mono input prints the reference's message and gives a null Audio.  Where the reference makes a zero-frame Audio -- a
+	 *  moving source and 32 frames or fewer -- this gives a null Audio and one line on std::cout, before anything is sampled: an Audio
+	 *  without frames is a null Audio here.  The result stays device-resident until read. */
+	Audio stereo_spatialize( const Function<Second, vec2> & position, Meter head_width = 0.18f,
+		const Function<Second, float> & speed_limit = std::numeric_limits<float>::max() ) const;
 
 	// the older camelCase spellings BASELINE.json's north_star uses
 	PV convertToPV( Frame window_size = 2048, Frame hop = 128, Frame dft_size = 4096, flan_CANCEL_ARG ) const;

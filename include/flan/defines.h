@@ -12,6 +12,7 @@ using Channel = int32_t;    using Frame = int32_t;      using Bin = int32_t;    
 using fFrame = float;       using fBin = float;         // fractional frame / bin positions
 using Second = float;       using Sample = float;       using Frequency = float;    using Magnitude = float;
 using FrameRate = float;    using Radian = float;        using Decibel = float;      using Amplitude = float;
+using Meter = float;
 
 struct MF { Magnitude m; Frequency f; };   // defines.h:31-35
 struct TF { Second t; Frequency f; };      // defines.h:37-41

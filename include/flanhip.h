@@ -793,6 +793,91 @@ int flanhip_halfband_multiply_dev(const float * d_a, int64_t channels_a, int64_t
                                   const float * d_b, int64_t channels_b, int64_t frames_b, float sample_rate_b,
                                   float * d_out, void * d_workspace, void * stream);
 
+/* ---- Audio::stereo_spatialize (Audio/AudioSpatial.cpp:88-281): a mono source moving in the plane, rendered per ear
+ * (flan_amd/csrc/spatial.hip) ------------------------------------------------------------------------------------- */
+/* head_ild (:116-131) and falloff (:104-114) for one ear or both.  audio: float[n], mono (any other num_channels is
+ * FLANHIP_ERR_INVALID_ARG); lowpassed: float[n], the audio through filter_1pole_lowpass( 500, 1 ) (flanhip_filter_1pole_dev; the same
+ * for both ears); positions: double[n][2], the source's ( x, y ) per frame after the speed limiter (:238-257), or NULL for the constant
+ * ( position_x, position_y ); out: float[1 or 2][n], with FLANHIP_SPATIAL_BOTH the left ear first.  Per frame f and ear, in the
+ * reference's types and order, one rounding per operation and no fused multiply-add:
+ *   q     = int( ( f * ( 1.0f / sr ) ) * sr ) in fp32 -- the frame the reference's callables read the weight and the distance at
+ *           (FunctionSample.h:130-133, :109): f, or for some f, f - 1
+ *   rel   = positions[q] - ( 0, +- head_width / 2.0f ) in fp64, + for the left ear (:261-263)
+ *   mix   = 0.5f + 0.5f * cosf( atan2f( float( rel.y ), float( rel.x ) ) - direct ), direct = +- 75.0f * pi2 / 360.0f (:120-122, :276-277)
+ *   out   = ( lowpassed[f] * ( 1.0f - mix ) + audio[f] * mix ) * ( 1.0f / ( float( |rel| ) + 0.00001f ) ) (:129-130, :112)
+ * atan2f and cosf are the device's.  Null audio / lowpassed / out, a non-positive size, sample_rate <= 0, a NaN head_width and an unknown
+ * `ears` are FLANHIP_ERR_INVALID_ARG, before any device call. */
+#define FLANHIP_SPATIAL_LEFT  1
+#define FLANHIP_SPATIAL_RIGHT 2
+#define FLANHIP_SPATIAL_BOTH  3
+int flanhip_spatial_ear(const float * audio, const float * lowpassed, int64_t num_channels, int64_t num_frames, float sample_rate,
+                        const double * positions, double position_x, double position_y, float head_width, int ears,
+                        float * out, volatile int * cancel);
+int flanhip_spatial_ear_dev(const float * d_audio, const float * d_lowpassed, int64_t num_channels, int64_t num_frames, float sample_rate,
+                            const double * d_positions, double position_x, double position_y, float head_width, int ears,
+                            float * d_out, void * stream);
+/* head_itd for a source that stands still (:139-153): out[e][ Frame( frame + delays[e] ) ] = audio[e][frame], the index formed in fp32
+ * as the reference forms it, everything else 0.  d_audio: float[ears][n]; delays and out_frames: HOST arrays, one per ear (the delay in
+ * frames, time_to_frame( dist / 343 ), and the ear's output length Frame( n + delay )); d_out: float[ears][out_stride], each row zero
+ * past what is written.  Where two frames land on one index (above 2^24 frames) the later one stays, as in the reference's loop. */
+int flanhip_spatial_delay_dev(const float * d_audio, int64_t num_ears, int64_t num_frames, const float * delays, const int64_t * out_frames,
+                              int64_t out_stride, float * d_out, void * stream);
+/* head_itd for a moving source (:155-221): the reference feeds a WDL_Resampler (SetMode( true, 0, true, 32 ), SetFeedMode( true ))
+ * 32 input frames per block at the rate sr -> sr * stretches[block], and every block delivers what the resampler can give: a number of
+ * output frames that depends on the data.  The hand-over between blocks -- the fractional read position and the samples that stay
+ * buffered -- is reproduced exactly by a host loop in fp64 (flanhip_spatial_itd_plan; one addition per output frame); the samples are
+ * computed on the device, one 2 x 32-tap sum each (1 x 32 where the rates are "ideal", WDL/resample.cpp:1095-1141) against a
+ * Blackman-Harris x sinc table the kernel builds per run of blocks with the same ( filtpos, oversize ).  Products are fp32, sums fp64 in
+ * tap order; within a block the read position is fma( j, ratio, fracpos ), not j additions.  The reference never flushes the resampler:
+ * the last 33 or so input frames are not heard.  Deterministic (two calls agree bit for bit).
+ * count = ceil( n / 32 ) everywhere: any other count is FLANHIP_ERR_INVALID_ARG, like null pointers, non-positive sizes, sample_rate <= 0,
+ * more than two ears and a stretch that is not a number or outside [1/16, 1024] (the method's own stay within ( 1/2, 343 ]).  More than
+ * 2^22 blocks or 2^33 output frames per ear are FLANHIP_ERR_UNSUPPORTED. */
+/* :159-186 from the source's distances (metres, fp64) at frames 0, 32, 64, ...: returns the output length ceil( time_to_frame(
+ * max_needed_length ) ) with the reference's float / double mix (0 for n <= 32), or a negative FLANHIP_ERR_*; stretches (may be NULL):
+ * double[count], 1 / ( 1 - change / 32 / 343 * sr ).  Host arithmetic. */
+int64_t flanhip_spatial_itd_out_frames(int64_t num_frames, float sample_rate, const double * distances, int64_t count, double * stretches);
+/* The block loop alone (host arithmetic, no device): returns the number of blocks (or a negative FLANHIP_ERR_*) and fills the first
+ * `capacity` records of every array that is not null: the stream index of the resampler buffer's first sample (the stream: 15 zeros,
+ * the input, zeros), srcpos of the block's first output frame relative to it, the ratio, the table's filtpos / oversize / ideal flag, the
+ * block's first output frame, the frames it delivers, and the samples buffered while it runs (15 + 32 in the first block, then 66 at
+ * most; 64 to 66 for the method's own stretches).  *total_out: the frames all blocks deliver together. */
+int64_t flanhip_spatial_itd_plan(int64_t num_frames, float sample_rate, const double * stretches, int64_t count, int64_t capacity,
+                                 int64_t * offsets, double * fracpos, double * ratio, double * filtpos, int32_t * oversize, int32_t * ideal,
+                                 int64_t * first_out, int32_t * delivered, int32_t * buffered, int64_t * total_out);
+/* bytes of device workspace flanhip_spatial_itd_dev needs (host arithmetic: it runs the plans; 0 for arguments it refuses): the window
+ * factors (64 x 1040 doubles), 56 bytes per block of every ear and 64 per run.  stretches: double[ears][count]. */
+size_t flanhip_spatial_itd_workspace_bytes(int64_t num_ears, int64_t num_frames, float sample_rate, const double * stretches, int64_t count);
+/* audio: float[ears][n], each ear's own input; stretches: double[ears][count] and out_frames: int64[ears], both HOST memory (the plans run
+ * on the host); out: float[ears][out_stride].  Ear e keeps output frames below out_frames[e] <= out_stride (:213-215); frames no block
+ * reaches, and the rest of the row, are 0.  Both ears run in one launch and each is what it would be alone.  The workspace need not be
+ * cleared; the records go up before the launch and the stream is synchronised once for that.  `cancel` is polled before the upload and
+ * before the launch. */
+int flanhip_spatial_itd(const float * audio, int64_t num_ears, int64_t num_frames, float sample_rate, const double * stretches, int64_t count,
+                        const int64_t * out_frames, int64_t out_stride, float * out, volatile int * cancel);
+int flanhip_spatial_itd_dev(const float * d_audio, int64_t num_ears, int64_t num_frames, float sample_rate, const double * stretches,
+                            int64_t count, const int64_t * out_frames, int64_t out_stride, float * d_out, void * d_workspace, void * stream);
+
+/* ---- Audio::pan_in_place (Audio/AudioSpatial.cpp:21-40), convert_to_stereo / convert_to_mono (Audio/AudioConversions.cpp:58-104),
+ * combine_channels / split_channels (Audio/AudioChannels.cpp) ------------------------------------------------------------------- */
+/* audio, out: float[2][n] (any other num_channels is FLANHIP_ERR_INVALID_ARG); out may be the audio.  pan: a curve of n floats in [-1, 1]
+ * or, with a NULL curve, the scalar.  p = pan[f] / 2.0f + 0.5f; channel 0 times sine2( p ), channel 1 times sine2( 1.0f - p ), with
+ * sine2( x ) = float( double( sqrtf( 2 ) ) * sin( double( pi / 4.0f * x ) ) ) (Utility/Interpolator.cpp:85-91: the unqualified sin is the
+ * double one there).  One fp32 product per sample. */
+int flanhip_audio_pan(const float * audio, int64_t num_channels, int64_t num_frames, const float * pan_curve, float pan,
+                      float * out, volatile int * cancel);
+int flanhip_audio_pan_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, const float * d_pan, float pan,
+                          float * d_out, void * stream);
+/* :68-77: mono float[n] -> float[2][n], both channels s / sqrt( 2.0f ) */
+int flanhip_audio_to_stereo_dev(const float * d_audio, int64_t num_frames, float * d_out, void * stream);
+/* :87-104: float[ch][n] -> float[n], the channels added in order from 0.0f in fp32, the sum divided by float( ch ) */
+int flanhip_audio_to_mono_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, float * d_out, void * stream);
+/* num_rows rows of src_frames floats, src_stride apart, copied to rows dst_stride apart; every destination row is dst_frames >=
+ * src_frames long and zero behind the copy.  combine_channels copies each input's channels into its rows of the output this way,
+ * split_channels each channel into a buffer of its own.  The buffers must not overlap. */
+int flanhip_audio_copy_rows_dev(const float * d_src, int64_t src_stride, int64_t num_rows, int64_t src_frames,
+                                float * d_dst, int64_t dst_stride, int64_t dst_frames, void * stream);
+
 /* ---- Audio::resample (Audio/AudioConversions.cpp:14-30, r8brain CDSPResampler with default parameters) --------- */
 /* AudioConversions.cpp:22: out frames = Frame( float(num_frames) * ( dst_rate / src_rate ) ) */
 int64_t flanhip_resample_out_frames(int64_t num_frames, float src_rate, float dst_rate);
