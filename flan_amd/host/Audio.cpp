@@ -8,105 +8,93 @@
 #include <cmath>
 #include <iostream>
 
-#include "device_block.h"
+#include "device_call.h"
 #include "flan/PV.h"
 
 namespace flan {
 
 namespace {
+using detail::DeviceArg;
+using detail::DeviceCall;
 
-// A Function of time as the device entry points take it: a constant goes as the scalar and samples nothing; a callable is sampled once
-// per frame at x * scale (Function::sample's arithmetic, Function.h:141-153) into a page-locked block and uploaded.
-struct DeviceCurve
-	{
-	std::shared_ptr<detail::DeviceBlock> block;
-	float scalar = 0.0f;
-	bool ok = true;
-	const float * ptr() const { return block ? static_cast<const float*>( block->ptr ) : nullptr; }
-	};
-
-// time_of( x ): the time frame x is sampled at
+// A Function of time for the device (detail::DeviceArg): a constant goes as the scalar and samples nothing; a callable is sampled once per
+// frame (Function::sample's arithmetic, Function.h:141-153) into a page-locked block and uploaded.  time_of( x ): the time frame x is sampled at
 template<typename TimeOf>
-DeviceCurve upload_curve_at( const Function<Second, float> & fn, Frame n, TimeOf time_of )
+DeviceArg upload_curve_at( const Function<Second, float> & fn, Frame n, TimeOf time_of )
 	{
-	DeviceCurve c;
-	if( fn.is_constant() ) { c.scalar = fn.get_constant(); return c; }
+	if( fn.is_constant() ) return DeviceArg( fn.get_constant() );
 	detail::StagingVector<float> sampled( size_t( std::max( n, 0 ) ) );
 	detail::for_each_index( 0, n, fn.get_execution_policy(), [&]( int x ){ sampled[size_t( x )] = fn( time_of( x ) ); } );
-	c.block = detail::DeviceBlock::allocate( sizeof( float ) * sampled.size() );
-	c.ok = c.block && detail::upload_from_host( c.block->ptr, sampled.data(), sizeof( float ) * sampled.size() );
-	if( c.block && !c.ok ) std::cerr << "flan: upload of a sampled Function failed: " << flanhip_last_error() << std::endl;
-	return c;
+	return DeviceArg::from_host( sampled.data(), sizeof( float ) * sampled.size(), "a sampled Function" );
 	}
 
-DeviceCurve upload_curve( const Function<Second, float> & fn, Frame n, float scale )
+DeviceArg upload_curve( const Function<Second, float> & fn, Frame n, float scale )
 	{
 	return upload_curve_at( fn, n, [scale]( int x ){ return Second( x * scale ); } );
 	}
 
-// One cascade of flanhip_filter2_dev over `me` with its three arguments already on the device (or scalars): a fresh device block
-Audio filter2_cascade( const Audio & me, const DeviceCurve & cutoff, const DeviceCurve & damping, const DeviceCurve & gain, int kind, uint16_t order,
+// host values as a curve on the device
+DeviceArg upload_values( const detail::StagingVector<float> & values )
+	{
+	return DeviceArg::from_host( values.data(), sizeof( float ) * values.size(), "a curve" );
+	}
+
+// what the skeleton could not make is the reference's null Audio, with its line on stdout
+Audio or_null( AudioBuffer && out )
+	{
+	if( out.is_null() ) return Audio::create_null();
+	return Audio( std::move( out ) );
+	}
+
+// One launch( out, ws ) into a fresh block of format f (detail::device_call)
+template<typename Launch>
+Audio audio_call( const char * who, const AudioBuffer::Format & f, bool have, size_t ws_bytes, Launch launch )
+	{
+	return or_null( detail::device_call<AudioBuffer, float>( who, f, size_t( f.num_channels ) * size_t( f.num_frames ), have, ws_bytes, launch ) );
+	}
+
+// What the three cascades below share: null in, null out (AudioFilter.cpp:287, :376, :385); a shape the C ABI refuses (no workspace) is a null
+// too, before the data is asked onto the device; then one launch( d_x, out, ws ) over `me` into a fresh block of its format
+template<typename Launch>
+Audio cascade_call( const Audio & me, size_t ws_bytes, bool have, const char * who, Launch launch )
+	{
+	if( me.is_null() || ws_bytes == 0 ) return Audio::create_null();
+	const float * d_x = me.device_data();
+	if( !d_x ) return Audio::create_null();
+	return audio_call( who, me.get_format(), have, ws_bytes, [&]( float * out, void * ws ){ return launch( d_x, out, ws ); } );
+	}
+
+// One cascade of flanhip_filter2_dev over `me` with its three arguments already on the device (or scalars)
+Audio filter2_cascade( const Audio & me, const DeviceArg & cutoff, const DeviceArg & damping, const DeviceArg & gain, int kind, uint16_t order,
 	const char * who )
 	{
-	if( me.is_null() ) return Audio::create_null();
-	const size_t ws_bytes = flanhip_filter2_workspace_bytes( me.get_num_channels(), me.get_num_frames() );
-	if( ws_bytes == 0 ) return Audio::create_null();
-	const float * d_x = me.device_data();
-	if( !d_x ) return Audio::create_null();
-	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( me.get_num_channels() ) * size_t( me.get_num_frames() ) );
-	auto ws = detail::DeviceBlock::allocate( ws_bytes );
-	if( !cutoff.ok || !damping.ok || !gain.ok || !block || !ws ) return Audio::create_null();
-	const int rc = flanhip_filter2_dev( d_x, me.get_num_channels(), me.get_num_frames(), me.get_sample_rate(), cutoff.ptr(), cutoff.scalar,
-		damping.ptr(), damping.scalar, gain.ptr(), gain.scalar, kind, int( order ), static_cast<float*>( block->ptr ), ws->ptr, nullptr );
-	if( !detail::report( rc, who ) ) return Audio::create_null();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), who ) ) return Audio::create_null();                 // the workspace and the curves go back idle
-	return AudioBuffer::adopt_device( me.get_format(), std::move( block ) );
+	return cascade_call( me, flanhip_filter2_workspace_bytes( me.get_num_channels(), me.get_num_frames() ), cutoff.ok && damping.ok && gain.ok, who,
+		[&]( const float * d_x, float * out, void * ws )
+		{
+		return flanhip_filter2_dev( d_x, me.get_num_channels(), me.get_num_frames(), me.get_sample_rate(), cutoff.ptr(), cutoff.scalar,
+			damping.ptr(), damping.scalar, gain.ptr(), gain.scalar, kind, int( order ), out, ws, nullptr );
+		} );
 	}
 
-// One cascade of flanhip_filter_1pole_dev over `me` with a cutoff already on the device (or a scalar): a fresh device block
-Audio filter_cascade( const Audio & me, const DeviceCurve & cutoff, int kind, uint16_t order, const char * who )
+// One cascade of flanhip_filter_1pole_dev over `me` with a cutoff already on the device (or a scalar)
+Audio filter_cascade( const Audio & me, const DeviceArg & cutoff, int kind, uint16_t order, const char * who )
 	{
-	if( me.is_null() ) return Audio::create_null();             // AudioFilter.cpp:287, :376, :385
-	const size_t ws_bytes = flanhip_filter_1pole_workspace_bytes( me.get_num_channels(), me.get_num_frames() );
-	if( ws_bytes == 0 ) return Audio::create_null();
-	const float * d_x = me.device_data();
-	if( !d_x ) return Audio::create_null();
-	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( me.get_num_channels() ) * size_t( me.get_num_frames() ) );
-	auto ws = detail::DeviceBlock::allocate( ws_bytes );
-	if( !cutoff.ok || !block || !ws ) return Audio::create_null();
-	const int rc = flanhip_filter_1pole_dev( d_x, me.get_num_channels(), me.get_num_frames(), me.get_sample_rate(), cutoff.ptr(), cutoff.scalar,
-		kind, int( order ), static_cast<float*>( block->ptr ), ws->ptr, nullptr );
-	if( !detail::report( rc, who ) ) return Audio::create_null();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), who ) ) return Audio::create_null();                 // the workspace and the curve go back idle
-	return AudioBuffer::adopt_device( me.get_format(), std::move( block ) );
-	}
-
-// host values as a curve on the device
-DeviceCurve upload_values( const detail::StagingVector<float> & values )
-	{
-	DeviceCurve c;
-	c.block = detail::DeviceBlock::allocate( sizeof( float ) * values.size() );
-	c.ok = c.block && detail::upload_from_host( c.block->ptr, values.data(), sizeof( float ) * values.size() );
-	if( c.block && !c.ok ) std::cerr << "flan: upload of a curve failed: " << flanhip_last_error() << std::endl;
-	return c;
+	return cascade_call( me, flanhip_filter_1pole_workspace_bytes( me.get_num_channels(), me.get_num_frames() ), cutoff.ok, who,
+		[&]( const float * d_x, float * out, void * ws )
+		{
+		return flanhip_filter_1pole_dev( d_x, me.get_num_channels(), me.get_num_frames(), me.get_sample_rate(), cutoff.ptr(), cutoff.scalar, kind, int( order ), out, ws, nullptr );
+		} );
 	}
 
 // flanhip_halfband_modulate_dev over `me` with the modulator already on the device (re and im, or the phase that stands for both)
-Audio halfband_modulated( const Audio & me, const DeviceCurve & re, const DeviceCurve & im, const DeviceCurve * phase, const char * who )
+Audio halfband_modulated( const Audio & me, const DeviceArg & re, const DeviceArg & im, const DeviceArg * phase, const char * who )
 	{
-	if( me.is_null() ) return Audio::create_null();
-	const size_t ws_bytes = flanhip_halfband_workspace_bytes( me.get_num_channels(), me.get_num_frames() );
-	if( ws_bytes == 0 ) return Audio::create_null();
-	const float * d_x = me.device_data();
-	if( !d_x ) return Audio::create_null();
-	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( me.get_num_channels() ) * size_t( me.get_num_frames() ) );
-	auto ws = detail::DeviceBlock::allocate( ws_bytes );
-	if( !re.ok || !im.ok || ( phase && ( !phase->ok || !phase->ptr() ) ) || !block || !ws ) return Audio::create_null();
-	const int rc = flanhip_halfband_modulate_dev( d_x, me.get_num_channels(), me.get_num_frames(), me.get_sample_rate(), re.ptr(), re.scalar,
-		im.ptr(), im.scalar, phase ? phase->ptr() : nullptr, static_cast<float*>( block->ptr ), ws->ptr, nullptr );
-	if( !detail::report( rc, who ) ) return Audio::create_null();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), who ) ) return Audio::create_null();                 // the workspace and the curves go back idle
-	return AudioBuffer::adopt_device( me.get_format(), std::move( block ) );
+	return cascade_call( me, flanhip_halfband_workspace_bytes( me.get_num_channels(), me.get_num_frames() ), re.ok && im.ok && ( !phase || ( phase->ok && phase->ptr() ) ), who,
+		[&]( const float * d_x, float * out, void * ws )
+		{
+		return flanhip_halfband_modulate_dev( d_x, me.get_num_channels(), me.get_num_frames(), me.get_sample_rate(), re.ptr(), re.scalar,
+			im.ptr(), im.scalar, phase ? phase->ptr() : nullptr, out, ws, nullptr );
+		} );
 	}
 
 } // namespace
@@ -156,26 +144,19 @@ PV Audio::convert_to_PV( Frame window_size, Frame hop, Frame dft_size, flan_CANC
 
 	const float * d_audio = device_data();
 	if( !d_audio ) return PV();
-	auto block = detail::DeviceBlock::allocate( sizeof( MF ) * size_t( f.num_channels ) * f.num_frames * f.num_bins );
-	if( !block ) return PV();
+	DeviceCall call( "convert_to_PV" );
+	flanhip_MF * d_pv = call.output<flanhip_MF>( size_t( f.num_channels ) * f.num_frames * f.num_bins );
+	if( !d_pv ) return PV();
 	if( canceller ) return PV();
-	// fused round trip: the analysis kernel also leaves what convert_to_audio's pre-pass would compute (flanhip.h)
-	std::shared_ptr<detail::DeviceBlock> ws;
-	const size_t ws_bytes = flanhip_synthesize_workspace_bytes( f.num_channels, f.num_frames, f.num_bins, f.sample_rate, f.analysis_rate, f.window_size );
-	if( ws_bytes ) ws = detail::DeviceBlock::allocate( ws_bytes );
-	const int rc = ws
-		? flanhip_analyze_dev_fused( d_audio, f.num_channels, get_num_frames(), get_sample_rate(), window_size, hop, dft_size,
-			static_cast<flanhip_MF*>( block->ptr ), ws->ptr, nullptr )
-		: flanhip_analyze_dev( d_audio, f.num_channels, get_num_frames(), get_sample_rate(), window_size, hop, dft_size,
-			static_cast<flanhip_MF*>( block->ptr ), nullptr );
-	if( !detail::report( rc, "convert_to_PV" ) ) return PV();
+	// fused round trip: with a workspace the analysis kernel also leaves what convert_to_audio's pre-pass would compute (flanhip.h)
+	void * ws = call.workspace( flanhip_synthesize_workspace_bytes( f.num_channels, f.num_frames, f.num_bins, f.sample_rate, f.analysis_rate, f.window_size ), true );
+	const bool launched = call.launch( ws
+		? flanhip_analyze_dev_fused( d_audio, f.num_channels, get_num_frames(), get_sample_rate(), window_size, hop, dft_size, d_pv, ws, nullptr )
+		: flanhip_analyze_dev( d_audio, f.num_channels, get_num_frames(), get_sample_rate(), window_size, hop, dft_size, d_pv, nullptr ) );
+	if( !launched ) return PV();
 	// flan_CANCEL_POINT while the kernels run: the flag is polled during the wait and stops the launch (flanhip_wait_cancellable_fn)
-	const int waited = flanhip_wait_cancellable_fn( nullptr, detail::poll_canceller, &canceller );
-	if( waited == FLANHIP_ERR_CANCELLED || canceller ) return PV();
-	if( !detail::report( waited, "convert_to_PV" ) ) return PV();
-	PVBuffer out = PVBuffer::adopt_device( f, std::move( block ) );
-	if( ws ) out.attach_synthesis_workspace( std::move( ws ) );
-	return out;
+	if( call.wait( canceller ) == FLANHIP_ERR_CANCELLED || canceller ) return PV();
+	return call.finish_fused<PVBuffer>( f );
 	}
 
 PV Audio::convertToPV( Frame window_size, Frame hop, Frame dft_size, flan_CANCEL_ARG_CPP ) const
@@ -199,12 +180,8 @@ Audio Audio::convert_to_mid_side() const
 		}
 	const float * d_in = device_data();
 	if( !d_in ) return Audio::create_null();
-	auto block = detail::DeviceBlock::allocate( sizeof( float ) * 2 * size_t( get_num_frames() ) );
-	if( !block ) return Audio::create_null();
-	if( !detail::report( flanhip_mid_side_dev( d_in, get_num_frames(), static_cast<float*>( block->ptr ), nullptr ), "convert_to_mid_side" ) )
-		return Audio::create_null();
-	flanhip_stream_synchronize( nullptr );
-	return AudioBuffer::adopt_device( get_format(), std::move( block ) );
+	return audio_call( "convert_to_mid_side", get_format(), true, detail::kNoWorkspace, [&]( float * out, void * )
+		{ return flanhip_mid_side_dev( d_in, get_num_frames(), out, nullptr ); } );
 	}
 
 Audio Audio::convert_to_left_right() const { return convert_to_mid_side(); }   // AudioConversions.cpp:53-56
@@ -218,13 +195,9 @@ Audio Audio::resample( FrameRate new_sample_rate ) const
 	f.sample_rate = new_sample_rate;
 	if( f.num_frames <= 0 ) return Audio::create_null();
 	const float * d_in = device_data();
-	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( f.num_channels ) * f.num_frames );
-	if( !d_in || !block ) return Audio::create_null();
 	// r8brain CDSPResampler with default parameters, one stream over the whole buffer (:25-27), whatever chain of stages it builds for the two rates
-	if( !detail::report( flanhip_resample_dev( d_in, get_num_channels(), get_num_frames(), get_sample_rate(), new_sample_rate,
-			static_cast<float*>( block->ptr ), nullptr ), "resample" ) ) return Audio::create_null();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "resample" ) ) return Audio::create_null();
-	return AudioBuffer::adopt_device( f, std::move( block ) );
+	return audio_call( "resample", f, d_in != nullptr, detail::kNoWorkspace, [&]( float * out, void * )
+		{ return flanhip_resample_dev( d_in, get_num_channels(), get_num_frames(), get_sample_rate(), new_sample_rate, out, nullptr ); } );
 	}
 
 Audio Audio::convolve( const Audio & ir, bool normalize ) const
@@ -247,14 +220,8 @@ Audio Audio::convolve( const Audio & ir, bool normalize ) const
 	const float * d_x = device_data();
 	const float * d_h = h.device_data();
 	if( !d_x || !d_h ) return Audio::create_null();
-	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( f.num_channels ) * size_t( f.num_frames ) );
-	auto ws = detail::DeviceBlock::allocate( ws_bytes );
-	if( !block || !ws ) return Audio::create_null();
-	const int rc = flanhip_convolve_dev( d_x, get_num_channels(), get_num_frames(), d_h, h.get_num_channels(), h.get_num_frames(),
-		get_sample_rate(), normalize ? 1 : 0, static_cast<float*>( block->ptr ), ws->ptr, nullptr );
-	if( !detail::report( rc, "convolve" ) ) return Audio::create_null();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "convolve" ) ) return Audio::create_null();   // the workspace goes back idle
-	return AudioBuffer::adopt_device( f, std::move( block ) );
+	return audio_call( "convolve", f, true, ws_bytes, [&]( float * out, void * ws )
+		{ return flanhip_convolve_dev( d_x, get_num_channels(), get_num_frames(), d_h, h.get_num_channels(), h.get_num_frames(), get_sample_rate(), normalize ? 1 : 0, out, ws, nullptr ); } );
 	}
 
 Audio Audio::repitch( const Function<Second, float> & factor, Second granularity, WDLResampleType quality ) const
@@ -289,14 +256,8 @@ Audio Audio::repitch( const Function<Second, float> & factor, Second granularity
 		}
 	const float * d_x = device_data();
 	if( !d_x ) return Audio::create_null();
-	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( f.num_channels ) * size_t( f.num_frames ) );
-	auto ws = detail::DeviceBlock::allocate( ws_bytes );
-	if( !block || !ws ) return Audio::create_null();
-	const int rc = flanhip_audio_repitch_dev( d_x, get_num_channels(), get_num_frames(), get_sample_rate(), inv.data(), int64_t( inv.size() ), g, q,
-		static_cast<float*>( block->ptr ), ws->ptr, nullptr );
-	if( !detail::report( rc, "repitch" ) ) return Audio::create_null();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "repitch" ) ) return Audio::create_null();     // the workspace goes back idle
-	return AudioBuffer::adopt_device( f, std::move( block ) );
+	return audio_call( "repitch", f, true, ws_bytes, [&]( float * out, void * ws )
+		{ return flanhip_audio_repitch_dev( d_x, get_num_channels(), get_num_frames(), get_sample_rate(), inv.data(), int64_t( inv.size() ), g, q, out, ws, nullptr ); } );
 	}
 
 Audio Audio::modify_volume( const Function<Second, float> & gain ) const
@@ -304,13 +265,9 @@ Audio Audio::modify_volume( const Function<Second, float> & gain ) const
 	if( is_null() ) return Audio::create_null();                // AudioVolume.cpp:9
 	const float * d_x = device_data();
 	if( !d_x ) return Audio::create_null();
-	const DeviceCurve g = upload_curve( gain, get_num_frames(), 1.0f / get_sample_rate() );     // :36
-	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( get_num_channels() ) * size_t( get_num_frames() ) );
-	if( !g.ok || !block ) return Audio::create_null();
-	const int rc = flanhip_audio_gain_dev( d_x, get_num_channels(), get_num_frames(), g.ptr(), g.scalar, static_cast<float*>( block->ptr ), nullptr );
-	if( !detail::report( rc, "modify_volume" ) ) return Audio::create_null();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "modify_volume" ) ) return Audio::create_null();   // the curve goes back idle
-	return AudioBuffer::adopt_device( get_format(), std::move( block ) );
+	const DeviceArg g = upload_curve( gain, get_num_frames(), 1.0f / get_sample_rate() );     // :36
+	return audio_call( "modify_volume", get_format(), g.ok, detail::kNoWorkspace, [&]( float * out, void * )
+		{ return flanhip_audio_gain_dev( d_x, get_num_channels(), get_num_frames(), g.ptr(), g.scalar, out, nullptr ); } );
 	}
 
 // the in-place forms compute into a fresh block and take it over: the block under *this may be shared (device_block())
@@ -327,16 +284,11 @@ Audio Audio::set_volume( const Function<Second, Amplitude> & level ) const
 	if( is_null() ) return Audio::create_null();                // :50
 	const float * d_x = device_data();
 	if( !d_x ) return Audio::create_null();
-	const DeviceCurve l = upload_curve( level, get_num_frames(), 1.0f / get_sample_rate() );
-	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( get_num_channels() ) * size_t( get_num_frames() ) );
-	auto ws = detail::DeviceBlock::allocate( flanhip_audio_set_volume_workspace_bytes( get_num_channels(), get_num_frames() ) );
-	if( !l.ok || !block || !ws ) return Audio::create_null();
-	// :63-66: the maximum, the m == 0 case and level( t ) / m are the device's
-	const int rc = flanhip_audio_set_volume_dev( d_x, get_num_channels(), get_num_frames(), get_sample_rate(), l.ptr(), l.scalar,
-		static_cast<float*>( block->ptr ), ws->ptr, nullptr );
-	if( !detail::report( rc, "set_volume" ) ) return Audio::create_null();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "set_volume" ) ) return Audio::create_null();      // the workspace goes back idle
-	return AudioBuffer::adopt_device( get_format(), std::move( block ) );
+	const DeviceArg l = upload_curve( level, get_num_frames(), 1.0f / get_sample_rate() );
+	// :63-66: the maximum, the m == 0 case and level( t ) / m are the device's (and so is the refusal of a shape: no 0 bytes reach the skeleton)
+	const size_t ws_bytes = std::max<size_t>( flanhip_audio_set_volume_workspace_bytes( get_num_channels(), get_num_frames() ), 1 );
+	return audio_call( "set_volume", get_format(), l.ok, ws_bytes, [&]( float * out, void * ws )
+		{ return flanhip_audio_set_volume_dev( d_x, get_num_channels(), get_num_frames(), get_sample_rate(), l.ptr(), l.scalar, out, ws, nullptr ); } );
 	}
 
 Audio & Audio::set_volume_in_place( const Function<Second, Amplitude> & level )
@@ -365,18 +317,14 @@ Audio Audio::compress( const Function<Second, Decibel> & threshold, const Functi
 	const float * d_side = side.device_data();
 	if( !d_x || !d_side ) return Audio::create_null();
 	const float step = frame_to_time( 1 );                       // :220-224
-	const DeviceCurve t = upload_curve( threshold, get_num_frames(), step ), r = upload_curve( compression_ratio, get_num_frames(), step ),
+	const DeviceArg t = upload_curve( threshold, get_num_frames(), step ), r = upload_curve( compression_ratio, get_num_frames(), step ),
 		a = upload_curve( attack, get_num_frames(), step ), rel = upload_curve( release, get_num_frames(), step ),
 		k = upload_curve( knee_width, get_num_frames(), step );
-	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( get_num_channels() ) * size_t( get_num_frames() ) );
-	auto ws = detail::DeviceBlock::allocate( ws_bytes );
-	if( !t.ok || !r.ok || !a.ok || !rel.ok || !k.ok || !block || !ws ) return Audio::create_null();
-	const int rc = flanhip_compress_dev( d_x, get_num_channels(), get_num_frames(), get_sample_rate(), d_side, side.get_num_channels(),
-		side.get_num_frames(), t.ptr(), t.scalar, r.ptr(), r.scalar, a.ptr(), a.scalar, rel.ptr(), rel.scalar, k.ptr(), k.scalar,
-		static_cast<float*>( block->ptr ), nullptr, ws->ptr, nullptr );
-	if( !detail::report( rc, "compress" ) ) return Audio::create_null();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "compress" ) ) return Audio::create_null();        // the workspace and the curves go back idle
-	return AudioBuffer::adopt_device( get_format(), std::move( block ) );
+	return audio_call( "compress", get_format(), t.ok && r.ok && a.ok && rel.ok && k.ok, ws_bytes, [&]( float * out, void * ws )
+		{
+		return flanhip_compress_dev( d_x, get_num_channels(), get_num_frames(), get_sample_rate(), d_side, side.get_num_channels(), side.get_num_frames(),
+			t.ptr(), t.scalar, r.ptr(), r.scalar, a.ptr(), a.scalar, rel.ptr(), rel.scalar, k.ptr(), k.scalar, out, nullptr, ws, nullptr );
+		} );
 	}
 
 // :119, :291, :342: sample_function_over_domain is the Function sampled once per frame at f * frame_to_time( 1 ); the clamp is the device's
@@ -397,7 +345,7 @@ std::vector<Audio> Audio::filter_1pole_split( const Function<Second, Frequency> 
 	std::vector<Audio> outs;
 	if( is_null() || !device_data() ) { outs.push_back( Audio::create_null() ); outs.push_back( Audio::create_null() ); return outs; }
 	// :401-404: the cutoff is sampled once; the reference's round( time_to_frame( t ) ) indexing hands the sampled curve itself to every call
-	const DeviceCurve c = upload_curve( cutoff, get_num_frames(), frame_to_time( 1 ) );
+	const DeviceArg c = upload_curve( cutoff, get_num_frames(), frame_to_time( 1 ) );
 	const uint16_t n = order <= 1 ? uint16_t( 1 ) : order;     // :406-412
 	Audio low = filter_cascade( *this, c, FLANHIP_FILTER_BUTTERWORTH_LOW, n, "filter_1pole_split" );
 	Audio high = filter_cascade( *this, c, FLANHIP_FILTER_BUTTERWORTH_HIGH, n, "filter_1pole_split" );
@@ -429,7 +377,7 @@ static Audio filter_2pole( const Audio & me, const Function<Second, Frequency> &
 	{
 	if( me.is_null() || !me.device_data() ) return Audio::create_null();     // :590; without a device nothing is sampled
 	const float step = me.frame_to_time( 1 );
-	return filter2_cascade( me, upload_curve( cutoff, me.get_num_frames(), step ), upload_curve( damping, me.get_num_frames(), step ), DeviceCurve(),
+	return filter2_cascade( me, upload_curve( cutoff, me.get_num_frames(), step ), upload_curve( damping, me.get_num_frames(), step ), DeviceArg(),
 		kind, order, who );
 	}
 
@@ -489,7 +437,7 @@ static Audio filter_1pole_shelf( const Audio & me, const Function<Second, Freque
 	{
 	if( me.is_null() || !me.device_data() ) return Audio::create_null();     // :496, :508
 	const float step = 1.0f / me.get_sample_rate();
-	return filter2_cascade( me, upload_curve( cutoff, me.get_num_frames(), step ), DeviceCurve(), upload_curve( gain, me.get_num_frames(), step ),
+	return filter2_cascade( me, upload_curve( cutoff, me.get_num_frames(), step ), DeviceArg(), upload_curve( gain, me.get_num_frames(), step ),
 		kind, order, who );
 	}
 
@@ -512,16 +460,13 @@ Audio Audio::filter_comb( const Function<Second, Frequency> & cutoff, const Func
 	const size_t ws_bytes = flanhip_filter_comb_workspace_bytes( get_num_channels(), get_num_frames() );
 	if( ws_bytes == 0 ) return Audio::create_null();
 	const float step = 1.0f / get_sample_rate();
-	const DeviceCurve c = upload_curve( cutoff, get_num_frames(), step ), k = upload_curve( feedback, get_num_frames(), step ),
+	const DeviceArg c = upload_curve( cutoff, get_num_frames(), step ), k = upload_curve( feedback, get_num_frames(), step ),
 		a = upload_curve( wet_dry, get_num_frames(), step );
-	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( get_num_channels() ) * size_t( get_num_frames() ) );
-	auto ws = detail::DeviceBlock::allocate( ws_bytes );
-	if( !c.ok || !k.ok || !a.ok || !block || !ws ) return Audio::create_null();
-	const int rc = flanhip_filter_comb_dev( device_data(), get_num_channels(), get_num_frames(), get_sample_rate(), c.ptr(), c.scalar, k.ptr(), k.scalar,
-		a.ptr(), a.scalar, invert ? 1 : 0, static_cast<float*>( block->ptr ), ws->ptr, nullptr );
-	if( !detail::report( rc, "filter_comb" ) ) return Audio::create_null();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "filter_comb" ) ) return Audio::create_null();         // the workspace and the curves go back idle
-	return AudioBuffer::adopt_device( get_format(), std::move( block ) );
+	return audio_call( "filter_comb", get_format(), c.ok && k.ok && a.ok, ws_bytes, [&]( float * out, void * ws )
+		{
+		return flanhip_filter_comb_dev( device_data(), get_num_channels(), get_num_frames(), get_sample_rate(), c.ptr(), c.scalar, k.ptr(), k.scalar,
+			a.ptr(), a.scalar, invert ? 1 : 0, out, ws, nullptr );
+		} );
 	}
 
 // :813-815, :830-831, :912-915, :978: every parameter once per frame at f * ( 1.0f / sr ), as filter_comb samples; the clamp, the prewarp and the
@@ -545,16 +490,13 @@ static Audio multinotch( const Audio & me, const char * name, int kind, uint16_t
 	if( !me.device_data() ) return Audio::create_null();               // without a device nothing is sampled
 	const Frame n = me.get_num_frames();
 	const float step = 1.0f / me.get_sample_rate();
-	const DeviceCurve c = upload_curve( cutoff, n, step ), R = damping ? upload_curve( *damping, n, step ) : DeviceCurve{},
+	const DeviceArg c = upload_curve( cutoff, n, step ), R = damping ? upload_curve( *damping, n, step ) : DeviceArg(),
 		k = upload_curve( feedback, n, step ), a = upload_curve( wet_dry, n, step );
-	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( me.get_num_channels() ) * size_t( n ) );
-	auto ws = detail::DeviceBlock::allocate( ws_bytes );
-	if( !c.ok || ( damping && !R.ok ) || !k.ok || !a.ok || !block || !ws ) return Audio::create_null();
-	const int rc = flanhip_multinotch_dev( me.device_data(), me.get_num_channels(), n, me.get_sample_rate(), c.ptr(), c.scalar, R.ptr(), R.scalar,
-		k.ptr(), k.scalar, a.ptr(), a.scalar, kind, order, invert ? 1 : 0, static_cast<float*>( block->ptr ), ws->ptr, nullptr );
-	if( !detail::report( rc, name ) ) return Audio::create_null();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), name ) ) return Audio::create_null();         // the workspace and the curves go back idle
-	return AudioBuffer::adopt_device( me.get_format(), std::move( block ) );
+	return audio_call( name, me.get_format(), c.ok && R.ok && k.ok && a.ok, ws_bytes, [&]( float * out, void * ws )
+		{
+		return flanhip_multinotch_dev( me.device_data(), me.get_num_channels(), n, me.get_sample_rate(), c.ptr(), c.scalar, R.ptr(), R.scalar,
+			k.ptr(), k.scalar, a.ptr(), a.scalar, kind, order, invert ? 1 : 0, out, ws, nullptr );
+		} );
 	}
 
 Audio Audio::filter_1pole_multinotch( uint16_t order, const Function<Second, Frequency> & cutoff, const Function<Second, float> & feedback, bool invert,
@@ -573,7 +515,7 @@ Audio Audio::filter_2pole_multinotch( uint16_t order, const Function<Second, Fre
 Audio Audio::halfband_modulate( const Function<Second, std::complex<float>> & modulator ) const
 	{
 	if( is_null() || !device_data() ) return Audio::create_null();     // :1166; without a device nothing is sampled
-	DeviceCurve re, im;
+	DeviceArg re, im;
 	if( modulator.is_constant() ) { re.scalar = modulator.get_constant().real(); im.scalar = modulator.get_constant().imag(); }
 	else
 		{
@@ -600,7 +542,7 @@ Audio Audio::shift_frequency( const Function<Second, Frequency> & shift, const F
 	auto frame_of = [&]( Frame f ){ return std::clamp( Frame( std::round( time_to_frame( Second( f * step ) ) ) ), Frame( 0 ), n - 1 ); };
 	// :1218-1219: shift * pi2 / sr summed one frame after the other from 0.0f, exclusive
 	detail::StagingVector<float> phase( static_cast<size_t>( n ) );
-	DeviceCurve lp, hp;
+	DeviceArg lp, hp;
 	if( shift.is_constant() )
 		{
 		const Frequency s = shift.get_constant();
@@ -626,11 +568,11 @@ Audio Audio::shift_frequency( const Function<Second, Frequency> & shift, const F
 		}
 	detail::StagingVector<float> read( static_cast<size_t>( n ) );     // :1223-1225: the modulator reads the phase through the same round trip
 	for( Frame f = 0; f < n; ++f ) read[size_t( f )] = phase[size_t( frame_of( f ) )];
-	const DeviceCurve d_phase = upload_values( read );
+	const DeviceArg d_phase = upload_values( read );
 	const Audio antialiased = filter_cascade( filter_cascade( *this, lp, FLANHIP_FILTER_BUTTERWORTH_LOW, 8, "shift_frequency" ), hp,
 		FLANHIP_FILTER_BUTTERWORTH_HIGH, 8, "shift_frequency" );
 	if( antialiased.is_null() ) return Audio::create_null();
-	return halfband_modulated( antialiased, DeviceCurve(), DeviceCurve(), &d_phase, "shift_frequency" );
+	return halfband_modulated( antialiased, DeviceArg(), DeviceArg(), &d_phase, "shift_frequency" );
 	}
 
 Audio Audio::halfband_multiply( const Audio & modulator ) const
@@ -638,9 +580,7 @@ Audio Audio::halfband_multiply( const Audio & modulator ) const
 	if( is_null() || modulator.is_null() || !device_data() ) return Audio::create_null();     // :1233; the reference dereferences a null modulator
 	auto bandpass_antialias = []( const Audio & a )                    // :1235-1240
 		{
-		DeviceCurve low, high;
-		low.scalar = 30;
-		high.scalar = a.get_sample_rate() / 2 - 2000;
+		const DeviceArg low( 30.0f ), high( a.get_sample_rate() / 2 - 2000 );
 		return filter_cascade( filter_cascade( a, high, FLANHIP_FILTER_BUTTERWORTH_LOW, 8, "halfband_multiply" ), low,
 			FLANHIP_FILTER_BUTTERWORTH_HIGH, 8, "halfband_multiply" );
 		};
@@ -653,14 +593,10 @@ Audio Audio::halfband_multiply( const Audio & modulator ) const
 	if( ws_bytes == 0 ) return Audio::create_null();
 	const float * d_a = a.device_data(), * d_b = b.device_data();
 	if( !d_a || !d_b ) return Audio::create_null();
-	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( f.num_channels ) * size_t( f.num_frames ) );
-	auto ws = detail::DeviceBlock::allocate( ws_bytes );
-	if( !block || !ws ) return Audio::create_null();
-	const int rc = flanhip_halfband_multiply_dev( d_a, a.get_num_channels(), a.get_num_frames(), a.get_sample_rate(), d_b, b.get_num_channels(),
-		b.get_num_frames(), b.get_sample_rate(), static_cast<float*>( block->ptr ), ws->ptr, nullptr );
-	if( !detail::report( rc, "halfband_multiply" ) ) return Audio::create_null();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "halfband_multiply" ) ) return Audio::create_null();     // the workspace goes back idle
-	return AudioBuffer::adopt_device( f, std::move( block ) );
+	return audio_call( "halfband_multiply", f, true, ws_bytes, [&]( float * out, void * ws )
+		{
+		return flanhip_halfband_multiply_dev( d_a, a.get_num_channels(), a.get_num_frames(), a.get_sample_rate(), d_b, b.get_num_channels(), b.get_num_frames(), b.get_sample_rate(), out, ws, nullptr );
+		} );
 	}
 
 // ---- channels (Audio/AudioConversions.cpp:58-104, Audio/AudioChannels.cpp) --------------------------------------------------------------
@@ -677,11 +613,8 @@ Audio Audio::convert_to_stereo() const
 	if( !d_x ) return Audio::create_null();
 	AudioBuffer::Format f = get_format();
 	f.num_channels = 2;
-	auto block = detail::DeviceBlock::allocate( sizeof( float ) * 2 * size_t( f.num_frames ) );
-	if( !block ) return Audio::create_null();
-	if( !detail::report( flanhip_audio_to_stereo_dev( d_x, f.num_frames, static_cast<float*>( block->ptr ), nullptr ), "convert_to_stereo" ) ) return Audio::create_null();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "convert_to_stereo" ) ) return Audio::create_null();
-	return AudioBuffer::adopt_device( f, std::move( block ) );
+	return audio_call( "convert_to_stereo", f, true, detail::kNoWorkspace, [&]( float * out, void * )
+		{ return flanhip_audio_to_stereo_dev( d_x, f.num_frames, out, nullptr ); } );
 	}
 
 Audio Audio::convert_to_mono() const
@@ -691,12 +624,8 @@ Audio Audio::convert_to_mono() const
 	if( !d_x ) return Audio::create_null();
 	AudioBuffer::Format f = get_format();
 	f.num_channels = 1;
-	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( f.num_frames ) );
-	if( !block ) return Audio::create_null();
-	if( !detail::report( flanhip_audio_to_mono_dev( d_x, get_num_channels(), f.num_frames, static_cast<float*>( block->ptr ), nullptr ), "convert_to_mono" ) )
-		return Audio::create_null();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "convert_to_mono" ) ) return Audio::create_null();
-	return AudioBuffer::adopt_device( f, std::move( block ) );
+	return audio_call( "convert_to_mono", f, true, detail::kNoWorkspace, [&]( float * out, void * )
+		{ return flanhip_audio_to_mono_dev( d_x, get_num_channels(), f.num_frames, out, nullptr ); } );
 	}
 
 std::vector<Audio> Audio::split_channels() const
@@ -706,14 +635,15 @@ std::vector<Audio> Audio::split_channels() const
 	const float * d_x = device_data();
 	AudioBuffer::Format f = get_format();
 	f.num_channels = 1;
+	DeviceCall call( "split_channels" );                        // a channel's block is handed out once its copy is launched; one wait for them all
 	for( Channel channel = 0; channel < get_num_channels(); ++channel )
 		{
-		auto block = d_x ? detail::DeviceBlock::allocate( sizeof( float ) * size_t( f.num_frames ) ) : nullptr;
-		const bool ok = block && detail::report( flanhip_audio_copy_rows_dev( d_x + size_t( channel ) * size_t( f.num_frames ), f.num_frames, 1, f.num_frames,
-			static_cast<float*>( block->ptr ), f.num_frames, f.num_frames, nullptr ), "split_channels" );
-		channels.emplace_back( ok ? Audio( AudioBuffer::adopt_device( f, std::move( block ) ) ) : Audio() );
+		float * out = d_x ? call.output<float>( size_t( f.num_frames ) ) : nullptr;
+		const bool ok = out && call.launch( flanhip_audio_copy_rows_dev( d_x + size_t( channel ) * size_t( f.num_frames ), f.num_frames, 1, f.num_frames,
+			out, f.num_frames, f.num_frames, nullptr ) );
+		channels.emplace_back( ok ? Audio( call.adopt<AudioBuffer>( f ) ) : Audio() );
 		}
-	if( d_x ) detail::report( flanhip_stream_synchronize( nullptr ), "split_channels" );
+	if( d_x ) call.sync();
 	return channels;
 	}
 
@@ -741,20 +671,19 @@ Audio Audio::combine_channels( const std::vector<const Audio *> & channels_unmat
 	f.sample_rate = channels[0]->get_sample_rate();
 	f.num_channels = 0; f.num_frames = 0;
 	for( const Audio * a : channels ) { f.num_channels += a->get_num_channels(); f.num_frames = std::max( f.num_frames, a->get_num_frames() ); }
-	auto block = detail::DeviceBlock::allocate( sizeof( float ) * size_t( f.num_channels ) * size_t( f.num_frames ) );
-	if( !block ) return Audio::create_null();
+	DeviceCall call( "combine_channels" );
+	float * out = call.output<float>( size_t( f.num_channels ) * size_t( f.num_frames ) );
+	if( !out ) return Audio::create_null();
 	Channel current = 0;
 	for( const Audio * a : channels )                                              // :50-59; what lies behind a shorter input is zero (:48)
 		{
 		const float * d_a = a->device_data();
 		if( !d_a ) return Audio::create_null();
-		const int rc = flanhip_audio_copy_rows_dev( d_a, a->get_num_frames(), a->get_num_channels(), a->get_num_frames(),
-			static_cast<float*>( block->ptr ) + size_t( current ) * size_t( f.num_frames ), f.num_frames, f.num_frames, nullptr );
-		if( !detail::report( rc, "combine_channels" ) ) return Audio::create_null();
+		if( !call.launch( flanhip_audio_copy_rows_dev( d_a, a->get_num_frames(), a->get_num_channels(), a->get_num_frames(),
+				out + size_t( current ) * size_t( f.num_frames ), f.num_frames, f.num_frames, nullptr ) ) ) return Audio::create_null();
 		current += a->get_num_channels();
 		}
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "combine_channels" ) ) return Audio::create_null();
-	return AudioBuffer::adopt_device( f, std::move( block ) );
+	return or_null( call.finish<AudioBuffer>( f ) );
 	}
 
 Audio Audio::combine_channels( const std::vector<Audio> & channels )
@@ -770,13 +699,10 @@ static Audio panned( const Audio & stereo, const Function<Second, float> & pan_a
 	{
 	const float * d_x = stereo.device_data();
 	if( !d_x ) return Audio();                                    // without a device nothing is sampled
-	const DeviceCurve p = upload_curve( pan_amount, stereo.get_num_frames(), 1.0f / stereo.get_sample_rate() );
-	auto block = detail::DeviceBlock::allocate( sizeof( float ) * 2 * size_t( stereo.get_num_frames() ) );
-	if( !p.ok || !block ) return Audio();
-	const int rc = flanhip_audio_pan_dev( d_x, 2, stereo.get_num_frames(), p.ptr(), p.scalar, static_cast<float*>( block->ptr ), nullptr );
-	if( !detail::report( rc, "pan" ) ) return Audio();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "pan" ) ) return Audio();                   // the curve goes back idle
-	return AudioBuffer::adopt_device( stereo.get_format(), std::move( block ) );
+	const DeviceArg p = upload_curve( pan_amount, stereo.get_num_frames(), 1.0f / stereo.get_sample_rate() );
+	// (a failure is a plain null here: pan() says "Null Audio created", pan_in_place() keeps what it has)
+	return detail::device_call<AudioBuffer, float>( "pan", stereo.get_format(), 2 * size_t( stereo.get_num_frames() ), p.ok, detail::kNoWorkspace,
+		[&]( float * out, void * ){ return flanhip_audio_pan_dev( d_x, 2, stereo.get_num_frames(), p.ptr(), p.scalar, out, nullptr ); } );
 	}
 
 Audio Audio::pan( const Function<Second, float> & pan_amount ) const
@@ -823,11 +749,10 @@ Audio Audio::stereo_spatialize( const Function<Second, vec2> & position, Meter h
 	const float * d_x = device_data();
 	if( !d_x ) return Audio::create_null();                                        // without a device nothing is sampled
 	// head_ild's low-pass (:128) is the same for both ears: once
-	DeviceCurve cutoff;
-	cutoff.scalar = 500;
-	const Audio lowpassed = filter_cascade( *this, cutoff, FLANHIP_FILTER_BUTTERWORTH_LOW, 1, "stereo_spatialize" );
+	const Audio lowpassed = filter_cascade( *this, DeviceArg( 500.0f ), FLANHIP_FILTER_BUTTERWORTH_LOW, 1, "stereo_spatialize" );
 	if( lowpassed.is_null() ) return Audio::create_null();
-	auto shaped = detail::DeviceBlock::allocate( sizeof( float ) * 2 * size_t( n ) );
+	DeviceCall call( "stereo_spatialize" );                                       // two launches: every `return` below the first waits for it
+	float * shaped = static_cast<float*>( call.scratch( sizeof( float ) * 2 * size_t( n ) ) );
 	if( !shaped ) return Audio::create_null();
 	const vec2d ear_position[2] = { vec2d( 0, 1 * head_width / 2.0f ), vec2d( 0, -1 * head_width / 2.0f ) };    // :261, the left ear first
 	AudioBuffer::Format f = get_format();
@@ -846,14 +771,12 @@ Audio Audio::stereo_spatialize( const Function<Second, vec2> & position, Meter h
 			out_frames[e] = Frame( n + delays[e] );                                // :148
 			}
 		f.num_frames = Frame( std::max( out_frames[0], out_frames[1] ) );
-		if( !detail::report( flanhip_spatial_ear_dev( d_x, lowpassed.device_data(), 1, n, sr, nullptr, p.x(), p.y(), head_width, FLANHIP_SPATIAL_BOTH,
-				static_cast<float*>( shaped->ptr ), nullptr ), "stereo_spatialize" ) ) return Audio::create_null();
-		auto block = detail::DeviceBlock::allocate( sizeof( float ) * 2 * size_t( f.num_frames ) );
-		if( !block ) return Audio::create_null();
-		if( !detail::report( flanhip_spatial_delay_dev( static_cast<const float*>( shaped->ptr ), 2, n, delays, out_frames, f.num_frames,
-				static_cast<float*>( block->ptr ), nullptr ), "stereo_spatialize" ) ) return Audio::create_null();
-		if( !detail::report( flanhip_stream_synchronize( nullptr ), "stereo_spatialize" ) ) return Audio::create_null();
-		return AudioBuffer::adopt_device( f, std::move( block ) );                 // combine_channels( l, r ) (:280): the longer ear's length
+		if( !call.launch( flanhip_spatial_ear_dev( d_x, lowpassed.device_data(), 1, n, sr, nullptr, p.x(), p.y(), head_width, FLANHIP_SPATIAL_BOTH,
+				shaped, nullptr ) ) ) return Audio::create_null();
+		float * out = call.output<float>( 2 * size_t( f.num_frames ) );
+		if( !out ) return Audio::create_null();
+		call.launch( flanhip_spatial_delay_dev( shaped, 2, n, delays, out_frames, f.num_frames, out, nullptr ) );
+		return or_null( call.finish<AudioBuffer>( f ) );                           // combine_channels( l, r ) (:280): the longer ear's length
 		}
 
 	// :235: the position once per frame, as doubles
@@ -905,21 +828,19 @@ Audio Audio::stereo_spatialize( const Function<Second, vec2> & position, Meter h
 		std::cerr << std::endl;
 		return Audio::create_null();
 		}
-	auto d_ps = detail::DeviceBlock::allocate( sizeof( double ) * ps.size() );
-	auto block = detail::DeviceBlock::allocate( sizeof( float ) * 2 * size_t( f.num_frames ) );
-	auto ws = detail::DeviceBlock::allocate( ws_bytes );
-	if( !d_ps || !block || !ws ) return Audio::create_null();
-	if( !detail::upload_from_host( d_ps->ptr, ps.data(), sizeof( double ) * ps.size() ) )
+	double * d_ps = static_cast<double*>( call.scratch( sizeof( double ) * ps.size() ) );
+	float * out = call.output<float>( 2 * size_t( f.num_frames ) );
+	void * ws = call.workspace( ws_bytes );
+	if( !call.ok() ) return Audio::create_null();
+	if( !detail::upload_from_host( d_ps, ps.data(), sizeof( double ) * ps.size() ) )
 		{
 		std::cerr << "flan: upload of the sampled positions failed: " << flanhip_last_error() << std::endl;
 		return Audio::create_null();
 		}
-	if( !detail::report( flanhip_spatial_ear_dev( d_x, lowpassed.device_data(), 1, n, sr, static_cast<const double*>( d_ps->ptr ), 0.0, 0.0, head_width,
-			FLANHIP_SPATIAL_BOTH, static_cast<float*>( shaped->ptr ), nullptr ), "stereo_spatialize" ) ) return Audio::create_null();
-	if( !detail::report( flanhip_spatial_itd_dev( static_cast<const float*>( shaped->ptr ), 2, n, sr, stretches.data(), count, out_frames, f.num_frames,
-			static_cast<float*>( block->ptr ), ws->ptr, nullptr ), "stereo_spatialize" ) ) return Audio::create_null();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "stereo_spatialize" ) ) return Audio::create_null();     // the workspace and the positions go back idle
-	return AudioBuffer::adopt_device( f, std::move( block ) );                     // combine_channels( l, r ) (:280): the longer ear's length
+	if( !call.launch( flanhip_spatial_ear_dev( d_x, lowpassed.device_data(), 1, n, sr, d_ps, 0.0, 0.0, head_width, FLANHIP_SPATIAL_BOTH, shaped, nullptr ) ) )
+		return Audio::create_null();
+	call.launch( flanhip_spatial_itd_dev( shaped, 2, n, sr, stretches.data(), count, out_frames, f.num_frames, out, ws, nullptr ) );
+	return or_null( call.finish<AudioBuffer>( f ) );                               // combine_channels( l, r ) (:280): the longer ear's length
 	}
 
 } // namespace flan

@@ -7,21 +7,26 @@
 #include <limits>
 #include <iostream>
 
-#include "device_block.h"
+#include "device_call.h"
 #include "flan/Audio.h"
 
 namespace flan {
 
 namespace {
+using detail::DeviceArg;
 using detail::DeviceBlock;
+using detail::DeviceCall;
+using detail::upload;
 
-std::shared_ptr<DeviceBlock> upload( const void * host, size_t bytes )
+size_t mf_count( const PVBuffer::Format & f ) { return size_t( f.num_channels ) * f.num_frames * f.num_bins; }
+const flanhip_MF * as_c( const MF * d ) { return reinterpret_cast<const flanhip_MF*>( d ); }
+
+// One launch( d_pv, out ) over `me`'s data on the device, beside whatever else the method `have`s, into a fresh block of format f (detail::device_call)
+template<typename Launch>
+PV pv_call( const char * who, const PV & me, const PVBuffer::Format & f, bool have, Launch launch )
 	{
-	auto b = DeviceBlock::allocate( bytes );
-	if( !b ) return nullptr;
-	if( !detail::report( flanhip_memcpy_h2d( b->ptr, host, bytes, nullptr ), "upload" ) ) return nullptr;
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "upload" ) ) return nullptr;   // a staging block goes back to its cache after this
-	return b;
+	const flanhip_MF * d_pv = as_c( me.device_data() );
+	return detail::device_call<PVBuffer, flanhip_MF>( who, f, mf_count( f ), have && d_pv, detail::kNoWorkspace, [&]( flanhip_MF * out, void * ){ return launch( d_pv, out ); } );
 	}
 
 // Declared AFTER the staging vectors / device blocks of a function that starts asynchronous copies, so that it is destroyed FIRST: on
@@ -197,32 +202,29 @@ Audio PV::convert_to_audio( flan_CANCEL_ARG_CPP ) const
 	if( !d_pv ) return Audio::create_null();
 	const size_t ws_bytes = flanhip_synthesize_workspace_bytes( get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(), get_analysis_rate(), get_window_size() );
 	if( ws_bytes == 0 ) { detail::report( FLANHIP_ERR_UNSUPPORTED, "convert_to_audio (unsupported dft / window)" ); return Audio::create_null(); }
-	auto out = DeviceBlock::allocate( sizeof( float ) * size_t( af.num_channels ) * af.num_frames );
 	const bool conditional = synthesis_workspace_is_conditional();
-	auto fused_ws = take_synthesis_workspace();                 // left by convert_to_PV / modify_time when this PV came straight from them
+	const auto fused_ws = take_synthesis_workspace();           // left by convert_to_PV / modify_time when this PV came straight from them
 	const bool fused = fused_ws && fused_ws->bytes >= ws_bytes;
-	auto ws = fused ? fused_ws : DeviceBlock::allocate( ws_bytes );
-	auto flag = DeviceBlock::allocate( sizeof( int ) );
-	if( !out || !ws || !flag ) return Audio::create_null();
-	flanhip_memset( flag->ptr, 0, sizeof( int ), nullptr );
+	int nan_flag = 0;
+	DeviceCall call( "convert_to_audio" );
+	float * out = call.output<float>( size_t( af.num_channels ) * af.num_frames );
+	void * ws = fused ? fused_ws->ptr : call.workspace( ws_bytes );
+	int * flag = static_cast<int*>( call.scratch( sizeof( int ) ) );
+	if( !call.ok() ) return Audio::create_null();
+	if( flanhip_memset( flag, 0, sizeof( int ), nullptr ) == FLANHIP_OK ) call.launch( FLANHIP_OK );   // the device is busy from here on
 	if( canceller ) return Audio::create_null();
 	const auto fused_entry = conditional ? flanhip_synthesize_dev_fused_checked : flanhip_synthesize_dev_fused;
-	const int rc = fused
-		? fused_entry( reinterpret_cast<const flanhip_MF*>( d_pv ), get_num_channels(), get_num_frames(), get_num_bins(),
-			get_sample_rate(), get_analysis_rate(), get_window_size(), static_cast<float*>( out->ptr ), ws->ptr, static_cast<int*>( flag->ptr ), nullptr )
-		: flanhip_synthesize_dev( reinterpret_cast<const flanhip_MF*>( d_pv ), get_num_channels(), get_num_frames(), get_num_bins(),
-			get_sample_rate(), get_analysis_rate(), get_window_size(), static_cast<float*>( out->ptr ), ws->ptr, static_cast<int*>( flag->ptr ), nullptr );
-	if( !detail::report( rc, "convert_to_audio" ) ) return Audio::create_null();
-	int nan_flag = 0;
-	flanhip_memcpy_d2h( &nan_flag, flag->ptr, sizeof( int ), nullptr );
-	const int waited = flanhip_wait_cancellable_fn( nullptr, detail::poll_canceller, &canceller );   // flan_CANCEL_POINT while the kernels run
-	if( waited == FLANHIP_ERR_CANCELLED ) return Audio::create_null();
-	if( !detail::report( waited, "convert_to_audio" ) ) return Audio::create_null();
+	const bool launched = call.launch( ( fused ? fused_entry : flanhip_synthesize_dev )( as_c( d_pv ), get_num_channels(), get_num_frames(), get_num_bins(),
+		get_sample_rate(), get_analysis_rate(), get_window_size(), out, ws, flag, nullptr ) );
+	if( !launched ) return Audio::create_null();
+	flanhip_memcpy_d2h( &nan_flag, flag, sizeof( int ), nullptr );
+	if( call.wait( canceller ) == FLANHIP_ERR_CANCELLED ) return Audio::create_null();   // flan_CANCEL_POINT while the kernels run
+	if( !call.sync() ) return Audio::create_null();            // (reports how the wait ended; nothing is waited for twice)
 	if( nan_flag & 2 ) { detail::report( FLANHIP_ERR_INVALID_ARG, "convert_to_audio (the synthesis workspace was overwritten by another producer)" ); return Audio::create_null(); }
 	if( nan_flag & 1 )                                         // AudioPV.cpp:88-89
 		std::cout << "flan::convert_to_audio recieved a nan or infinite value. This often happens when dividing by zero in an earlier algorithm.";
 	if( canceller ) return Audio::create_null();
-	return AudioBuffer::adopt_device( af, std::move( out ) );
+	return Audio( call.finish<AudioBuffer>( af ) );
 	}
 
 Audio PV::convertToAudio( flan_CANCEL_ARG_CPP ) const { return convert_to_audio( canceller ); }
@@ -269,23 +271,19 @@ static PV modify_time_device( const PV & me, std::shared_ptr<DeviceBlock> d_mod,
 	f.num_frames = Frame( last_output_frame );                                     // :315
 	if( f.num_frames <= 0 ) return PV();
 	const MF * d_pv = me.device_data();
-	auto out = DeviceBlock::allocate( sizeof( MF ) * size_t( f.num_channels ) * f.num_frames * f.num_bins );
-	if( !d_pv || !out ) return PV();
+	DeviceCall call( "modify_time" );
+	call.need( d_pv );
+	flanhip_MF * out = call.output<flanhip_MF>( mf_count( f ) );
+	if( !call.ok() ) return PV();
 	// the kernel that writes the output can also leave convert_to_audio's pre-pass in a workspace for the new PV (it can when the
-	// time map never runs backwards -- decided on the device): hand that workspace to the result
-	const size_t ws_bytes = flanhip_synthesize_workspace_bytes( f.num_channels, f.num_frames, f.num_bins, f.sample_rate, f.analysis_rate, f.window_size );
-	auto ws = ws_bytes ? DeviceBlock::allocate( ws_bytes ) : nullptr;
-	const int rc = ws
-		? flanhip_modify_time_interp_dev_fused( reinterpret_cast<const flanhip_MF*>( d_pv ), me.get_num_channels(), me.get_num_frames(), me.get_num_bins(),
-			me.get_sample_rate(), me.get_analysis_rate(), static_cast<const float*>( d_mod->ptr ), f.num_frames, interp, static_cast<flanhip_MF*>( out->ptr ),
-			me.get_window_size(), ws->ptr, nullptr )
-		: flanhip_modify_time_interp_dev( reinterpret_cast<const flanhip_MF*>( d_pv ), me.get_num_channels(), me.get_num_frames(), me.get_num_bins(),
-			me.get_sample_rate(), me.get_hop_size(), static_cast<const float*>( d_mod->ptr ), f.num_frames, interp, static_cast<flanhip_MF*>( out->ptr ), nullptr );
-	if( !detail::report( rc, "modify_time" ) ) return PV();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "modify_time" ) ) return PV();
-	PV result = PVBuffer::adopt_device( f, std::move( out ) );
-	if( ws ) result.attach_synthesis_workspace( std::move( ws ), true );
-	return result;
+	// time map never runs backwards -- decided on the device): that workspace goes with the result
+	void * ws = call.workspace( flanhip_synthesize_workspace_bytes( f.num_channels, f.num_frames, f.num_bins, f.sample_rate, f.analysis_rate, f.window_size ), true );
+	call.launch( ws
+		? flanhip_modify_time_interp_dev_fused( as_c( d_pv ), me.get_num_channels(), me.get_num_frames(), me.get_num_bins(),
+			me.get_sample_rate(), me.get_analysis_rate(), static_cast<const float*>( d_mod->ptr ), f.num_frames, interp, out, me.get_window_size(), ws, nullptr )
+		: flanhip_modify_time_interp_dev( as_c( d_pv ), me.get_num_channels(), me.get_num_frames(), me.get_num_bins(),
+			me.get_sample_rate(), me.get_hop_size(), static_cast<const float*>( d_mod->ptr ), f.num_frames, interp, out, nullptr ) );
+	return call.finish_fused<PVBuffer>( f, true );
 	}
 
 PV PV::modify_time( const Function<TF, Second> & mod, const Interpolator & interp ) const
@@ -305,42 +303,35 @@ PV PV::stretch( const Function<TF, float> & factor, const Interpolator & interp 
 	if( is_null() ) return PV();
 	const DeviceInterp device_interp( interp );                                      // named kind, or the callable sampled into a table
 	if( !device_interp.ok() ) return PV();
-	auto d_max = DeviceBlock::allocate( sizeof( float ) );
-	std::shared_ptr<DeviceBlock> d_grid;
-	if( factor.is_constant() )
-		{
-		// a constant factor: the map from the number alone (the running sum of a constant in closed form, csrc/const_sum.h) -- no grid, no scan
-		d_grid = DeviceBlock::allocate( sizeof( float ) * size_t( get_num_frames() ) * get_num_bins() );
-		if( !d_grid || !d_max ) return PV();
-		if( !detail::report( flanhip_stretch_map_const_dev( factor.get_constant(), static_cast<float*>( d_grid->ptr ), get_num_frames(), get_num_bins(), get_sample_rate(),
-				get_hop_size(), static_cast<float*>( d_max->ptr ), nullptr ), "stretch" ) ) return PV();
-		}
-	else
-		{
-		d_grid = function_grid_to_device( *this, factor );                           // PVModify.cpp:373
-		if( !d_grid || !d_max ) return PV();
-		// :376-382 running sum over frames per bin, frame_to_time -- on the device, plus the maximum modify_time_base needs
-		if( !detail::report( flanhip_stretch_map_dev( static_cast<float*>( d_grid->ptr ), get_num_frames(), get_num_bins(), get_sample_rate(), get_hop_size(),
-				static_cast<float*>( d_max->ptr ), nullptr ), "stretch" ) ) return PV();
-		}
 	float mx = 0.0f;
-	flanhip_memcpy_d2h( &mx, d_max->ptr, sizeof( float ), nullptr );
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "stretch" ) ) return PV();
+	std::shared_ptr<DeviceBlock> d_grid;
+		{
+		DeviceCall map( "stretch" );                                                 // the time map and its maximum: a call of its own, modify_time's follows
+		float * d_max = static_cast<float*>( map.scratch( sizeof( float ) ) );
+		// a constant factor: the map from the number alone (the running sum of a constant in closed form, csrc/const_sum.h) -- no grid, no scan
+		d_grid = factor.is_constant() ? DeviceBlock::allocate( sizeof( float ) * size_t( get_num_frames() ) * get_num_bins() )
+			: function_grid_to_device( *this, factor );                              // PVModify.cpp:373
+		if( !d_grid || !d_max ) return PV();
+		float * grid = static_cast<float*>( d_grid->ptr );
+		// :376-382 running sum over frames per bin, frame_to_time -- on the device, plus the maximum modify_time_base needs
+		const bool launched = map.launch( factor.is_constant()
+			? flanhip_stretch_map_const_dev( factor.get_constant(), grid, get_num_frames(), get_num_bins(), get_sample_rate(), get_hop_size(), d_max, nullptr )
+			: flanhip_stretch_map_dev( grid, get_num_frames(), get_num_bins(), get_sample_rate(), get_hop_size(), d_max, nullptr ) );
+		if( !launched ) return PV();
+		flanhip_memcpy_d2h( &mx, d_max, sizeof( float ), nullptr );
+		if( !map.sync() ) return PV();
+		}
 	return modify_time_device( *this, std::move( d_grid ), mx, device_interp.kind() );
 	}
 
 // modify_frequency_base, PVModify.cpp:196-257
 static PV modify_frequency_device( const PV & me, const DeviceBlock & d_mod, const DeviceBlock & d_in_modified, int interp )
 	{
-	const MF * d_pv = me.device_data();
-	const size_t n = size_t( me.get_num_channels() ) * me.get_num_frames() * me.get_num_bins();
-	auto out = DeviceBlock::allocate( sizeof( MF ) * n );
-	if( !d_pv || !out ) return PV();
-	if( !detail::report( flanhip_modify_frequency_interp_dev( reinterpret_cast<const flanhip_MF*>( d_pv ), me.get_num_channels(), me.get_num_frames(), me.get_num_bins(),
-			me.get_sample_rate(), static_cast<const float*>( d_mod.ptr ), static_cast<const float*>( d_in_modified.ptr ), interp, static_cast<flanhip_MF*>( out->ptr ), nullptr ),
-			"modify_frequency" ) ) return PV();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "modify_frequency" ) ) return PV();
-	return PVBuffer::adopt_device( me.get_format(), std::move( out ) );
+	return pv_call( "modify_frequency", me, me.get_format(), true, [&]( const flanhip_MF * d_pv, flanhip_MF * out )
+		{
+		return flanhip_modify_frequency_interp_dev( d_pv, me.get_num_channels(), me.get_num_frames(), me.get_num_bins(), me.get_sample_rate(),
+			static_cast<const float*>( d_mod.ptr ), static_cast<const float*>( d_in_modified.ptr ), interp, out, nullptr );
+		} );
 	}
 
 PV PV::modify_frequency( const Function<TF, Frequency> & mod, const Interpolator & interp ) const
@@ -366,14 +357,11 @@ PV PV::repitch( const Function<TF, float> & factor, const Interpolator & interp 
 	const DeviceInterp device_interp( interp );                                      // named kind, or the callable sampled into a table
 	if( !device_interp.ok() ) return PV();
 	auto d_grid = function_grid_to_device( *this, factor );                        // PVModify.cpp:275
-	const MF * d_pv = device_data();
-	auto out = DeviceBlock::allocate( sizeof( MF ) * size_t( get_num_channels() ) * get_num_frames() * get_num_bins() );
-	if( !d_grid || !d_pv || !out ) return PV();
 	// :278-302 running sum over bins, bin_to_frequency, per-MF lerp, then modify_frequency_base (:196-257) -- one call, on the device
-	if( !detail::report( flanhip_repitch_interp_dev( reinterpret_cast<const flanhip_MF*>( d_pv ), get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(),
-			static_cast<float*>( d_grid->ptr ), device_interp.kind(), static_cast<flanhip_MF*>( out->ptr ), nullptr ), "repitch" ) ) return PV();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "repitch" ) ) return PV();
-	return PVBuffer::adopt_device( get_format(), std::move( out ) );
+	return pv_call( "repitch", *this, get_format(), bool( d_grid ), [&]( const flanhip_MF * d_pv, flanhip_MF * out )
+		{
+		return flanhip_repitch_interp_dev( d_pv, get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(), static_cast<float*>( d_grid->ptr ), device_interp.kind(), out, nullptr );
+		} );
 	}
 
 PV PV::shape( const Function<MF, MF> & shaper, bool use_shift_alignment ) const
@@ -383,41 +371,35 @@ PV PV::shape( const Function<MF, MF> & shaper, bool use_shift_alignment ) const
 	auto d_shaped = map_rows_to_device<MF>( *this, shaper.get_execution_policy(), [&]( int, const MF * mfs, MF * out )
 		{ for( Bin bin = 0; bin < get_num_bins(); ++bin ) out[bin] = shaper( mfs[bin] ); } );
 	const MF * d_pv = device_data();
-	auto out = DeviceBlock::allocate( sizeof( MF ) * size_t( get_num_channels() ) * get_num_frames() * get_num_bins() );
-	if( !d_shaped || !d_pv || !out ) return PV();
+	DeviceCall call( "shape" );
+	call.need( bool( d_shaped ) );
+	call.need( d_pv );
+	flanhip_MF * out = call.output<flanhip_MF>( mf_count( get_format() ) );
+	if( !call.ok() ) return PV();
+	const flanhip_MF * shaped = static_cast<const flanhip_MF*>( d_shaped->ptr );
 	// without alignment the kernel that writes the result can leave convert_to_audio's pre-pass for it in a workspace
-	const size_t ws_bytes = use_shift_alignment ? 0 : flanhip_synthesize_workspace_bytes( get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(), get_analysis_rate(), get_window_size() );
-	auto ws = ws_bytes ? DeviceBlock::allocate( ws_bytes ) : nullptr;
-	const int rc = ws
-		? flanhip_shape_table_dev_fused( reinterpret_cast<const flanhip_MF*>( d_pv ), static_cast<const flanhip_MF*>( d_shaped->ptr ), get_num_channels(), get_num_frames(),
-			get_num_bins(), get_sample_rate(), get_analysis_rate(), static_cast<flanhip_MF*>( out->ptr ), get_window_size(), ws->ptr, nullptr )
-		: flanhip_shape_table_dev( reinterpret_cast<const flanhip_MF*>( d_pv ), static_cast<const flanhip_MF*>( d_shaped->ptr ), get_num_channels(),
-			get_num_frames(), get_num_bins(), get_sample_rate(), use_shift_alignment ? 1 : 0, static_cast<flanhip_MF*>( out->ptr ), nullptr );
-	if( !detail::report( rc, "shape" ) ) return PV();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "shape" ) ) return PV();
-	PV result = PVBuffer::adopt_device( get_format(), std::move( out ) );
-	if( ws ) result.attach_synthesis_workspace( std::move( ws ) );
-	return result;
+	void * ws = call.workspace( use_shift_alignment ? 0 : flanhip_synthesize_workspace_bytes( get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(), get_analysis_rate(), get_window_size() ), true );
+	call.launch( ws
+		? flanhip_shape_table_dev_fused( as_c( d_pv ), shaped, get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(), get_analysis_rate(), out,
+			get_window_size(), ws, nullptr )
+		: flanhip_shape_table_dev( as_c( d_pv ), shaped, get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(), use_shift_alignment ? 1 : 0, out, nullptr ) );
+	return call.finish_fused<PVBuffer>( get_format() );
 	}
 
 PV PV::shape_affine( float a, float b, float c, float d, bool use_shift_alignment ) const
 	{
 	if( is_null() ) return PV();
 	const MF * d_pv = device_data();
-	auto out = DeviceBlock::allocate( sizeof( MF ) * size_t( get_num_channels() ) * get_num_frames() * get_num_bins() );
-	if( !d_pv || !out ) return PV();
-	const size_t ws_bytes = use_shift_alignment ? 0 : flanhip_synthesize_workspace_bytes( get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(), get_analysis_rate(), get_window_size() );
-	auto ws = ws_bytes ? DeviceBlock::allocate( ws_bytes ) : nullptr;
-	const int rc = ws
-		? flanhip_shape_affine_dev_fused( reinterpret_cast<const flanhip_MF*>( d_pv ), get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(), get_analysis_rate(),
-			a, b, c, d, static_cast<flanhip_MF*>( out->ptr ), get_window_size(), ws->ptr, nullptr )
-		: flanhip_shape_affine_dev( reinterpret_cast<const flanhip_MF*>( d_pv ), get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(),
-			a, b, c, d, use_shift_alignment ? 1 : 0, static_cast<flanhip_MF*>( out->ptr ), nullptr );
-	if( !detail::report( rc, "shape_affine" ) ) return PV();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "shape_affine" ) ) return PV();
-	PV result = PVBuffer::adopt_device( get_format(), std::move( out ) );
-	if( ws ) result.attach_synthesis_workspace( std::move( ws ) );
-	return result;
+	DeviceCall call( "shape_affine" );
+	call.need( d_pv );
+	flanhip_MF * out = call.output<flanhip_MF>( mf_count( get_format() ) );
+	if( !call.ok() ) return PV();
+	void * ws = call.workspace( use_shift_alignment ? 0 : flanhip_synthesize_workspace_bytes( get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(), get_analysis_rate(), get_window_size() ), true );
+	call.launch( ws
+		? flanhip_shape_affine_dev_fused( as_c( d_pv ), get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(), get_analysis_rate(),
+			a, b, c, d, out, get_window_size(), ws, nullptr )
+		: flanhip_shape_affine_dev( as_c( d_pv ), get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(), a, b, c, d, use_shift_alignment ? 1 : 0, out, nullptr ) );
+	return call.finish_fused<PVBuffer>( get_format() );
 	}
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -425,38 +407,24 @@ PV PV::shape_affine( float a, float b, float c, float d, bool use_shift_alignmen
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
 // a sampled Function<TF,float> as the ( device grid or nullptr, constant ) pair the C ABI takes
-struct GridArg { std::shared_ptr<DeviceBlock> block; const float * ptr = nullptr; float constant = 0.0f; bool ok = true; };
-GridArg grid_arg( const FunctionSample2d<float> & s )
+DeviceArg grid_arg( const FunctionSample2d<float> & s )
 	{
-	GridArg g;
-	if( s.is_constant() ) { g.constant = s.get_constant(); return g; }
-	g.block = upload( s.get_vector().data(), sizeof( float ) * s.size() );
-	g.ok = bool( g.block );
-	if( g.ok ) g.ptr = static_cast<const float*>( g.block->ptr );
-	return g;
+	if( s.is_constant() ) return DeviceArg( s.get_constant() );
+	return DeviceArg( upload( s.get_vector().data(), sizeof( float ) * s.size() ) );
 	}
-PV finish( int rc, const char * what, const PVBuffer::Format & f, std::shared_ptr<DeviceBlock> out )
-	{
-	if( !detail::report( rc, what ) ) return PV();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), what ) ) return PV();
-	return PVBuffer::adopt_device( f, std::move( out ) );
-	}
-size_t mf_count( const PVBuffer::Format & f ) { return size_t( f.num_channels ) * f.num_frames * f.num_bins; }
 }
 
 static PV combine_amplitudes( const PV & me, const PV & amp_source, const Function<TF, float> & amount, bool subtract )
 	{
 	if( me.is_null() || amp_source.is_null() ) return PV();                        // PV.cpp:207-210
-	const GridArg g = grid_arg( me.sample_function_over_domain( amount ) );        // :211
-	const MF * d_pv = me.device_data();
-	const MF * d_src = amp_source.device_data();
-	auto out = DeviceBlock::allocate( sizeof( MF ) * mf_count( me.get_format() ) );
-	if( !g.ok || !d_pv || !d_src || !out ) return PV();
+	const DeviceArg g = grid_arg( me.sample_function_over_domain( amount ) );      // :211
+	const flanhip_MF * d_src = as_c( amp_source.device_data() );
 	const auto fn = subtract ? flanhip_subtract_amplitudes_dev : flanhip_replace_amplitudes_dev;
-	const int rc = fn( reinterpret_cast<const flanhip_MF*>( d_pv ), me.get_num_channels(), me.get_num_frames(), me.get_num_bins(),
-		reinterpret_cast<const flanhip_MF*>( d_src ), amp_source.get_num_channels(), amp_source.get_num_frames(), amp_source.get_num_bins(),
-		g.ptr, g.constant, static_cast<flanhip_MF*>( out->ptr ), nullptr );
-	return finish( rc, subtract ? "subtract_amplitudes" : "replace_amplitudes", me.get_format(), std::move( out ) );
+	return pv_call( subtract ? "subtract_amplitudes" : "replace_amplitudes", me, me.get_format(), g.ok && d_src, [&]( const flanhip_MF * d_pv, flanhip_MF * out )
+		{
+		return fn( d_pv, me.get_num_channels(), me.get_num_frames(), me.get_num_bins(),
+			d_src, amp_source.get_num_channels(), amp_source.get_num_frames(), amp_source.get_num_bins(), g.ptr(), g.scalar, out, nullptr );
+		} );
 	}
 
 PV PV::replace_amplitudes( const PV & amp_source, const Function<TF, float> & amount ) const { return combine_amplitudes( *this, amp_source, amount, false ); }
@@ -467,20 +435,14 @@ static PV n_loudest( const PV & me, const Function<Second, Bin> & num_bins, bool
 	{
 	if( me.is_null() ) return PV();
 	const auto sampled = num_bins.sample( 0, me.get_num_frames(), me.frame_to_time( 1 ) );   // :555
-	std::shared_ptr<DeviceBlock> d_n;
-	if( !sampled.is_constant() )
+	static_assert( sizeof( Bin ) == sizeof( int32_t ), "Bin is int32" );
+	const DeviceArg n = sampled.is_constant() ? DeviceArg() : DeviceArg( upload( sampled.get_vector().data(), sizeof( int32_t ) * sampled.get_vector().size() ) );
+	if( !n.ok ) return PV();
+	return pv_call( remove ? "remove_n_loudest_partials" : "retain_n_loudest_partials", me, me.get_format(), true, [&]( const flanhip_MF * d_pv, flanhip_MF * out )
 		{
-		static_assert( sizeof( Bin ) == sizeof( int32_t ), "Bin is int32" );
-		d_n = upload( sampled.get_vector().data(), sizeof( int32_t ) * sampled.get_vector().size() );
-		if( !d_n ) return PV();
-		}
-	const MF * d_pv = me.device_data();
-	auto out = DeviceBlock::allocate( sizeof( MF ) * mf_count( me.get_format() ) );
-	if( !d_pv || !out ) return PV();
-	const int rc = flanhip_n_loudest_partials_dev( reinterpret_cast<const flanhip_MF*>( d_pv ), me.get_num_channels(), me.get_num_frames(), me.get_num_bins(),
-		d_n ? static_cast<const int32_t*>( d_n->ptr ) : nullptr, sampled.is_constant() ? int32_t( sampled.get_constant() ) : 0, remove ? 1 : 0,
-		static_cast<flanhip_MF*>( out->ptr ), nullptr );
-	return finish( rc, remove ? "remove_n_loudest_partials" : "retain_n_loudest_partials", me.get_format(), std::move( out ) );
+		return flanhip_n_loudest_partials_dev( d_pv, me.get_num_channels(), me.get_num_frames(), me.get_num_bins(),
+			n.ptr<int32_t>(), sampled.is_constant() ? int32_t( sampled.get_constant() ) : 0, remove ? 1 : 0, out, nullptr );
+		} );
 	}
 
 PV PV::retain_n_loudest_partials( const Function<Second, Bin> & num_bins ) const { return n_loudest( *this, num_bins, false ); }
@@ -494,13 +456,9 @@ PV PV::resonate( Second length, const Function<TF, float> & decay ) const
 	PVBuffer::Format f = get_format();
 	f.num_frames = Frame( Fo );
 	// :616: decay is sampled over the OUTPUT's domain
-	const GridArg g = grid_arg( decay.sample( 0, float( f.num_frames ), 1.0f / get_analysis_rate(), 0, float( f.num_bins ), bin_to_frequency( 1 ) ) );
-	const MF * d_pv = device_data();
-	auto out = DeviceBlock::allocate( sizeof( MF ) * mf_count( f ) );
-	if( !g.ok || !d_pv || !out ) return PV();
-	const int rc = flanhip_resonate_dev( reinterpret_cast<const flanhip_MF*>( d_pv ), get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(),
-		get_hop_size(), Fo, g.ptr, g.constant, static_cast<flanhip_MF*>( out->ptr ), nullptr );
-	return finish( rc, "resonate", f, std::move( out ) );
+	const DeviceArg g = grid_arg( decay.sample( 0, float( f.num_frames ), 1.0f / get_analysis_rate(), 0, float( f.num_bins ), bin_to_frequency( 1 ) ) );
+	return pv_call( "resonate", *this, f, g.ok, [&]( const flanhip_MF * d_pv, flanhip_MF * out )
+		{ return flanhip_resonate_dev( d_pv, get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(), get_hop_size(), Fo, g.ptr(), g.scalar, out, nullptr ); } );
 	}
 
 PV PV::desample( const Function<TF, float> & decimation_ratio, const Interpolator & interp ) const
@@ -508,13 +466,9 @@ PV PV::desample( const Function<TF, float> & decimation_ratio, const Interpolato
 	if( is_null() ) return PV();
 	const DeviceInterp device_interp( interp );                                      // named kind, or the callable sampled into a table
 	if( !device_interp.ok() ) return PV();
-	const GridArg g = grid_arg( sample_function_over_domain( decimation_ratio ) ); // PVModify.cpp:450
-	const MF * d_pv = device_data();
-	auto out = DeviceBlock::allocate( sizeof( MF ) * mf_count( get_format() ) );
-	if( !g.ok || !d_pv || !out ) return PV();
-	const int rc = flanhip_desample_dev( reinterpret_cast<const flanhip_MF*>( d_pv ), get_num_channels(), get_num_frames(), get_num_bins(), g.ptr, g.constant,
-		device_interp.kind(), static_cast<flanhip_MF*>( out->ptr ), nullptr );
-	return finish( rc, "desample", get_format(), std::move( out ) );
+	const DeviceArg g = grid_arg( sample_function_over_domain( decimation_ratio ) ); // PVModify.cpp:450
+	return pv_call( "desample", *this, get_format(), g.ok, [&]( const flanhip_MF * d_pv, flanhip_MF * out )
+		{ return flanhip_desample_dev( d_pv, get_num_channels(), get_num_frames(), get_num_bins(), g.ptr(), g.scalar, device_interp.kind(), out, nullptr ); } );
 	}
 
 PV PV::time_extrapolate( Second start_time, Second end_time, Second extrapolation_time, const Interpolator & interpolator ) const
@@ -536,13 +490,11 @@ PV PV::time_extrapolate( Second start_time, Second end_time, Second extrapolatio
 	std::vector<float> interp_samples( size_t( f.num_frames - start_frame ) );     // :631-633, literally
 	for( Frame frame = 0; frame < Frame( interp_samples.size() ); ++frame )
 		interp_samples[frame] = interpolator( float( frame - start_frame ) / float( end_frame - start_frame ) );
-	auto d_samples = upload( interp_samples.data(), sizeof( float ) * interp_samples.size() );
-	const MF * d_pv = device_data();
-	auto out = DeviceBlock::allocate( sizeof( MF ) * mf_count( f ) );
-	if( !d_samples || !d_pv || !out ) return PV();
-	const int rc = flanhip_time_extrapolate_dev( reinterpret_cast<const flanhip_MF*>( d_pv ), get_num_channels(), get_num_frames(), get_num_bins(),
-		get_sample_rate(), start_frame, end_frame, f.num_frames, static_cast<const float*>( d_samples->ptr ), static_cast<flanhip_MF*>( out->ptr ), nullptr );
-	return finish( rc, "time_extrapolate", f, std::move( out ) );
+	const DeviceArg samples( upload( interp_samples.data(), sizeof( float ) * interp_samples.size() ) );
+	return pv_call( "time_extrapolate", *this, f, samples.ok, [&]( const flanhip_MF * d_pv, flanhip_MF * out )
+		{
+		return flanhip_time_extrapolate_dev( d_pv, get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(), start_frame, end_frame, f.num_frames, samples.ptr(), out, nullptr );
+		} );
 	}
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -554,12 +506,8 @@ PV PV::get_frame( Second time ) const
 	const float selected = std::clamp( time_to_frame( time ), 0.0f, float( get_num_frames() - 1 ) );   // PV.cpp:28
 	PVBuffer::Format f = get_format();
 	f.num_frames = 1;                                                               // :30-31
-	const MF * d_pv = device_data();
-	auto out = DeviceBlock::allocate( sizeof( MF ) * mf_count( f ) );
-	if( !d_pv || !out ) return PV();
-	const int rc = flanhip_get_frame_dev( reinterpret_cast<const flanhip_MF*>( d_pv ), get_num_channels(), get_num_frames(), get_num_bins(), selected,
-		FLANHIP_INTERP_LINEAR, static_cast<flanhip_MF*>( out->ptr ), nullptr );
-	return finish( rc, "get_frame", f, std::move( out ) );
+	return pv_call( "get_frame", *this, f, true, [&]( const flanhip_MF * d_pv, flanhip_MF * out )
+		{ return flanhip_get_frame_dev( d_pv, get_num_channels(), get_num_frames(), get_num_bins(), selected, FLANHIP_INTERP_LINEAR, out, nullptr ); } );
 	}
 
 PV PV::select( Second length, const Function<TF, TF> & selector ) const
@@ -569,13 +517,9 @@ PV PV::select( Second length, const Function<TF, TF> & selector ) const
 	PVBuffer::Format f = get_format();
 	f.num_frames = Frame( time_to_frame( length ) );                                // :100-101
 	if( f.num_frames <= 0 ) return PV();
-	auto d_sel = function_grid_to_device( *this, selector, static_cast<FunctionSample2d<TF>*>( nullptr ), f.num_frames );   // :103, over the OUTPUT's domain
-	const MF * d_pv = device_data();
-	auto out = DeviceBlock::allocate( sizeof( MF ) * mf_count( f ) );
-	if( !d_sel || !d_pv || !out ) return PV();
-	const int rc = flanhip_select_dev( reinterpret_cast<const flanhip_MF*>( d_pv ), get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(),
-		get_hop_size(), static_cast<const float*>( d_sel->ptr ), f.num_frames, static_cast<flanhip_MF*>( out->ptr ), nullptr );
-	return finish( rc, "select", f, std::move( out ) );
+	const DeviceArg d_sel( function_grid_to_device( *this, selector, static_cast<FunctionSample2d<TF>*>( nullptr ), f.num_frames ) );   // :103, over the OUTPUT's domain
+	return pv_call( "select", *this, f, d_sel.ok, [&]( const flanhip_MF * d_pv, flanhip_MF * out )
+		{ return flanhip_select_dev( d_pv, get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(), get_hop_size(), d_sel.ptr(), f.num_frames, out, nullptr ); } );
 	}
 
 PV PV::freeze( const std::vector<Second> & pause_times, const std::vector<Second> & pause_lengths ) const
@@ -593,13 +537,9 @@ PV PV::freeze( const std::vector<Second> & pause_times, const std::vector<Second
 	flanhip_freeze_plan( get_num_frames(), get_sample_rate(), get_hop_size(), pause_times.data(), pause_lengths.data(), n, src.data() );
 	PVBuffer::Format f = get_format();
 	f.num_frames = Frame( Fo );                                                     // :170-171
-	auto d_src = upload( src.data(), sizeof( int32_t ) * src.size() );
-	const MF * d_pv = device_data();
-	auto out = DeviceBlock::allocate( sizeof( MF ) * mf_count( f ) );
-	if( !d_src || !d_pv || !out ) return PV();
-	const int rc = flanhip_select_frames_dev( reinterpret_cast<const flanhip_MF*>( d_pv ), get_num_channels(), get_num_frames(), get_num_bins(),
-		static_cast<const int32_t*>( d_src->ptr ), Fo, static_cast<flanhip_MF*>( out->ptr ), nullptr );
-	return finish( rc, "freeze", f, std::move( out ) );
+	const DeviceArg d_src( upload( src.data(), sizeof( int32_t ) * src.size() ) );
+	return pv_call( "freeze", *this, f, d_src.ok, [&]( const flanhip_MF * d_pv, flanhip_MF * out )
+		{ return flanhip_select_frames_dev( d_pv, get_num_channels(), get_num_frames(), get_num_bins(), d_src.ptr<int32_t>(), Fo, out, nullptr ); } );
 	}
 
 PV PV::modify( const Function<TF, TF> & mod, const Interpolator & interp ) const
@@ -629,12 +569,11 @@ PV PV::modify( const Function<TF, TF> & mod, const Interpolator & interp ) const
 		} );
 	PVBuffer::Format f = get_format();
 	f.num_frames = Frame( Fo );
-	const MF * d_pv = device_data();
-	auto out = DeviceBlock::allocate( sizeof( MF ) * mf_count( f ) );
-	if( !d_in_f || !d_pv || !out ) return PV();
-	const int rc = flanhip_modify_dev( reinterpret_cast<const flanhip_MF*>( d_pv ), get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(), get_hop_size(),
-		static_cast<const float*>( d_mod->ptr ), static_cast<const float*>( d_in_f->ptr ), device_interp.kind(), Fo, static_cast<flanhip_MF*>( out->ptr ), nullptr );
-	return finish( rc, "modify", f, std::move( out ) );
+	return pv_call( "modify", *this, f, bool( d_in_f ), [&]( const flanhip_MF * d_pv, flanhip_MF * out )
+		{
+		return flanhip_modify_dev( d_pv, get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(), get_hop_size(),
+			static_cast<const float*>( d_mod->ptr ), static_cast<const float*>( d_in_f->ptr ), device_interp.kind(), Fo, out, nullptr );
+		} );
 	}
 
 PV PV::stretch_spline( const Function<Second, float> & interpolation ) const
@@ -654,12 +593,8 @@ PV PV::stretch_spline( const Function<Second, float> & interpolation ) const
 	if( Fo <= 0 ) return PV();
 	PVBuffer::Format f = get_format();
 	f.num_frames = Frame( Fo );
-	const MF * d_pv = device_data();
-	auto out = DeviceBlock::allocate( sizeof( MF ) * mf_count( f ) );
-	if( !d_pv || !out ) return PV();
-	const int rc = flanhip_stretch_spline_dev( reinterpret_cast<const flanhip_MF*>( d_pv ), get_num_channels(), get_num_frames(), get_num_bins(), steps.data(), Fo,
-		static_cast<flanhip_MF*>( out->ptr ), nullptr );
-	return finish( rc, "stretch_spline", f, std::move( out ) );
+	return pv_call( "stretch_spline", *this, f, true, [&]( const flanhip_MF * d_pv, flanhip_MF * out )
+		{ return flanhip_stretch_spline_dev( d_pv, get_num_channels(), get_num_frames(), get_num_bins(), steps.data(), Fo, out, nullptr ); } );
 	}
 
 PV PV::smear_time( const Function<TF, Second> & smear_size, const Function<TF, int> & granularity, const Function<Second, float> & distribution ) const
@@ -667,9 +602,9 @@ PV PV::smear_time( const Function<TF, Second> & smear_size, const Function<TF, i
 	if( is_null() ) return PV();
 	// PVModify.cpp:520-524: both grids over this PV's domain (the clamps to >= 1 and >= 0 happen where the values are used)
 	FunctionSample2d<Second> smear_host{ 0.0f, 0, 0 };
-	std::shared_ptr<DeviceBlock> d_smear, d_gran;
-	if( !smear_size.is_constant() ) { d_smear = function_grid_to_device( *this, smear_size, &smear_host ); if( !d_smear ) return PV(); }
-	if( !granularity.is_constant() ) { d_gran = function_grid_to_device( *this, granularity ); if( !d_gran ) return PV(); }
+	DeviceArg d_smear, d_gran;
+	if( !smear_size.is_constant() ) { d_smear = DeviceArg( function_grid_to_device( *this, smear_size, &smear_host ) ); if( !d_smear.ok ) return PV(); }
+	if( !granularity.is_constant() ) { d_gran = DeviceArg( function_grid_to_device( *this, granularity ) ); if( !d_gran.ok ) return PV(); }
 	int32_t true_left = 0, dist_samples_2 = 0;
 	int64_t Fo = 0;
 	if( !detail::report( flanhip_smear_time_plan( get_num_frames(), get_num_bins(), get_sample_rate(), get_hop_size(),
@@ -684,17 +619,15 @@ PV PV::smear_time( const Function<TF, Second> & smear_size, const Function<TF, i
 		if( sampled.is_constant() ) dist.assign( size_t( 2 ) * dist_samples_2, sampled.get_constant() );
 		else dist = sampled.get_vector();
 		}
-	auto d_dist = dist.empty() ? nullptr : upload( dist.data(), sizeof( float ) * dist.size() );
+	const DeviceArg d_dist = dist.empty() ? DeviceArg() : DeviceArg( upload( dist.data(), sizeof( float ) * dist.size() ) );
 	PVBuffer::Format f = get_format();
 	f.num_frames = Frame( Fo );                                                     // :562-563
-	const MF * d_pv = device_data();
-	auto out = DeviceBlock::allocate( sizeof( MF ) * mf_count( f ) );
-	if( ( !dist.empty() && !d_dist ) || !d_pv || !out ) return PV();
-	const int rc = flanhip_smear_time_dev( reinterpret_cast<const flanhip_MF*>( d_pv ), get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(), get_hop_size(),
-		d_smear ? static_cast<const float*>( d_smear->ptr ) : nullptr, smear_size.is_constant() ? smear_size.get_constant() : 0.0f,
-		d_gran ? static_cast<const int32_t*>( d_gran->ptr ) : nullptr, granularity.is_constant() ? granularity.get_constant() : 0,
-		d_dist ? static_cast<const float*>( d_dist->ptr ) : nullptr, int64_t( dist.size() ), true_left, Fo, static_cast<flanhip_MF*>( out->ptr ), nullptr );
-	return finish( rc, "smear_time", f, std::move( out ) );
+	return pv_call( "smear_time", *this, f, d_dist.ok, [&]( const flanhip_MF * d_pv, flanhip_MF * out )
+		{
+		return flanhip_smear_time_dev( d_pv, get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate(), get_hop_size(),
+			d_smear.ptr(), smear_size.is_constant() ? smear_size.get_constant() : 0.0f, d_gran.ptr<int32_t>(), granularity.is_constant() ? granularity.get_constant() : 0,
+			d_dist.ptr(), int64_t( dist.size() ), true_left, Fo, out, nullptr );
+		} );
 	}
 
 // harmonic_scaler, PV.cpp:362-407
@@ -708,13 +641,9 @@ static PV harmonic_scale( const PV & me, const Function<std::pair<Second, Harmon
 		const Second t = me.frame_to_time( fFrame( frame ) );
 		for( size_t h = 0; h < H; ++h ) sampled[h + size_t( frame ) * H] = series( std::pair<Second, Harmonic>( t, Harmonic( h ) ) );
 		}, 16 );
-	auto d_series = H ? upload( sampled.data(), sizeof( float ) * sampled.size() ) : nullptr;
-	const MF * d_pv = me.device_data();
-	auto out = DeviceBlock::allocate( sizeof( MF ) * mf_count( me.get_format() ) );
-	if( ( H && !d_series ) || !d_pv || !out ) return PV();
-	const int rc = flanhip_harmonic_scale_dev( reinterpret_cast<const flanhip_MF*>( d_pv ), me.get_num_channels(), frames, me.get_num_bins(), me.get_sample_rate(),
-		d_series ? static_cast<const float*>( d_series->ptr ) : nullptr, int( H ), mode, static_cast<flanhip_MF*>( out->ptr ), nullptr );
-	return finish( rc, mode == 0 ? "add_octaves" : "add_harmonics", me.get_format(), std::move( out ) );
+	const DeviceArg d_series = H ? DeviceArg( upload( sampled.data(), sizeof( float ) * sampled.size() ) ) : DeviceArg();
+	return pv_call( mode == 0 ? "add_octaves" : "add_harmonics", me, me.get_format(), d_series.ok, [&]( const flanhip_MF * d_pv, flanhip_MF * out )
+		{ return flanhip_harmonic_scale_dev( d_pv, me.get_num_channels(), frames, me.get_num_bins(), me.get_sample_rate(), d_series.ptr(), int( H ), mode, out, nullptr ); } );
 	}
 
 PV PV::add_octaves( const Function<std::pair<Second, Harmonic>, float> & series ) const
@@ -737,12 +666,8 @@ PV PV::cut_frames( Frame start, Frame end ) const
 	if( count <= 0 ) return PV::create_null();                                      // (an empty range gives an empty = null PV there too)
 	PVBuffer::Format f = get_format();
 	f.num_frames = count;
-	const MF * d_pv = device_data();
-	auto out = DeviceBlock::allocate( sizeof( MF ) * mf_count( f ) );
-	if( !d_pv || !out ) return PV();
-	const int rc = flanhip_cut_frames_dev( reinterpret_cast<const flanhip_MF*>( d_pv ), get_num_channels(), get_num_frames(), get_num_bins(), first, count,
-		static_cast<flanhip_MF*>( out->ptr ), nullptr );
-	return finish( rc, "cut_frames", f, std::move( out ) );
+	return pv_call( "cut_frames", *this, f, true, [&]( const flanhip_MF * d_pv, flanhip_MF * out )
+		{ return flanhip_cut_frames_dev( d_pv, get_num_channels(), get_num_frames(), get_num_bins(), first, count, out, nullptr ); } );
 	}
 
 std::vector<PV> PV::split_at_times( std::vector<Second> split_times ) const
@@ -773,20 +698,21 @@ PV PV::join( const std::vector<const PV *> & ins )
 	for( const PV * x : ins ) total += x->get_num_frames();                         // :705
 	if( total <= 0 || total > INT32_MAX ) return PV::create_null();
 	f.num_frames = Frame( total );
-	auto out = DeviceBlock::allocate( sizeof( MF ) * mf_count( f ) );
+	DeviceCall call( "join" );
+	flanhip_MF * out = call.output<flanhip_MF>( mf_count( f ) );
 	if( !out ) return PV();
-	if( !detail::report( flanhip_memset( out->ptr, 0, sizeof( MF ) * mf_count( f ), nullptr ), "join" ) ) return PV();   // :706-707
+	if( !call.launch( flanhip_memset( out, 0, sizeof( MF ) * mf_count( f ), nullptr ) ) ) return PV();   // :706-707
 	int64_t at = 0;
 	for( const PV * x : ins )                                                       // :709-717
 		{
 		if( x->get_num_frames() <= 0 || x->get_num_channels() <= 0 || x->get_num_bins() <= 0 ) continue;
 		const MF * d_in = x->device_data();
 		if( !d_in ) return PV();
-		if( !detail::report( flanhip_place_frames_dev( reinterpret_cast<const flanhip_MF*>( d_in ), x->get_num_channels(), x->get_num_frames(), x->get_num_bins(),
-				static_cast<flanhip_MF*>( out->ptr ), f.num_channels, f.num_frames, f.num_bins, at, nullptr ), "join" ) ) return PV();
+		if( !call.launch( flanhip_place_frames_dev( as_c( d_in ), x->get_num_channels(), x->get_num_frames(), x->get_num_bins(),
+				out, f.num_channels, f.num_frames, f.num_bins, at, nullptr ) ) ) return PV();
 		at += x->get_num_frames();
 		}
-	return finish( FLANHIP_OK, "join", f, std::move( out ) );
+	return call.finish<PVBuffer>( f );
 	}
 
 PV PV::join( const std::vector<PV> & ins )

@@ -2,15 +2,16 @@
 // SPV::convert_to_audio / convert_to_lr_audio (:110-150), SPV::modify_frequency / repitch (SPV/SPV.cpp:21-44).
 #include "flan/SPV.h"
 
+#include <algorithm>
 #include <iostream>
 #include <utility>
 
-#include "device_block.h"
+#include "device_call.h"
 #include "flan/Audio.h"
 
 namespace flan {
 
-using detail::DeviceBlock;
+using detail::DeviceCall;
 
 SPV::SPV() : SPVBuffer() {}
 SPV::SPV( SPVBuffer && other ) : SPVBuffer( std::move( other ) ) {}
@@ -28,14 +29,12 @@ SPV Audio::convert_to_SPV( Bin dft_size, flan_CANCEL_ARG_CPP ) const
 	f.sample_rate = get_sample_rate();
 	const float * d_audio = device_data();
 	if( !d_audio ) return SPV();
-	auto block = DeviceBlock::allocate( sizeof( MF ) * size_t( f.num_channels ) * size_t( f.num_frames ) * size_t( f.num_bins ) );
-	if( !block ) return SPV();
-	if( !detail::report( flanhip_spv_analyze_dev( d_audio, f.num_channels, f.num_frames, f.sample_rate, f.num_bins,
-			static_cast<flanhip_MF*>( block->ptr ), nullptr ), "convert_to_SPV" ) ) return SPV();
-	const int waited = flanhip_wait_cancellable_fn( nullptr, detail::poll_canceller, &canceller );
-	if( waited == FLANHIP_ERR_CANCELLED || canceller ) return SPV();
-	if( !detail::report( waited, "convert_to_SPV" ) ) return SPV();
-	return SPVBuffer::adopt_device( f, std::move( block ) );
+	DeviceCall call( "convert_to_SPV" );
+	flanhip_MF * d_spv = call.output<flanhip_MF>( size_t( f.num_channels ) * size_t( f.num_frames ) * size_t( f.num_bins ) );
+	if( !d_spv ) return SPV();
+	if( !call.launch( flanhip_spv_analyze_dev( d_audio, f.num_channels, f.num_frames, f.sample_rate, f.num_bins, d_spv, nullptr ) ) ) return SPV();
+	if( call.wait( canceller ) == FLANHIP_ERR_CANCELLED || canceller ) return SPV();
+	return call.finish<SPVBuffer>( f );
 	}
 
 SPV Audio::convert_to_ms_SPV( Bin dft_size, flan_CANCEL_ARG_CPP ) const
@@ -53,15 +52,17 @@ Audio SPV::convert_to_audio( flan_CANCEL_ARG_CPP ) const
 	af.sample_rate = get_sample_rate();
 	const MF * d_spv = device_data();
 	if( !d_spv ) return Audio::create_null();
-	auto out = DeviceBlock::allocate( sizeof( float ) * size_t( af.num_channels ) * size_t( af.num_frames ) );
-	auto ws = DeviceBlock::allocate( flanhip_spv_synthesize_workspace_bytes( get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate() ) );
-	if( !out || !ws ) return Audio::create_null();
-	if( !detail::report( flanhip_spv_synthesize_dev( reinterpret_cast<const flanhip_MF*>( d_spv ), get_num_channels(), get_num_frames(),
-			get_num_bins(), get_sample_rate(), static_cast<float*>( out->ptr ), ws->ptr, nullptr ), "SPV::convert_to_audio" ) ) return Audio::create_null();
-	const int waited = flanhip_wait_cancellable_fn( nullptr, detail::poll_canceller, &canceller );
-	if( waited == FLANHIP_ERR_CANCELLED || canceller ) return Audio::create_null();
-	if( !detail::report( waited, "SPV::convert_to_audio" ) ) return Audio::create_null();
-	return AudioBuffer::adopt_device( af, std::move( out ) );
+	DeviceCall call( "SPV::convert_to_audio" );
+	float * out = call.output<float>( size_t( af.num_channels ) * size_t( af.num_frames ) );
+	// (a shape the device does not take is the launch's to refuse and report: no 0 bytes reach the skeleton)
+	void * ws = call.workspace( std::max<size_t>( flanhip_spv_synthesize_workspace_bytes( get_num_channels(), get_num_frames(), get_num_bins(), get_sample_rate() ), 1 ) );
+	if( !call.ok() ) return Audio::create_null();
+	if( !call.launch( flanhip_spv_synthesize_dev( reinterpret_cast<const flanhip_MF*>( d_spv ), get_num_channels(), get_num_frames(),
+			get_num_bins(), get_sample_rate(), out, ws, nullptr ) ) ) return Audio::create_null();
+	if( call.wait( canceller ) == FLANHIP_ERR_CANCELLED || canceller ) return Audio::create_null();
+	AudioBuffer audio = call.finish<AudioBuffer>( af );
+	if( !call.ok() ) return Audio::create_null();
+	return Audio( std::move( audio ) );
 	}
 
 Audio SPV::convert_to_lr_audio( flan_CANCEL_ARG_CPP ) const
@@ -74,12 +75,11 @@ namespace {
 SPV modify_frequency_const( const SPV & in, float c, int multiply )
 	{
 	const MF * d_in = in.device_data();
-	auto out = DeviceBlock::allocate( sizeof( MF ) * size_t( in.get_num_channels() ) * size_t( in.get_num_frames() ) * size_t( in.get_num_bins() ) );
-	if( !d_in || !out ) return SPV();
-	if( !detail::report( flanhip_spv_modify_frequency_const_dev( reinterpret_cast<const flanhip_MF*>( d_in ), in.get_num_channels(), in.get_num_frames(),
-			in.get_num_bins(), c, multiply, static_cast<flanhip_MF*>( out->ptr ), nullptr ), "SPV::modify_frequency" ) ) return SPV();
-	if( !detail::report( flanhip_stream_synchronize( nullptr ), "SPV::modify_frequency" ) ) return SPV();
-	return SPVBuffer::adopt_device( in.get_format(), std::move( out ) );
+	const size_t count = size_t( in.get_num_channels() ) * size_t( in.get_num_frames() ) * size_t( in.get_num_bins() );
+	return detail::device_call<SPVBuffer, flanhip_MF>( "SPV::modify_frequency", in.get_format(), count, d_in != nullptr, detail::kNoWorkspace, [&]( flanhip_MF * out, void * )
+		{
+		return flanhip_spv_modify_frequency_const_dev( reinterpret_cast<const flanhip_MF*>( d_in ), in.get_num_channels(), in.get_num_frames(), in.get_num_bins(), c, multiply, out, nullptr );
+		} );
 	}
 }
 

@@ -9,8 +9,9 @@
 
 namespace flan { namespace detail {
 
-// host_runtime.cpp: blocks come from, and go back to, a cache of idle HBM blocks (every method synchronises before it returns,
-// so a block whose owner dies is idle); flanhip_malloc / flanhip_free only when the cache cannot serve.
+// host_runtime.cpp: blocks come from, and go back to, a cache of idle HBM blocks; flanhip_malloc / flanhip_free only when the cache
+// cannot serve.  A block whose owner dies must be idle: every method synchronises before it lets one go, on its failure paths too --
+// DeviceCall (device_call.h) enforces that for the null stream, DmaQuiesce (PV.cpp) for the copy streams of the upload helpers.
 void * device_acquire( size_t bytes, size_t * capacity, int * device );   // nullptr on failure (flanhip_last_error() says why)
 void device_release( void * ptr, size_t capacity, int device ) noexcept;
 void device_cache_flush() noexcept;                   // give every idle block back to the device

@@ -4,30 +4,15 @@ harmonic scaler) equals the table's NumPy restatement bit for bit -- so a case t
 callable that the two sides read differently -- and the table is whole: unique names, every method of include/flan/PV.h held."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_cpp
 import pv_methods_reference as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "cpp", "pv_methods_test")
-
-
-def build_driver():
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "flan_amd", "host")], check=True)
-    src = os.path.join(ROOT, "tests", "cpp", "pv_methods_test.cpp")
-    deps = [src, os.path.join(ROOT, "flan_amd", "libflan_host.so")]
-    if not os.path.exists(BIN) or any(os.path.getmtime(d) > os.path.getmtime(BIN) for d in deps):
-        subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), src, "-o", BIN,
-                        "-L" + os.path.join(ROOT, "flan_amd"), "-lflan_host", "-lflanhip",
-                        "-Wl,-rpath," + os.path.join(ROOT, "flan_amd"), "-lpthread"], check=True)
-
-
-def run_driver(*args, timeout=300):
-    env = dict(os.environ, LD_LIBRARY_PATH=os.path.join(ROOT, "flan_amd") + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
-    return subprocess.run([BIN] + list(args), capture_output=True, text=True, env=env, timeout=timeout)
+ROOT = host_cpp.ROOT
+BIN, build_driver, run_driver = host_cpp.driver("pv_methods_test", check=False, timeout=300)   # run_driver( *args, timeout=300 ): the caller checks
 
 
 def sample_only(out_dir):

@@ -2,39 +2,18 @@
 answer (and, without a device, a loud failure with a null result); on a device, cases of the reference-made fixture through
 Audio::repitch from the factors before inversion -- 0, negative and 1e-6 among them, so the method's own clamp is what is checked --
 against the C ABI bit for bit and the reference-made output, a ramp for the Function sampling, and the length of a constant Function."""
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_cpp
 import repitch_reference as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "cpp", "repitch_test")
+BIN, _build, _run = host_cpp.driver("repitch_test")
 FIXTURE_CASES = ("up1p5", "step", "u_down0p7", "zero", "negative", "tiny")
 # the factors of the clamp cases before inversion (golden/ref_made/make_wdl_repitch.py); the fixture keeps only what the clamp made of them
 RAW_FACTORS = {"zero": 0.0, "negative": -2.0, "tiny": 1e-6}
-
-
-def _build():
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "flan_amd", "host")], check=True)
-    src = os.path.join(ROOT, "tests", "cpp", "repitch_test.cpp")
-    deps = [src, os.path.join(ROOT, "flan_amd", "libflan_host.so")]
-    if not os.path.exists(BIN) or any(os.path.getmtime(d) > os.path.getmtime(BIN) for d in deps):
-        subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), src, "-o", BIN,
-                        "-L" + os.path.join(ROOT, "flan_amd"), "-lflan_host", "-lflanhip",
-                        "-Wl,-rpath," + os.path.join(ROOT, "flan_amd"), "-lpthread"], check=True)
-
-
-def _run(*args):
-    env = dict(os.environ, LD_LIBRARY_PATH=os.path.join(ROOT, "flan_amd") + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
-    r = subprocess.run([BIN] + list(args), capture_output=True, text=True, env=env, timeout=600)
-    print(r.stdout, r.stderr)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "PASSED" in r.stdout
-    return r
 
 
 def _write_fixture(path):
