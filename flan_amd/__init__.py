@@ -794,24 +794,31 @@ def audio_repitch_out_frames(inv_factors, granularity_frames):
     return int(lib.flanhip_audio_repitch_out_frames(_ptr(inv), inv.size, granularity_frames))
 
 
+def _block_plan(fields, call, total_name):
+    """A host plan's two calls: count the blocks, then fill one array per ( name, dtype ) of `fields`.  call( capacity, pointers, total )
+    makes the C call (pointers: one per field, all None while counting; total: a reference to the int64 the plan also returns) and gives
+    the number of blocks or an error code.  A dict of the arrays, and the total under `total_name`."""
+    total = _i64(0)
+    blocks = call(0, [None] * len(fields), C.byref(total))
+    if blocks < 0:
+        check(int(blocks))
+    p = {name: np.empty(blocks, dtype) for name, dtype in fields}
+    got = call(blocks, [_ptr(p[name]) for name, _ in fields], C.byref(total))
+    assert got == blocks
+    p[total_name] = int(total.value)
+    return p
+
+
+_PLAN_FIELDS = [("offset", np.int64), ("fracpos", np.float64), ("ratio", np.float64), ("filtpos", np.float64), ("oversize", np.int32),
+                ("ideal", np.int32), ("first_out", np.int64)]
+
+
 def audio_repitch_plan(num_frames, sample_rate, inv_factors, granularity_frames, quality=REPITCH_SINC):
     """The block loop on the host: a dict of per-block arrays (offset, fracpos, ratio, filtpos, oversize, ideal, first_out, wanted) and
     out_frames."""
     inv = np.ascontiguousarray(inv_factors, np.float32)
-    nout = _i64(0)
-    blocks = lib.flanhip_audio_repitch_plan(num_frames, sample_rate, _ptr(inv), inv.size, granularity_frames, quality, 0,
-                                            None, None, None, None, None, None, None, None, C.byref(nout))
-    if blocks < 0:
-        check(int(blocks))
-    p = {"offset": np.empty(blocks, np.int64), "fracpos": np.empty(blocks, np.float64), "ratio": np.empty(blocks, np.float64),
-         "filtpos": np.empty(blocks, np.float64), "oversize": np.empty(blocks, np.int32), "ideal": np.empty(blocks, np.int32),
-         "first_out": np.empty(blocks, np.int64), "wanted": np.empty(blocks, np.int32)}
-    got = lib.flanhip_audio_repitch_plan(num_frames, sample_rate, _ptr(inv), inv.size, granularity_frames, quality, blocks,
-                                         _ptr(p["offset"]), _ptr(p["fracpos"]), _ptr(p["ratio"]), _ptr(p["filtpos"]), _ptr(p["oversize"]),
-                                         _ptr(p["ideal"]), _ptr(p["first_out"]), _ptr(p["wanted"]), C.byref(nout))
-    assert got == blocks
-    p["out_frames"] = int(nout.value)
-    return p
+    return _block_plan(_PLAN_FIELDS + [("wanted", np.int32)], lambda capacity, pointers, total: lib.flanhip_audio_repitch_plan(
+        num_frames, sample_rate, _ptr(inv), inv.size, granularity_frames, quality, capacity, *pointers, total), "out_frames")
 
 
 def audio_repitch_workspace_bytes(num_frames, sample_rate, inv_factors, granularity_frames, quality=REPITCH_SINC):
@@ -1231,20 +1238,8 @@ def spatial_itd_plan(num_frames, sample_rate, stretches):
     """The block loop on the host: a dict of per-block arrays (offset, fracpos, ratio, filtpos, oversize, ideal, first_out, delivered,
     buffered) and total_out."""
     st = np.ascontiguousarray(stretches, np.float64)
-    total = _i64(0)
-    blocks = lib.flanhip_spatial_itd_plan(num_frames, sample_rate, _ptr(st), st.size, 0, None, None, None, None, None, None, None, None, None,
-                                          C.byref(total))
-    if blocks < 0:
-        check(int(blocks))
-    p = {"offset": np.empty(blocks, np.int64), "fracpos": np.empty(blocks, np.float64), "ratio": np.empty(blocks, np.float64),
-         "filtpos": np.empty(blocks, np.float64), "oversize": np.empty(blocks, np.int32), "ideal": np.empty(blocks, np.int32),
-         "first_out": np.empty(blocks, np.int64), "delivered": np.empty(blocks, np.int32), "buffered": np.empty(blocks, np.int32)}
-    got = lib.flanhip_spatial_itd_plan(num_frames, sample_rate, _ptr(st), st.size, blocks, _ptr(p["offset"]), _ptr(p["fracpos"]), _ptr(p["ratio"]),
-                                       _ptr(p["filtpos"]), _ptr(p["oversize"]), _ptr(p["ideal"]), _ptr(p["first_out"]), _ptr(p["delivered"]),
-                                       _ptr(p["buffered"]), C.byref(total))
-    assert got == blocks
-    p["total_out"] = int(total.value)
-    return p
+    return _block_plan(_PLAN_FIELDS + [("delivered", np.int32), ("buffered", np.int32)], lambda capacity, pointers, total:
+                       lib.flanhip_spatial_itd_plan(num_frames, sample_rate, _ptr(st), st.size, capacity, *pointers, total), "total_out")
 
 
 def spatial_itd_workspace_bytes(num_frames, sample_rate, stretches):

@@ -10,6 +10,7 @@
 #include <memory>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "flanhip.h"
@@ -45,6 +46,11 @@ int launch_kernel( const char * who, K kern, int64_t blocks, int threads, size_t
 	}
 // a typed pointer `offset` bytes into a workspace
 template<typename T> T * ws_at( void * d_ws, size_t offset ) { return reinterpret_cast<T*>( static_cast<char*>( d_ws ) + offset ); }
+
+inline bool aligned16( const void * p ) { return ( reinterpret_cast<uintptr_t>( p ) & 15 ) == 0; }
+// the { 16-byte loads, plain } pair of a kernel template from one bool: launch( V ) launches the instantiation with VEC = V.value
+// (a generic lambda's `auto V` may stand in a template argument as V.value: std::true_type is empty, reading V reads no object)
+template<typename L> int scan_pair( bool vec, L launch ) { return vec ? launch( std::true_type{} ) : launch( std::false_type{} ); }
 
 inline bool is_pow2( int64_t n ) { return n > 0 && ( n & ( n - 1 ) ) == 0; }
 inline int ilog2( int64_t n ) { int l = 0; while( ( int64_t( 1 ) << l ) < n ) ++l; return l; }

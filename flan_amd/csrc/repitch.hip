@@ -4,13 +4,14 @@
 // The reference feeds one resampler block after block on one thread.  Its state between blocks is two numbers (the fractional read
 // position and how many samples stay buffered), which a host loop reproduces exactly in fp64 (repitch_plan: O( output frames )
 // additions); after that every output sample is an independent 64-tap sum (two of them, interpolated, unless the rates are "ideal")
-// over a window of one continuous stream: 31 zeros, the input, zeros.
-//   k_repitch_window   the Blackman-Harris factor of every table entry, per oversize in use, in fp64 (once per call)
+// over a window of one continuous stream: 31 zeros, the input, zeros.  The resampler itself -- the choice of table, the table, the tap
+// sums, the stream -- is wdl_sinc.h's, shared with spatial.hip; the plan, the runs and the kernels around them are this file's.
+//   k_wdl_window<64>   the Blackman-Harris factor of every table entry, per oversize in use, in fp64 (once per call)
 //   k_repitch_sinc     one workgroup per run of consecutive blocks that share a coefficient table: builds the table in LDS, stages the
 //                      run's input window in LDS when it fits, one output sample per thread per channel
 //   k_repitch_point    the Uninterpolated quality: in[ int( srcpos ) ]
 // Every sum runs in a fixed order and nothing is atomic, so two runs agree bit for bit.
-#include "flanhip_internal.h"
+#include "wdl_sinc.h"
 
 #include <algorithm>
 
@@ -19,15 +20,10 @@ namespace flanhip {
 namespace {
 
 constexpr int RP_TAPS = 64;                    // SetMode( true, 0, true, 64 ): m_sincsize
-constexpr int RP_OVERSIZE = 32;                // m_sincoversize (SetMode's default), the slices of a table that is not "ideal"
-constexpr int RP_MAX_OVERSIZE = 2 * RP_OVERSIZE;               // an ideal table may have up to 2 x 32 slices (:1135)
-constexpr int RP_PRELUDE = RP_TAPS / 2 - 1;    // zeros in front of the stream (:1226-1237)
-constexpr int RP_THREADS = 256;
-constexpr int RP_SLICE_STRIDE = RP_TAPS + 1;   // LDS floats per table slice: lanes read tap i of DIFFERENT slices, 65 spreads them over the 64 banks
-constexpr int RP_TABLE_FLOATS = ( RP_MAX_OVERSIZE + 1 ) * RP_SLICE_STRIDE;
+using Rp = WdlSinc<RP_TAPS>;
+constexpr int RP_THREADS = WDL_THREADS;
 constexpr int RP_WINDOW_FLOATS = 6144;         // the staged input window of a run (24 KiB); a longer one is read from global memory
 constexpr int RP_RUN_OUTPUTS = 2048;           // output frames per run at most (8 per thread)
-constexpr int RP_WIN_SLOT = ( RP_MAX_OVERSIZE + 1 ) * ( RP_TAPS / 2 );   // doubles per oversize in the window-factor table (its largest half table)
 constexpr int64_t RP_MAX_FRAMES = int64_t( 1 ) << 40;
 constexpr int64_t RP_MAX_WORK = int64_t( 1 ) << 33;     // blocks x granularity the host loop accepts (its additions)
 constexpr int64_t RP_MAX_BLOCKS = int64_t( 1 ) << 22;   // blocks a call may have: 56 bytes of record each on the host and in the workspace (224 MiB)
@@ -68,45 +64,12 @@ int64_t rp_out_frames( const float * inv, int64_t count, int64_t g )
 	return frames >= 9.0e18f ? INT64_MAX : int64_t( frames );
 	}
 
-// BuildLowPass's choice of table (:1095-1141) for SetMode( true, 0, true, 64 )
-void rp_table_shape( double rate_in, double rate_out, double ratio, double * filtpos, int * oversize, int * ideal )
-	{
-	*filtpos = ratio > 1.0 ? 1.0 / ( ratio * 1.03 ) : 1.0;                   // :1327-1328
-	int want = RP_OVERSIZE, ideal_interp = 0;
-	if( ratio < 1.0 )
-		{
-		const double drat = rate_out / rate_in;
-		const int irat = int( drat + 0.5 );
-		if( irat > 1 && irat == drat ) ideal_interp = irat;
-		}
-	else
-		{
-		const int irat = int( ratio + 0.5 );
-		if( ratio == irat ) ideal_interp = 1;
-		}
-	if( !ideal_interp && rate_in < 2147483648.0 && rate_out < 2147483648.0 )
-		{
-		const int in1 = int( rate_in ), out1 = int( rate_out );
-		if( out1 > 0 && in1 > 0 && rate_in == double( in1 ) && rate_out == double( out1 ) )
-			{
-			int min_cd = out1 / ( 2 * want );
-			if( min_cd < 1 ) min_cd = 1;
-			int n1 = out1, n2 = in1;
-			while( n2 >= min_cd ) { const int tmp = n1; n1 = n2; n2 = tmp % n2; }
-			if( !n2 ) ideal_interp = out1 / n1;
-			}
-		}
-	if( ideal_interp > 0 && ideal_interp <= want * 2 ) want = ideal_interp;
-	*oversize = want;
-	*ideal = ideal_interp == want;
-	}
-
 // The block loop of :267-296 with the state of ResamplePrepare (:1218-1265) and ResampleOut (:1313, :1558-1566), in fp64 with the
 // reference's own chain of srcpos += ratio.  keep: store the records (else count only).  FLANHIP_OK, or why the loop cannot run.
 int rp_plan( int64_t n, float sr, const float * inv, int64_t count, int64_t g, int quality, bool keep, RpPlan * out, int64_t * num_blocks )
 	{
 	const int fsize = quality == FLANHIP_REPITCH_SINC ? RP_TAPS : 0;
-	const int64_t prelude = fsize ? RP_PRELUDE : 0;
+	const int64_t prelude = fsize ? Rp::PRELUDE : 0;
 	const double rate_in = std::max( double( sr ), 1.0 );                     // SetRates (:1080-1090)
 	double fracpos = 0.0;
 	int64_t S = 0, in_frame = 0, out_frame = 0, offset = 0, blocks = 0;
@@ -125,13 +88,11 @@ int rp_plan( int64_t n, float sr, const float * inv, int64_t count, int64_t g, i
 		RpBlock b{};
 		b.offset = offset; b.fracpos = fracpos; b.ratio = ratio; b.first_out = out_frame; b.wanted = int32_t( std::min<int64_t>( wanted, INT32_MAX ) );
 		b.filtpos = 1.0; b.oversize = 1; b.ideal = 0;
-		if( fsize ) rp_table_shape( rate_in, rate_out, ratio, &b.filtpos, &b.oversize, &b.ideal );
+		if( fsize ) wdl_table_shape( rate_in, rate_out, ratio, &b.filtpos, &b.oversize, &b.ideal );
 		if( keep ) out->blocks.push_back( b );
 		double srcpos = fracpos;
 		for( int64_t j = 0; j < g; ++j ) srcpos += ratio;
-		const int64_t isrcpos = std::min( int64_t( srcpos ), S );                // :1558-1559
-		fracpos = srcpos - double( isrcpos );
-		if( fsize && b.ideal ) fracpos = std::floor( b.oversize * fracpos + 0.5 ) / b.oversize;   // :1562-1563
+		const int64_t isrcpos = wdl_hand_over( srcpos, S, b.ideal, b.oversize, &fracpos );      // (ideal is 0 without a table)
 		S -= isrcpos;
 		offset += isrcpos;
 		in_frame += wanted;
@@ -174,77 +135,14 @@ void rp_runs( const RpPlan & plan, int64_t g, int quality, std::vector<RpRun> * 
 		}
 	}
 
-struct RpLayout { size_t win_off, block_off, run_off, total; };
-
-RpLayout rp_layout( int64_t num_blocks, int64_t num_runs )
-	{
-	RpLayout l;
-	l.win_off = 0;
-	l.block_off = sizeof( double ) * size_t( RP_MAX_OVERSIZE ) * RP_WIN_SLOT;
-	l.run_off = l.block_off + sizeof( RpBlock ) * size_t( num_blocks );
-	l.total = l.run_off + sizeof( RpRun ) * size_t( num_runs );
-	return l;
-	}
-
-// sample `s` of the stream: `prelude` zeros, the n input frames, zeros
-__device__ __forceinline__ float rp_stream( const float * __restrict__ x, int64_t n, int64_t prelude, int64_t s )
-	{
-	const int64_t t = s - prelude;
-	return ( t >= 0 && t < n ) ? x[t] : 0.0f;
-	}
-
-// half table entry e is ( slice e / 64, tap e % 64 ): every slice but the last has 64 entries (:1164-1171)
-__global__ __launch_bounds__( RP_THREADS ) void k_repitch_window( double * __restrict__ win, uint64_t used )
-	{
-	const int oversize = int( blockIdx.x ) + 1;
-	if( !( ( used >> blockIdx.x ) & 1 ) ) return;
-	const int half = ( RP_TAPS / 2 ) * ( oversize + 1 );
-	double * w = win + size_t( blockIdx.x ) * RP_WIN_SLOT;
-	const double dwindowpos = 2.0 * 3.1415926535897932384626433832795 / double( RP_TAPS );       // :1157
-	for( int e = threadIdx.x; e < half; e += RP_THREADS )
-		{
-		const double frac = double( e / RP_TAPS ) / double( oversize );
-		const double xfrac = frac + double( e % RP_TAPS );
-		const double windowpos = dwindowpos * xfrac;
-		w[e] = 0.35875 - 0.48829 * cos( windowpos ) + 0.14128 * cos( 2 * windowpos ) - 0.01168 * cos( 3 * windowpos );   // :1185
-		}
-	}
-
-// 64 taps: float products (each rounded), added into fp64 in tap order (the SincSample templates, :106-257, with float samples and coefficients)
-template<bool LDS_IN>
-__device__ __forceinline__ void rp_taps2( const float * f1, const float * f2, const float * in_lds, const float * __restrict__ x, int64_t n, int64_t s0,
-	double * sum, double * sum2 )
-	{
-	double a = 0.0, b = 0.0;
-	#pragma unroll 8
-	for( int i = 0; i < RP_TAPS; ++i )
-		{
-		const float v = LDS_IN ? in_lds[i] : rp_stream( x, n, RP_PRELUDE, s0 + i );
-		a += double( __fmul_rn( f1[i], v ) );
-		b += double( __fmul_rn( f2[i], v ) );
-		}
-	*sum = a; *sum2 = b;
-	}
-
-template<bool LDS_IN>
-__device__ __forceinline__ double rp_taps1( const float * f2, const float * in_lds, const float * __restrict__ x, int64_t n, int64_t s0 )
-	{
-	double b = 0.0;
-	#pragma unroll 8
-	for( int i = 0; i < RP_TAPS; ++i )
-		{
-		const float v = LDS_IN ? in_lds[i] : rp_stream( x, n, RP_PRELUDE, s0 + i );
-		b += double( __fmul_rn( f2[i], v ) );
-		}
-	return b;
-	}
+WdlLayout rp_layout( int64_t num_blocks, int64_t num_runs ) { return wdl_layout<RP_TAPS>( sizeof( RpBlock ), num_blocks, sizeof( RpRun ), num_runs ); }
 
 // grid: runs x channel groups of `cpw` channels.  x float[ch][n], out float[ch][out_frames].
 __global__ __launch_bounds__( RP_THREADS ) void k_repitch_sinc( const float * __restrict__ x, int64_t ch, int64_t n, int64_t g, int64_t out_frames,
 	const RpBlock * __restrict__ blocks, const RpRun * __restrict__ runs, const double * __restrict__ win, int64_t groups, int cpw,
 	float * __restrict__ out )
 	{
-	__shared__ float s_tab[RP_TABLE_FLOATS];
+	__shared__ float s_tab[Rp::TABLE_FLOATS];
 	__shared__ float s_in[RP_WINDOW_FLOATS];
 	__shared__ double s_red[RP_THREADS];
 	const int lane = threadIdx.x;
@@ -252,43 +150,7 @@ __global__ __launch_bounds__( RP_THREADS ) void k_repitch_sinc( const float * __
 	const int64_t c0 = ( int64_t( blockIdx.x ) - run_index * groups ) * cpw;
 	const RpRun run = runs[run_index];
 	const int oversize = run.oversize;
-	const int half = ( RP_TAPS / 2 ) * ( oversize + 1 );
-
-	// the table (BuildLowPass :1157-1202): window x sinc in fp64 rounded to float; filtpower in a fixed order (each thread its own
-	// entries in rising order, then a tree over the threads); the first half scaled and rounded again; the second half mirrors it
-	const double dsincpos = 3.1415926535897932384626433832795 * run.filtpos;
-	const double * w = win + size_t( oversize - 1 ) * RP_WIN_SLOT;
-	double power = 0.0;
-	for( int e = lane; e < half; e += RP_THREADS )
-		{
-		const int slice = e / RP_TAPS, tap = e % RP_TAPS;
-		float c = 1.0f;                                                          // the centre tap of slice 0 (:1173-1177)
-		if( e != RP_TAPS / 2 )
-			{
-			const double xfrac = double( slice ) / double( oversize ) + double( tap );
-			const double sincpos = dsincpos * ( xfrac - double( RP_TAPS / 2 ) );
-			const double val = w[e] * sin( sincpos ) / sincpos;
-			power += slice ? val * 2 : val;
-			c = float( val );
-			}
-		s_tab[slice * RP_SLICE_STRIDE + tap] = c;
-		}
-	s_red[lane] = power;
-	__syncthreads();
-	for( int off = RP_THREADS / 2; off > 0; off >>= 1 )
-		{
-		if( lane < off ) s_red[lane] = s_red[lane] + s_red[lane + off];
-		__syncthreads();
-		}
-	const double scale = double( oversize ) / ( s_red[0] + 1.0 );            // :1193
-	for( int e = lane; e < half; e += RP_THREADS )
-		{
-		const int at = ( e / RP_TAPS ) * RP_SLICE_STRIDE + e % RP_TAPS;
-		const float c = float( double( s_tab[at] ) * scale );
-		s_tab[at] = c;
-		const int m = 2 * half - 1 - e;                                          // :1202
-		s_tab[( m / RP_TAPS ) * RP_SLICE_STRIDE + m % RP_TAPS] = c;
-		}
+	wdl_build_table<RP_TAPS>( s_tab, s_red, win + size_t( oversize - 1 ) * Rp::WIN_SLOT, oversize, run.filtpos );
 
 	const int64_t total = int64_t( run.num_blocks ) * g;
 	const int64_t c1 = c0 + cpw < ch ? c0 + cpw : ch;
@@ -296,7 +158,7 @@ __global__ __launch_bounds__( RP_THREADS ) void k_repitch_sinc( const float * __
 		{
 		const float * xc = x + c * n;
 		__syncthreads();                                                         // the table is whole; the last channel's reads of s_in are done
-		for( int i = lane; i < run.win_len; i += RP_THREADS ) s_in[i] = rp_stream( xc, n, RP_PRELUDE, run.win_start + i );
+		for( int i = lane; i < run.win_len; i += RP_THREADS ) s_in[i] = wdl_stream<RP_TAPS>( xc, n, run.win_start + i );
 		__syncthreads();
 		for( int64_t t = lane; t < total; t += RP_THREADS )
 			{
@@ -305,34 +167,7 @@ __global__ __launch_bounds__( RP_THREADS ) void k_repitch_sinc( const float * __
 			const int64_t frame = b.first_out + j;
 			if( frame >= out_frames ) continue;
 			const double srcpos = fma( double( j ), b.ratio, b.fracpos );
-			const int64_t ipos = int64_t( srcpos );
-			const double frac = srcpos - double( ipos );
-			const int64_t s0 = b.offset + ipos;                                  // stream index of tap 0
-			const int64_t rel = s0 - run.win_start;
-			const bool staged = rel >= 0 && rel + RP_TAPS <= int64_t( run.win_len );
-			float y;
-			if( run.ideal )
-				{
-				int ifpos = int( frac * oversize + 0.5 );                        // SincSample1N (:184-200)
-				ifpos = ifpos < 0 ? 0 : ifpos > oversize ? oversize : ifpos;
-				const float * f2 = s_tab + ( oversize - ifpos ) * RP_SLICE_STRIDE;
-				const double sum2 = staged ? rp_taps1<true>( f2, s_in + rel, xc, n, s0 ) : rp_taps1<false>( f2, s_in, xc, n, s0 );
-				y = float( sum2 );
-				}
-			else
-				{
-				double fr = frac * oversize;                                     // SincSample1 (:160-182)
-				int ifpos = int( fr );
-				ifpos = ifpos < 0 ? 0 : ifpos > oversize - 1 ? oversize - 1 : ifpos;
-				fr -= ifpos;
-				const float * f2 = s_tab + ( oversize - ifpos ) * RP_SLICE_STRIDE;
-				const float * f1 = f2 - RP_SLICE_STRIDE;
-				double sum, sum2;
-				if( staged ) rp_taps2<true>( f1, f2, s_in + rel, xc, n, s0, &sum, &sum2 );
-				else rp_taps2<false>( f1, f2, s_in, xc, n, s0, &sum, &sum2 );
-				y = float( __dadd_rn( __dmul_rn( sum, fr ), __dmul_rn( sum2, 1.0 - fr ) ) );
-				}
-			out[c * out_frames + frame] = y;
+			out[c * out_frames + frame] = wdl_sample<RP_TAPS>( s_tab, s_in, run.win_start, run.win_len, xc, n, b.offset, srcpos, oversize, run.ideal );
 			}
 		}
 	}
@@ -351,7 +186,7 @@ __global__ __launch_bounds__( RP_THREADS ) void k_repitch_point( const float * _
 		const int64_t frame = b.first_out + j;
 		if( frame >= out_frames ) continue;
 		const double srcpos = fma( double( j ), b.ratio, b.fracpos );
-		out[c * out_frames + frame] = rp_stream( x + c * n, n, 0, b.offset + int64_t( srcpos ) );
+		out[c * out_frames + frame] = wdl_stream( x + c * n, n, 0, b.offset + int64_t( srcpos ) );
 		}
 	}
 
@@ -402,7 +237,7 @@ int launch_repitch( const float * d_x, int64_t ch, int64_t n, int64_t g, int qua
 	float * d_out, void * d_ws, hipStream_t s )
 	{
 	const int64_t num_blocks = int64_t( plan.blocks.size() );
-	const RpLayout l = rp_layout( num_blocks, int64_t( runs.size() ) );
+	const WdlLayout l = rp_layout( num_blocks, int64_t( runs.size() ) );
 	char * ws = static_cast<char*>( d_ws );
 	FLANHIP_CHECK( hipMemcpyAsync( ws + l.block_off, plan.blocks.data(), sizeof( RpBlock ) * plan.blocks.size(), hipMemcpyHostToDevice, s ) );
 	if( !runs.empty() )
@@ -425,7 +260,7 @@ int launch_repitch( const float * d_x, int64_t ch, int64_t n, int64_t g, int qua
 	uint64_t used = 0;
 	for( const RpRun & r : runs ) used |= uint64_t( 1 ) << ( r.oversize - 1 );
 	double * d_win = (double*) ( ws + l.win_off );
-	if( int rc = launch_kernel( "repitch", k_repitch_window, RP_MAX_OVERSIZE, RP_THREADS, 0, s, d_win, used ) ) return rc;
+	if( int rc = launch_kernel( "repitch", k_wdl_window<RP_TAPS>, WDL_MAX_OVERSIZE, RP_THREADS, 0, s, d_win, used ) ) return rc;
 	const int cpw = rp_cpw( plan, runs, ch, g );
 	const int64_t groups = ( ch + cpw - 1 ) / cpw;
 	return launch_kernel( "repitch", k_repitch_sinc, int64_t( runs.size() ) * groups, RP_THREADS, 0, s, d_x, ch, n, g, plan.out_frames, d_blocks,

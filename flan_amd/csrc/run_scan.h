@@ -9,8 +9,6 @@
 #pragma once
 #include "flanhip_internal.h"
 
-#include <type_traits>
-
 namespace flanhip {
 
 constexpr int SCAN_THREADS = 256;
@@ -26,10 +24,6 @@ inline int64_t scan_blocks( int64_t n, int run )
 	const int64_t per_block = int64_t( SCAN_THREADS ) * run;
 	return ( n + per_block - 1 ) / per_block;
 	}
-inline bool aligned16( const void * p ) { return ( reinterpret_cast<uintptr_t>( p ) & 15 ) == 0; }
-// the { 16-byte loads, plain } pair of a kernel template from one bool: launch( V ) launches the instantiation with VEC = V.value
-// (a generic lambda's `auto V` may stand in a template argument as V.value: std::true_type is empty, reading V reads no object)
-template<typename L> int scan_pair( bool vec, L launch ) { return vec ? launch( std::true_type{} ) : launch( std::false_type{} ); }
 
 // Scan of one map per thread over the block, in thread order: excl = the maps of all earlier threads composed, total = the block's.
 // Every thread of the block calls it.

@@ -6,7 +6,7 @@
 // falloff (:104-114) and an interaural delay that follows the distance and so produces Doppler (head_itd, :135-221).
 //   k_spat_ear         both ears of a frame in one pass: the sinusoidal blend of the input with its 500 Hz low-pass, times 1 / distance
 //   k_spat_delay       head_itd for a source that stands still: a pure delay (:139-153)
-//   k_spat_window      the Blackman-Harris factor of every table entry, per oversize in use, in fp64 (once per call)
+//   k_wdl_window<32>   the Blackman-Harris factor of every table entry, per oversize in use, in fp64 (once per call)
 //   k_spat_itd         head_itd for a moving source.  The reference feeds one WDL_Resampler 32 input frames at a time in FEED mode
 //                      (SetFeedMode( true ), SetMode( true, 0, true, 32 )) with a rate that changes every block; what comes out of a block
 //                      depends on the data.  Between blocks the resampler carries two numbers (the fractional read position and how many
@@ -16,7 +16,7 @@
 //                      share a coefficient table, or a slice of one block whose output count exceeds a run's.
 //   k_pan, k_to_stereo, k_to_mono, k_copy_rows    one pass each, 16 bytes per access where the rows' alignment allows
 // Every sum runs in a fixed order and nothing is atomic, so two runs agree bit for bit.
-#include "flanhip_internal.h"
+#include "wdl_sinc.h"
 
 #include <algorithm>
 
@@ -26,16 +26,11 @@ namespace {
 
 constexpr int SP_G = 32;                       // granularity_frames (:137): input frames per block
 constexpr int SP_TAPS = 32;                    // SetMode( true, 0, true, 32 ): m_sincsize
-constexpr int SP_OVERSIZE = 32;                // m_sincoversize (SetMode's default), the slices of a table that is not "ideal"
-constexpr int SP_MAX_OVERSIZE = 2 * SP_OVERSIZE;               // an ideal table may have up to 2 x 32 slices (WDL/resample.cpp:1135)
-constexpr int SP_PRELUDE = SP_TAPS / 2 - 1;    // zeros in front of the stream (:1226-1237)
-constexpr int SP_THREADS = 256;
-constexpr int SP_SLICE_STRIDE = SP_TAPS + 1;   // LDS floats per table slice: lanes read tap i of DIFFERENT slices, 33 spreads them over the 64 banks
-constexpr int SP_TABLE_FLOATS = ( SP_MAX_OVERSIZE + 1 ) * SP_SLICE_STRIDE;
+using Sp = WdlSinc<SP_TAPS>;                   // the resampler itself is wdl_sinc.h's, shared with repitch.hip
+constexpr int SP_THREADS = WDL_THREADS;
 constexpr int SP_RUN_BLOCKS = 64;              // blocks of a run at most: their records and the prefix of their counts sit in LDS
 constexpr int SP_RUN_OUTPUTS = 2048;           // output frames per run at most (8 per thread)
 constexpr int SP_WINDOW_FLOATS = SP_RUN_BLOCKS * SP_G + 128;   // the staged stream window of a run; what lies outside is read from global memory
-constexpr int SP_WIN_SLOT = ( SP_MAX_OVERSIZE + 1 ) * ( SP_TAPS / 2 );   // doubles per oversize in the window-factor table (its largest half table)
 constexpr int64_t SP_MAX_FRAMES = int64_t( 1 ) << 31;   // the reference's Frame is an int
 constexpr int64_t SP_MAX_BLOCKS = int64_t( 1 ) << 22;   // blocks a call may have per ear: 56 bytes of record each on the host and in the workspace
 constexpr int64_t SP_MAX_WORK = int64_t( 1 ) << 33;     // additions the host loop accepts per ear
@@ -71,40 +66,6 @@ struct SpPlan
 	std::vector<SpBlock> blocks;
 	int64_t total_out = 0;                     // output frames the blocks deliver together
 	};
-
-// BuildLowPass's choice of table (WDL/resample.cpp:1095-1141) for SetMode( true, 0, true, 32 ): repitch.hip's rp_table_shape restated
-// (a function of an unnamed namespace there); neither depends on the tap count
-void sp_table_shape( double rate_in, double rate_out, double ratio, double * filtpos, int * oversize, int * ideal )
-	{
-	*filtpos = ratio > 1.0 ? 1.0 / ( ratio * 1.03 ) : 1.0;                   // :1327-1328
-	int want = SP_OVERSIZE, ideal_interp = 0;
-	if( ratio < 1.0 )
-		{
-		const double drat = rate_out / rate_in;
-		const int irat = int( drat + 0.5 );
-		if( irat > 1 && irat == drat ) ideal_interp = irat;
-		}
-	else
-		{
-		const int irat = int( ratio + 0.5 );
-		if( ratio == irat ) ideal_interp = 1;
-		}
-	if( !ideal_interp && rate_in < 2147483648.0 && rate_out < 2147483648.0 )
-		{
-		const int in1 = int( rate_in ), out1 = int( rate_out );
-		if( out1 > 0 && in1 > 0 && rate_in == double( in1 ) && rate_out == double( out1 ) )
-			{
-			int min_cd = out1 / ( 2 * want );
-			if( min_cd < 1 ) min_cd = 1;
-			int n1 = out1, n2 = in1;
-			while( n2 >= min_cd ) { const int tmp = n1; n1 = n2; n2 = tmp % n2; }
-			if( !n2 ) ideal_interp = out1 / n1;
-			}
-		}
-	if( ideal_interp > 0 && ideal_interp <= want * 2 ) want = ideal_interp;
-	*oversize = want;
-	*ideal = ideal_interp == want;
-	}
 
 int64_t sp_count( int64_t n ) { return ( n + SP_G - 1 ) / SP_G; }              // blocks of the loop of :194, and stretches.size() (:160-170)
 
@@ -146,15 +107,15 @@ int sp_plan( int64_t n, float sr, const double * stretches, int64_t count, bool 
 		if( !( stretch >= SP_MIN_STRETCH && stretch <= SP_MAX_STRETCH ) ) { set_error( "spatial_itd: stretch %g of block %lld is outside [1/16, 1024]", stretch, (long long) b ); return FLANHIP_ERR_INVALID_ARG; }
 		const double rate_out = std::max( double( sr ) * stretch, 1.0 );
 		const double ratio = rate_in / rate_out;
-		if( S < SP_PRELUDE )                                                     // :1226-1237: the first call only
+		if( S < Sp::PRELUDE )                                                     // :1226-1237: the first call only
 			{
 			if( b ) { set_error( "spatial_itd: the buffer ran below the prelude in block %lld", (long long) b ); return FLANHIP_ERR_UNSUPPORTED; }
-			S = SP_PRELUDE;
+			S = Sp::PRELUDE;
 			}
 		S += SP_G;                                                               // :1242, :1295
 		SpBlock r{};
 		r.offset = offset; r.fracpos = fracpos; r.ratio = ratio; r.first_out = out_frame; r.buffered = int32_t( S );
-		sp_table_shape( rate_in, rate_out, ratio, &r.filtpos, &r.oversize, &r.ideal );
+		wdl_table_shape( rate_in, rate_out, ratio, &r.filtpos, &r.oversize, &r.ideal );
 		int64_t ns = int64_t( std::ceil( SP_G * stretch ) );                     // :210
 		const int64_t limit = S - SP_TAPS - 1;                                   // ipos >= filtlen - 1 ends the block (:1343)
 		double srcpos = fracpos;
@@ -162,9 +123,7 @@ int sp_plan( int64_t n, float sr, const double * stretches, int64_t count, bool 
 		while( ns-- && int64_t( srcpos ) < limit ) { srcpos += ratio; ++delivered; }
 		r.count = int32_t( delivered );
 		if( keep ) out->blocks.push_back( r );
-		const int64_t isrcpos = std::min( int64_t( srcpos ), S );                // :1558-1559
-		fracpos = srcpos - double( isrcpos );
-		if( r.ideal ) fracpos = std::floor( r.oversize * fracpos + 0.5 ) / r.oversize;   // :1562-1563
+		const int64_t isrcpos = wdl_hand_over( srcpos, S, r.ideal, r.oversize, &fracpos );
 		S -= isrcpos;
 		offset += isrcpos;
 		out_frame += delivered;
@@ -220,70 +179,10 @@ void sp_runs( const SpPlan & plan, int ear, int64_t keep, std::vector<SpRun> * r
 		}
 	}
 
-struct SpLayout { size_t win_off, block_off, run_off, total; };
-
-// the workspace: the window factors, then every ear's block records one after the other, then all runs
-SpLayout sp_layout( int64_t num_blocks, int64_t num_runs )
+// the workspace: the window factors, then every ear's block records one after the other, then all runs (room for one where there is none)
+WdlLayout sp_layout( int64_t num_blocks, int64_t num_runs )
 	{
-	SpLayout l;
-	l.win_off = 0;
-	l.block_off = sizeof( double ) * size_t( SP_MAX_OVERSIZE ) * SP_WIN_SLOT;
-	l.run_off = l.block_off + sizeof( SpBlock ) * size_t( num_blocks );
-	l.total = l.run_off + sizeof( SpRun ) * size_t( std::max<int64_t>( num_runs, 1 ) );
-	return l;
-	}
-
-// sample `s` of the stream: 15 zeros, the n input frames, zeros
-__device__ __forceinline__ float sp_stream( const float * __restrict__ x, int64_t n, int64_t s )
-	{
-	const int64_t t = s - SP_PRELUDE;
-	return ( t >= 0 && t < n ) ? x[t] : 0.0f;
-	}
-
-// half table entry e is ( slice e / 32, tap e % 32 ): every slice but the last has 32 entries (WDL/resample.cpp:1164-1171)
-__global__ __launch_bounds__( SP_THREADS ) void k_spat_window( double * __restrict__ win, uint64_t used )
-	{
-	const int oversize = int( blockIdx.x ) + 1;
-	if( !( ( used >> blockIdx.x ) & 1 ) ) return;
-	const int half = ( SP_TAPS / 2 ) * ( oversize + 1 );
-	double * w = win + size_t( blockIdx.x ) * SP_WIN_SLOT;
-	const double dwindowpos = 2.0 * 3.1415926535897932384626433832795 / double( SP_TAPS );       // :1157
-	for( int e = threadIdx.x; e < half; e += SP_THREADS )
-		{
-		const double frac = double( e / SP_TAPS ) / double( oversize );
-		const double xfrac = frac + double( e % SP_TAPS );
-		const double windowpos = dwindowpos * xfrac;
-		w[e] = 0.35875 - 0.48829 * cos( windowpos ) + 0.14128 * cos( 2 * windowpos ) - 0.01168 * cos( 3 * windowpos );   // :1185
-		}
-	}
-
-// 32 taps: float products (each rounded), added into fp64 in tap order (the SincSample templates, :160-200, with float samples and coefficients)
-template<bool LDS_IN>
-__device__ __forceinline__ void sp_taps2( const float * f1, const float * f2, const float * in_lds, const float * __restrict__ x, int64_t n, int64_t s0,
-	double * sum, double * sum2 )
-	{
-	double a = 0.0, b = 0.0;
-	#pragma unroll 8
-	for( int i = 0; i < SP_TAPS; ++i )
-		{
-		const float v = LDS_IN ? in_lds[i] : sp_stream( x, n, s0 + i );
-		a += double( __fmul_rn( f1[i], v ) );
-		b += double( __fmul_rn( f2[i], v ) );
-		}
-	*sum = a; *sum2 = b;
-	}
-
-template<bool LDS_IN>
-__device__ __forceinline__ double sp_taps1( const float * f2, const float * in_lds, const float * __restrict__ x, int64_t n, int64_t s0 )
-	{
-	double b = 0.0;
-	#pragma unroll 8
-	for( int i = 0; i < SP_TAPS; ++i )
-		{
-		const float v = LDS_IN ? in_lds[i] : sp_stream( x, n, s0 + i );
-		b += double( __fmul_rn( f2[i], v ) );
-		}
-	return b;
+	return wdl_layout<SP_TAPS>( sizeof( SpBlock ), num_blocks, sizeof( SpRun ), std::max<int64_t>( num_runs, 1 ) );
 	}
 
 struct SpEars                                  // per ear: where its block records start, and how many output frames it keeps
@@ -296,7 +195,7 @@ struct SpEars                                  // per ear: where its block recor
 __global__ __launch_bounds__( SP_THREADS ) void k_spat_itd( const float * __restrict__ x, int64_t n, SpEars ears, int64_t out_stride,
 	const SpBlock * __restrict__ blocks, const SpRun * __restrict__ runs, const double * __restrict__ win, float * __restrict__ out )
 	{
-	__shared__ float s_tab[SP_TABLE_FLOATS];
+	__shared__ float s_tab[Sp::TABLE_FLOATS];
 	__shared__ float s_in[SP_WINDOW_FLOATS];
 	__shared__ double s_red[SP_THREADS];
 	__shared__ SpBlock s_blk[SP_RUN_BLOCKS];
@@ -305,7 +204,6 @@ __global__ __launch_bounds__( SP_THREADS ) void k_spat_itd( const float * __rest
 	const SpRun run = runs[blockIdx.x];
 	const int ear = run.ear;
 	const int oversize = run.oversize;
-	const int half = ( SP_TAPS / 2 ) * ( oversize + 1 );
 	const float * xe = x + int64_t( ear ) * n;
 	const SpBlock * eb = blocks + ears.block_base[ear] + run.first_block;
 	const int64_t out_frames = ears.out_frames[ear];
@@ -317,43 +215,9 @@ __global__ __launch_bounds__( SP_THREADS ) void k_spat_itd( const float * __rest
 		s_first[lane] = int( b.first_out - eb[0].first_out );
 		}
 	if( lane == 0 ) s_first[run.num_blocks] = run.first_j + run.count;           // (first_j is 0 unless the run is a slice of one block)
-	for( int i = lane; i < run.win_len; i += SP_THREADS ) s_in[i] = sp_stream( xe, n, run.win_start + i );
+	for( int i = lane; i < run.win_len; i += SP_THREADS ) s_in[i] = wdl_stream<SP_TAPS>( xe, n, run.win_start + i );
 
-	// the table (BuildLowPass :1157-1202): window x sinc in fp64 rounded to float; filtpower in a fixed order (each thread its own
-	// entries in rising order, then a tree over the threads); the first half scaled and rounded again; the second half mirrors it
-	const double dsincpos = 3.1415926535897932384626433832795 * run.filtpos;
-	const double * w = win + size_t( oversize - 1 ) * SP_WIN_SLOT;
-	double power = 0.0;
-	for( int e = lane; e < half; e += SP_THREADS )
-		{
-		const int slice = e / SP_TAPS, tap = e % SP_TAPS;
-		float c = 1.0f;                                                          // the centre tap of slice 0 (:1173-1177)
-		if( e != SP_TAPS / 2 )
-			{
-			const double xfrac = double( slice ) / double( oversize ) + double( tap );
-			const double sincpos = dsincpos * ( xfrac - double( SP_TAPS / 2 ) );
-			const double val = w[e] * sin( sincpos ) / sincpos;
-			power += slice ? val * 2 : val;
-			c = float( val );
-			}
-		s_tab[slice * SP_SLICE_STRIDE + tap] = c;
-		}
-	s_red[lane] = power;
-	__syncthreads();
-	for( int off = SP_THREADS / 2; off > 0; off >>= 1 )
-		{
-		if( lane < off ) s_red[lane] = s_red[lane] + s_red[lane + off];
-		__syncthreads();
-		}
-	const double scale = double( oversize ) / ( s_red[0] + 1.0 );            // :1193
-	for( int e = lane; e < half; e += SP_THREADS )
-		{
-		const int at = ( e / SP_TAPS ) * SP_SLICE_STRIDE + e % SP_TAPS;
-		const float c = float( double( s_tab[at] ) * scale );
-		s_tab[at] = c;
-		const int m = 2 * half - 1 - e;                                          // :1202
-		s_tab[( m / SP_TAPS ) * SP_SLICE_STRIDE + m % SP_TAPS] = c;
-		}
+	wdl_build_table<SP_TAPS>( s_tab, s_red, win + size_t( oversize - 1 ) * Sp::WIN_SLOT, oversize, run.filtpos );
 	__syncthreads();
 
 	for( int t = lane; t < run.count; t += SP_THREADS )
@@ -371,34 +235,7 @@ __global__ __launch_bounds__( SP_THREADS ) void k_spat_itd( const float * __rest
 		const int64_t frame = b.first_out + j;
 		if( frame >= out_frames ) continue;                                      // :213-215
 		const double srcpos = fma( double( j ), b.ratio, b.fracpos );
-		const int64_t ipos = int64_t( srcpos );
-		const double frac = srcpos - double( ipos );
-		const int64_t s0 = b.offset + ipos;                                      // stream index of tap 0
-		const int64_t rel = s0 - run.win_start;
-		const bool staged = rel >= 0 && rel + SP_TAPS <= int64_t( run.win_len );
-		float y;
-		if( run.ideal )
-			{
-			int ifpos = int( frac * oversize + 0.5 );                            // SincSample1N (:184-200)
-			ifpos = ifpos < 0 ? 0 : ifpos > oversize ? oversize : ifpos;
-			const float * f2 = s_tab + ( oversize - ifpos ) * SP_SLICE_STRIDE;
-			const double sum2 = staged ? sp_taps1<true>( f2, s_in + rel, xe, n, s0 ) : sp_taps1<false>( f2, s_in, xe, n, s0 );
-			y = float( sum2 );
-			}
-		else
-			{
-			double fr = frac * oversize;                                         // SincSample1 (:160-182)
-			int ifpos = int( fr );
-			ifpos = ifpos < 0 ? 0 : ifpos > oversize - 1 ? oversize - 1 : ifpos;
-			fr -= ifpos;
-			const float * f2 = s_tab + ( oversize - ifpos ) * SP_SLICE_STRIDE;
-			const float * f1 = f2 - SP_SLICE_STRIDE;
-			double sum, sum2;
-			if( staged ) sp_taps2<true>( f1, f2, s_in + rel, xe, n, s0, &sum, &sum2 );
-			else sp_taps2<false>( f1, f2, s_in, xe, n, s0, &sum, &sum2 );
-			y = float( __dadd_rn( __dmul_rn( sum, fr ), __dmul_rn( sum2, 1.0 - fr ) ) );
-			}
-		out[int64_t( ear ) * out_stride + frame] = y;
+		out[int64_t( ear ) * out_stride + frame] = wdl_sample<SP_TAPS>( s_tab, s_in, run.win_start, run.win_len, xe, n, b.offset, srcpos, oversize, run.ideal );
 		}
 	}
 
@@ -490,8 +327,6 @@ __device__ __forceinline__ void sp_store4( float * p, int64_t f, int valid, cons
 	#pragma unroll
 	for( int k = 0; k < 4; ++k ) if( k < valid ) p[f + k] = v[k];
 	}
-inline bool sp_aligned16( const void * p ) { return ( reinterpret_cast<uintptr_t>( p ) & 15 ) == 0; }
-template<typename L> int sp_pair( bool vec, L launch ) { return vec ? launch( std::true_type{} ) : launch( std::false_type{} ); }
 inline int64_t sp_quads( int64_t n ) { return ( n + 3 ) / 4; }
 
 // Interpolator::sine2 (Utility/Interpolator.cpp:85-91) as the reference's compiler resolves it: pi / 4.0f * x is fp32, the unqualified sin is
@@ -613,7 +448,7 @@ int sp_prepare( int64_t ears, int64_t n, float sr, const double * stretches, int
 int launch_itd( const float * d_x, int64_t ears, int64_t n, const int64_t * out_frames, int64_t out_stride, const SpPrepared & p,
 	float * d_out, void * d_ws, hipStream_t s )
 	{
-	const SpLayout l = sp_layout( p.num_blocks, int64_t( p.runs.size() ) );
+	const WdlLayout l = sp_layout( p.num_blocks, int64_t( p.runs.size() ) );
 	char * ws = static_cast<char*>( d_ws );
 	SpEars at{}, reached{};
 	int64_t base = 0;
@@ -640,7 +475,7 @@ int launch_itd( const float * d_x, int64_t ears, int64_t n, const int64_t * out_
 	uint64_t used = 0;
 	for( const SpRun & r : p.runs ) used |= uint64_t( 1 ) << ( r.oversize - 1 );
 	double * d_win = (double*) ( ws + l.win_off );
-	if( int rc = launch_kernel( "spatial_itd", k_spat_window, SP_MAX_OVERSIZE, SP_THREADS, 0, s, d_win, used ) ) return rc;
+	if( int rc = launch_kernel( "spatial_itd", k_wdl_window<SP_TAPS>, WDL_MAX_OVERSIZE, SP_THREADS, 0, s, d_win, used ) ) return rc;
 	return launch_kernel( "spatial_itd", k_spat_itd, int64_t( p.runs.size() ), SP_THREADS, 0, s, d_x, n, at, out_stride,
 		(const SpBlock*) ( ws + l.block_off ), (const SpRun*) ( ws + l.run_off ), (const double*) d_win, d_out );
 	}
@@ -677,8 +512,8 @@ int sp_check_pan( const void * x, int64_t ch, int64_t n, const void * out )
 
 int launch_pan( const float * d_x, int64_t n, const float * d_pan, float pan, float * d_out, hipStream_t s )
 	{
-	const bool vec = n % 4 == 0 && sp_aligned16( d_x ) && sp_aligned16( d_out ) && sp_aligned16( d_pan );
-	return sp_pair( vec, [&]( auto V ) { return launch_kernel( "audio_pan", k_pan<V.value>, ( sp_quads( n ) + 255 ) / 256, 256, 0, s, d_x, n, d_pan, pan, d_out ); } );
+	const bool vec = n % 4 == 0 && aligned16( d_x ) && aligned16( d_out ) && aligned16( d_pan );
+	return scan_pair( vec, [&]( auto V ) { return launch_kernel( "audio_pan", k_pan<V.value>, ( sp_quads( n ) + 255 ) / 256, 256, 0, s, d_x, n, d_pan, pan, d_out ); } );
 	}
 
 } // namespace
@@ -839,8 +674,8 @@ int flanhip_audio_to_stereo_dev( const float * d_audio, int64_t num_frames, floa
 	FLANHIP_REQUIRE( num_frames > 0, FLANHIP_ERR_INVALID_ARG, "non-positive size" );
 	FLANHIP_REQUIRE( num_frames <= SP_MAX_FRAMES, FLANHIP_ERR_UNSUPPORTED, "shape out of range" );
 	if( int rc = require_device() ) return rc;
-	const bool vec = num_frames % 4 == 0 && sp_aligned16( d_audio ) && sp_aligned16( d_out );
-	return sp_pair( vec, [&]( auto V ) { return launch_kernel( "audio_to_stereo", k_to_stereo<V.value>, ( sp_quads( num_frames ) + 255 ) / 256, 256, 0,
+	const bool vec = num_frames % 4 == 0 && aligned16( d_audio ) && aligned16( d_out );
+	return scan_pair( vec, [&]( auto V ) { return launch_kernel( "audio_to_stereo", k_to_stereo<V.value>, ( sp_quads( num_frames ) + 255 ) / 256, 256, 0,
 		(hipStream_t) stream, d_audio, num_frames, d_out ); } );
 	}
 
@@ -850,8 +685,8 @@ int flanhip_audio_to_mono_dev( const float * d_audio, int64_t num_channels, int6
 	FLANHIP_REQUIRE( num_channels > 0 && num_frames > 0, FLANHIP_ERR_INVALID_ARG, "non-positive size" );
 	FLANHIP_REQUIRE( num_frames <= SP_MAX_FRAMES && num_channels <= ( 1 << 20 ), FLANHIP_ERR_UNSUPPORTED, "shape out of range" );
 	if( int rc = require_device() ) return rc;
-	const bool vec = num_frames % 4 == 0 && sp_aligned16( d_audio ) && sp_aligned16( d_out );
-	return sp_pair( vec, [&]( auto V ) { return launch_kernel( "audio_to_mono", k_to_mono<V.value>, ( sp_quads( num_frames ) + 255 ) / 256, 256, 0,
+	const bool vec = num_frames % 4 == 0 && aligned16( d_audio ) && aligned16( d_out );
+	return scan_pair( vec, [&]( auto V ) { return launch_kernel( "audio_to_mono", k_to_mono<V.value>, ( sp_quads( num_frames ) + 255 ) / 256, 256, 0,
 		(hipStream_t) stream, d_audio, num_channels, num_frames, d_out ); } );
 	}
 
@@ -864,7 +699,7 @@ int flanhip_audio_copy_rows_dev( const float * d_src, int64_t src_stride, int64_
 		"a row is longer than its stride, or the source longer than the destination" );
 	FLANHIP_REQUIRE( dst_frames <= SP_MAX_FRAMES && num_rows < 65536, FLANHIP_ERR_UNSUPPORTED, "shape out of range" );
 	if( int rc = require_device() ) return rc;
-	const bool vec = src_stride % 4 == 0 && dst_stride % 4 == 0 && sp_aligned16( d_src ) && sp_aligned16( d_dst );
+	const bool vec = src_stride % 4 == 0 && dst_stride % 4 == 0 && aligned16( d_src ) && aligned16( d_dst );
 	const dim3 grid( unsigned( ( sp_quads( dst_frames ) + 255 ) / 256 ), unsigned( num_rows ) );
 	hipStream_t s = (hipStream_t) stream;
 	if( vec ) hipLaunchKernelGGL( k_copy_rows<true>, grid, dim3( 256 ), 0, s, d_src, src_stride, src_frames, d_dst, dst_stride, dst_frames );

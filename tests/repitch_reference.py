@@ -1,12 +1,15 @@
-"""Audio::repitch (Audio/AudioTemporal.cpp:236-299 over WDL_Resampler, WDL/resample.cpp) restated in Python: the block plan, the
-low-pass table and the tap sums, in the reference's own operation order.  The plan and the table run in scalar Python (math.sin /
-math.cos: the libm the reference calls); the tap sums are numpy fp32 products accumulated in fp64 in tap order.  DESIGN.md 4.13.
+"""Audio::repitch (Audio/AudioTemporal.cpp:236-299 over WDL_Resampler, WDL/resample.cpp) restated in Python: the block plan in the
+reference's own operation order, in scalar Python, around the resampler itself (the low-pass table and the tap sums:
+tests/wdl_reference.py, at 64 taps).  DESIGN.md 4.13.
 
 Also an fp64 "smooth truth" for constant factors: the same windowed sinc evaluated at the exact fractional position, all in fp64."""
 import math
 import os
 
 import numpy as np
+
+import wdl_reference as W
+from wdl_reference import table_shape, stream_window, tap_sums, _fma     # noqa: F401  (this module's names too)
 
 F32 = np.float32
 SINC, LINEAR, UNINTERPOLATED = 0, 1, 2
@@ -42,33 +45,6 @@ def rates(sr, inv):
     rate_in = max(float(F32(sr)), 1.0)
     rate_out = max(float(F32(sr)) * float(F32(inv)), 1.0)
     return rate_in, rate_out, rate_in / rate_out
-
-
-def table_shape(rate_in, rate_out, ratio):
-    """BuildLowPass's first half (:1095-1141): ( filtpos, oversize, ideal )"""
-    filtpos = 1.0 / (ratio * 1.03) if ratio > 1.0 else 1.0                  # :1327-1328
-    want, ideal_interp = SINC_OVERSIZE, 0
-    if ratio < 1.0:
-        drat = rate_out / rate_in
-        irat = int(drat + 0.5)
-        if irat > 1 and irat == drat:
-            ideal_interp = irat
-    else:
-        irat = int(ratio + 0.5)
-        if ratio == irat:
-            ideal_interp = 1
-    if not ideal_interp and rate_in < 2147483648.0 and rate_out < 2147483648.0:
-        in1, out1 = int(rate_in), int(rate_out)
-        if out1 > 0 and in1 > 0 and rate_in == in1 and rate_out == out1:
-            min_cd = max(out1 // (2 * want), 1)
-            n1, n2 = out1, in1
-            while n2 >= min_cd:
-                n1, n2 = n2, n1 % n2
-            if not n2:
-                ideal_interp = out1 // n1
-    if 0 < ideal_interp <= want * 2:
-        want = ideal_interp
-    return filtpos, want, ideal_interp == want
 
 
 def plan(n, sr, inv, g, quality=SINC):
@@ -119,62 +95,12 @@ def plan(n, sr, inv, g, quality=SINC):
 
 
 def window(x_frac):
-    """the Blackman-Harris factor of :1185 at table position xfrac (slice / oversize + tap)"""
-    wp = (2.0 * math.pi / SINC_SIZE) * x_frac
-    return 0.35875 - 0.48829 * math.cos(wp) + 0.14128 * math.cos(2 * wp) - 0.01168 * math.cos(3 * wp)
-
-
-_tables = {}
+    return W.window(x_frac, SINC_SIZE)
 
 
 def table(filtpos, oversize):
     """BuildLowPass's second half (:1157-1202): float32 [(oversize + 1) * 64]"""
-    key = (filtpos, oversize)
-    if key in _tables:
-        return _tables[key]
-    size, half = SINC_SIZE, SINC_SIZE // 2
-    dsincpos = math.pi * filtpos
-    vals, power = [], 0.0
-    for sl in range(oversize // 2 + 1):
-        frac = sl / float(oversize)
-        count = size if (sl < oversize // 2 or oversize & 1) else half
-        for x in range(count):
-            if sl == 0 and x == half:
-                vals.append(1.0)
-                continue
-            xfrac = frac + x
-            sincpos = dsincpos * (xfrac - half)
-            val = window(xfrac) * math.sin(sincpos) / sincpos
-            power += val * 2 if sl else val
-            vals.append(val)
-    alloc = size * (oversize + 1)
-    assert len(vals) == alloc // 2
-    first = np.array(vals, np.float64).astype(F32)
-    scale = oversize / (power + 1.0)
-    first = (first.astype(np.float64) * scale).astype(F32)
-    out = np.concatenate([first, first[::-1]])
-    _tables[key] = out
-    return out
-
-
-def stream_window(x, prelude, start, length):
-    """float32 [ch][length] of the stream (prelude zeros, x, zeros) from index `start`"""
-    ch, n = x.shape
-    out = np.zeros((ch, length), F32)
-    a, b = max(start - prelude, 0), min(start - prelude + length, n)
-    if b > a:
-        out[:, a - (start - prelude):b - (start - prelude)] = x[:, a:b]
-    return out
-
-
-def tap_sums(coef, taps):
-    """per output sample, the sum over 64 taps of float( coef * tap ) added into fp64 in tap order; coef [m][64], taps [ch][m][64] ->
-    float64 [ch][m]"""
-    prod = (coef[None, :, :] * taps).astype(F32).astype(np.float64)        # fp32 products, each rounded
-    s = np.zeros(taps.shape[:2], np.float64)
-    for i in range(SINC_SIZE):
-        s = s + prod[:, :, i]
-    return s
+    return W.table(filtpos, oversize, SINC_SIZE)
 
 
 def repitch(x, sr, inv, g, quality=SINC, position="chain"):
@@ -186,46 +112,20 @@ def repitch(x, sr, inv, g, quality=SINC, position="chain"):
     out = np.zeros((ch, nout), F32)
     fsize = SINC_SIZE if quality == SINC else 0
     prelude = fsize // 2 - 1 if fsize else 0
-    taps_index = np.arange(SINC_SIZE)
     for b in plan(n, sr, inv, g, quality):
         ratio, oversize = b["ratio"], b["oversize"]
         m = min(g, nout - b["first_out"])
         if m <= 0:
             continue
-        if position == "fma":
-            srcpos = np.array([_fma(j, ratio, b["fracpos"]) for j in range(m)], np.float64)
-        else:
-            srcpos = np.empty(m, np.float64)
-            p = b["fracpos"]
-            for j in range(m):
-                srcpos[j] = p
-                p += ratio
+        srcpos = W.positions(b["fracpos"], ratio, m, position)
         ipos = srcpos.astype(np.int64)                                     # truncation: srcpos >= 0
-        frac = srcpos - ipos
         buf = stream_window(x, prelude, b["offset"], int(ipos[-1]) + SINC_SIZE + 1)
         dst = out[:, b["first_out"]:b["first_out"] + m]
         if not fsize:
             dst[:] = buf[:, ipos]
             continue
-        tab = table(b["filtpos"], oversize).reshape(oversize + 1, SINC_SIZE)
-        taps = buf[:, ipos[:, None] + taps_index[None, :]]                 # [ch][m][64]
-        if b["ideal"]:
-            ifpos = (frac * oversize + 0.5).astype(np.int64)
-            dst[:] = tap_sums(tab[oversize - ifpos], taps).astype(F32)
-        else:
-            fr = frac * oversize
-            ifpos = fr.astype(np.int64)
-            fr = fr - ifpos
-            s1 = tap_sums(tab[oversize - ifpos - 1], taps)
-            s2 = tap_sums(tab[oversize - ifpos], taps)
-            dst[:] = (s1 * fr[None, :] + s2 * (1.0 - fr)[None, :]).astype(F32)
+        dst[:] = W.samples(srcpos, buf, table(b["filtpos"], oversize).reshape(oversize + 1, SINC_SIZE), b["ideal"])
     return out
-
-
-def _fma(j, ratio, fracpos):
-    """fma( j, ratio, fracpos ) with one rounding, from exact rational arithmetic"""
-    from fractions import Fraction
-    return float(Fraction(j) * Fraction(ratio) + Fraction(fracpos))
 
 
 def smooth_truth(x, sr, factor, nout):
@@ -235,7 +135,7 @@ def smooth_truth(x, sr, factor, nout):
     ch, n = x.shape
     inv = invert([factor])[0]
     rate_in, rate_out, ratio = rates(sr, inv)
-    filtpos = 1.0 / (ratio * 1.03) if ratio > 1.0 else 1.0
+    filtpos = table_shape(rate_in, rate_out, ratio)[0]
     half = SINC_SIZE // 2
     prelude = half - 1
     padded = np.zeros((ch, prelude + n + int(nout * ratio) + 2 * SINC_SIZE + 8))
@@ -246,10 +146,8 @@ def smooth_truth(x, sr, factor, nout):
     taps = np.arange(SINC_SIZE, dtype=np.float64)
     # slice s of the table holds xfrac = s / oversize + tap and is read at s = oversize - ifpos: the continuous form is tap + 1 - frac
     xfrac = taps[None, :] + 1.0 - frac[:, None]
-    wp = (2.0 * np.pi / SINC_SIZE) * xfrac
-    w = 0.35875 - 0.48829 * np.cos(wp) + 0.14128 * np.cos(2 * wp) - 0.01168 * np.cos(3 * wp)
     arg = np.pi * filtpos * (xfrac - half)
-    coef = w * np.sinc(arg / np.pi)
+    coef = W.window(xfrac, SINC_SIZE, np.cos) * np.sinc(arg / np.pi)
     coef *= filtpos_gain(filtpos)
     idx = ipos[:, None] + taps[None, :].astype(np.int64)
     out = np.empty((ch, nout))
@@ -260,18 +158,7 @@ def smooth_truth(x, sr, factor, nout):
 
 def filtpos_gain(filtpos, oversize=SINC_OVERSIZE):
     """the table's normalisation oversize / ( filtpower + 1 ) (:1193), from the fp64 table values"""
-    half = SINC_SIZE // 2
-    power = 0.0
-    for sl in range(oversize // 2 + 1):
-        count = SINC_SIZE if (sl < oversize // 2 or oversize & 1) else half
-        for x in range(count):
-            if sl == 0 and x == half:
-                continue
-            xfrac = sl / float(oversize) + x
-            sincpos = math.pi * filtpos * (xfrac - half)
-            val = window(xfrac) * math.sin(sincpos) / sincpos
-            power += val * 2 if sl else val
-    return oversize / (power + 1.0)
+    return oversize / (W.half_table(filtpos, oversize, SINC_SIZE)[1] + 1.0)
 
 
 def errors(y, ref):

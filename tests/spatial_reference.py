@@ -2,9 +2,9 @@
 head_itd over WDL_Resampler in feed mode (WDL/resample.cpp) --, pan (:9-45), and the channel plumbing under them (convert_to_stereo /
 convert_to_mono, Audio/AudioConversions.cpp:58-104; combine_channels, Audio/AudioChannels.cpp).  DESIGN.md 4.20.
 
-Everything runs in the reference's own types and operation order.  The limiter, the plan and the table run in scalar Python (math.sin /
-math.cos: the libm the reference calls); cosf / atan2f are libm's through ctypes where it can be loaded (numpy's own otherwise); the tap
-sums are numpy fp32 products accumulated in fp64 in tap order.  The 500 Hz low-pass is tests/filter_reference.py's."""
+Everything runs in the reference's own types and operation order.  The limiter and the plan run in scalar Python; cosf / atan2f are libm's
+through ctypes where it can be loaded (numpy's own otherwise); the resampler itself (the table and the tap sums) is tests/wdl_reference.py's
+at 32 taps.  The 500 Hz low-pass is tests/filter_reference.py's."""
 import ctypes
 import ctypes.util
 import math
@@ -13,7 +13,9 @@ import os
 import numpy as np
 
 import filter_reference as fr
-from repitch_reference import table_shape, errors, _fma          # BuildLowPass's choice of table does not depend on the tap count
+import wdl_reference as W
+from repitch_reference import errors                              # noqa: F401
+from wdl_reference import table_shape, tap_sums, _fma             # noqa: F401  (this module's names too)
 
 F32, F64 = np.float32, np.float64
 G = 32                                                  # granularity_frames (:137)
@@ -195,59 +197,17 @@ def itd_plan(n, sr, stretches):
 
 
 def window(x_frac):
-    """the Blackman-Harris factor of :1185 at table position xfrac (slice / oversize + tap)"""
-    wp = (2.0 * math.pi / TAPS) * x_frac
-    return 0.35875 - 0.48829 * math.cos(wp) + 0.14128 * math.cos(2 * wp) - 0.01168 * math.cos(3 * wp)
-
-
-_tables = {}
+    return W.window(x_frac, TAPS)
 
 
 def table(filtpos, oversize):
     """BuildLowPass's second half (:1157-1202) at 32 taps: float32 [(oversize + 1) * 32]"""
-    key = (filtpos, oversize)
-    if key in _tables:
-        return _tables[key]
-    size, half = TAPS, TAPS // 2
-    dsincpos = math.pi * filtpos
-    vals, power = [], 0.0
-    for sl in range(oversize // 2 + 1):
-        frac = sl / float(oversize)
-        count = size if (sl < oversize // 2 or oversize & 1) else half
-        for x in range(count):
-            if sl == 0 and x == half:
-                vals.append(1.0)
-                continue
-            xfrac = frac + x
-            sincpos = dsincpos * (xfrac - half)
-            val = window(xfrac) * math.sin(sincpos) / sincpos
-            power += val * 2 if sl else val
-            vals.append(val)
-    assert len(vals) == size * (oversize + 1) // 2
-    first = np.array(vals, F64).astype(F32)
-    first = (first.astype(F64) * (oversize / (power + 1.0))).astype(F32)
-    out = np.concatenate([first, first[::-1]])
-    _tables[key] = out
-    return out
+    return W.table(filtpos, oversize, TAPS)
 
 
 def stream_window(x, start, length):
     """float32 [length] of the stream (15 zeros, x, zeros) from index `start`"""
-    n = x.size
-    out = np.zeros(length, F32)
-    a, b = max(start - PRELUDE, 0), min(start - PRELUDE + length, n)
-    if b > a:
-        out[a - (start - PRELUDE):b - (start - PRELUDE)] = x[a:b]
-    return out
-
-
-def tap_sums(coef, taps):
-    """per output sample, the sum over 32 taps of float( coef * tap ) added into fp64 in tap order; [m][32] each -> float64 [m]"""
-    prod = (coef * taps).astype(F32).astype(F64)
-    s = np.zeros(taps.shape[0], F64)
-    for i in range(TAPS):
-        s = s + prod[:, i]
-    return s
+    return W.stream_window(x, PRELUDE, start, length)
 
 
 def itd(x, sr, stretches, nout, position="chain", plan=None):
@@ -255,37 +215,16 @@ def itd(x, sr, stretches, nout, position="chain", plan=None):
     fracpos + j * ratio with one rounding like the device kernel (the block hand-over is the chain's in both)."""
     x = np.ascontiguousarray(x, F32).reshape(-1)
     out = np.zeros(nout, F32)
-    taps_index = np.arange(TAPS)
     for b in (plan if plan is not None else itd_plan(x.size, sr, stretches)):
         ratio, oversize = b["ratio"], b["oversize"]
         m = min(b["count"], nout - b["first_out"])                          # :213-215
         if m <= 0:
             continue
-        if position == "fma":
-            srcpos = np.array([_fma(j, ratio, b["fracpos"]) for j in range(m)], F64)
-        else:
-            srcpos = np.empty(m, F64)
-            p = b["fracpos"]
-            for j in range(m):
-                srcpos[j] = p
-                p += ratio
+        srcpos = W.positions(b["fracpos"], ratio, m, position)
         ipos = srcpos.astype(np.int64)
         assert int(ipos[-1]) + TAPS + 1 < b["buffered"], "a window ends at least two samples before the buffer's end"
-        frac = srcpos - ipos
         buf = stream_window(x, b["offset"], b["buffered"])
-        tab = table(b["filtpos"], oversize).reshape(oversize + 1, TAPS)
-        taps = buf[ipos[:, None] + taps_index[None, :]]
-        dst = out[b["first_out"]:b["first_out"] + m]
-        if b["ideal"]:
-            ifpos = (frac * oversize + 0.5).astype(np.int64)
-            dst[:] = tap_sums(tab[oversize - ifpos], taps).astype(F32)
-        else:
-            fr_ = frac * oversize
-            ifpos = fr_.astype(np.int64)
-            fr_ = fr_ - ifpos
-            s1 = tap_sums(tab[oversize - ifpos - 1], taps)
-            s2 = tap_sums(tab[oversize - ifpos], taps)
-            dst[:] = (s1 * fr_ + s2 * (1.0 - fr_)).astype(F32)
+        out[b["first_out"]:b["first_out"] + m] = W.samples(srcpos, buf, table(b["filtpos"], oversize).reshape(oversize + 1, TAPS), b["ideal"])
     return out
 
 
