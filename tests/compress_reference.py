@@ -7,6 +7,8 @@ DESIGN.md 4.14.
     compress()               all of it: ( out, c )
     get_max_sample_magnitude / modify_volume / set_volume
     errors(), CASES
+    LONG, long_case(), windows(), figures()
+                             rows of more than 256 blocks, past one pass of the carry kernel, and the windows they are held over
 
 log10, exp and pow of the fp32 loop are the fp64 functions rounded to fp32 once: what glibc's expf / powf return (they evaluate in
 double), and what the device kernels do."""
@@ -268,6 +270,68 @@ def case(name):
 def expected(name, dtype=F32):
     """( out, c ) of a case, computed once and shared: treat as read-only"""
     c = case(name)
+    out, gain = compress(c["x"], c["sr"], c["side"], dtype, **c["params"])
+    out.setflags(write=False)
+    gain.setflags(write=False)
+    return out, gain
+
+
+# ---- rows longer than one pass of the carry kernel --------------------------------------------------------------------------------
+# k_scan_carry (run_scan.h) scans 256 block totals in a pass and a block is 256 runs, so a pass is 65 536 runs: 65 536 frames at a run
+# of 1, 1 048 576 at the default run.  These rows are not in CASES (which feeds the C ABI and host C++ modules); the device tests and
+# the tests of the scan form build them here, once.
+PASS_RUNS = 256 * 256
+# at a run of 1: 256 blocks exactly, one pass; a second pass of one block of one frame; three passes, the third of 4 blocks, the last of 17 frames
+LONG_RUN1 = (PASS_RUNS, PASS_RUNS + 1, 2 * PASS_RUNS + 3 * 256 + 17)
+N_THREE_PASSES = LONG_RUN1[2]                          # 131 857
+N_LONG = 257 * BLOCK + 16                              # 1 052 688 at the default run: 258 blocks
+assert N_THREE_PASSES == 131857 and N_LONG == 1052688
+
+
+def windows(n, run):
+    """[( label, lo, hi )]: the whole row, every pass's frames, and the first block (256 runs) of every pass after the first: where a
+    state lost between passes shows before the release (0.1 s, 4800 frames) and the attack have let go of it"""
+    per_pass = PASS_RUNS * run
+    out = [("whole", 0, n)]
+    for p, lo in enumerate(range(0, n, per_pass)):
+        out.append(("pass %d" % p, lo, min(lo + per_pass, n)))
+        if p:
+            out.append(("pass %d head" % p, lo, min(lo + 256 * run, n)))
+    return out
+
+
+def errors_over(y, ref, lo, hi):
+    """errors() over frames [lo, hi), divided by the rms and the peak of the WHOLE ref: a quiet stretch cannot inflate them"""
+    y, ref = np.asarray(y, F64), np.asarray(ref, F64)
+    d = y[..., lo:hi] - ref[..., lo:hi]
+    return float(np.sqrt(np.mean(d * d) / np.mean(ref * ref))), float(np.max(np.abs(d)) / np.max(np.abs(ref)))
+
+
+def figures(got, want, truth, run):
+    """per window of windows(): ( label, vs the fp32 loop ( rms, max ), vs the truth ( rms, max ), the fp32 loop vs the truth ( rms, max ) )"""
+    return [(label, errors_over(got, want, lo, hi), errors_over(got, truth, lo, hi), errors_over(want, truth, lo, hi))
+            for label, lo, hi in windows(np.shape(want)[-1], run)]
+
+
+LONG = dict([("bursts_n%d_run1" % n, (2, n, 1, 1200 + i)) for i, n in enumerate(LONG_RUN1)] + [("bursts_n%d" % N_LONG, (2, N_LONG, None, 1210))])
+LONG_IDS = list(LONG)
+
+
+@functools.lru_cache(maxsize=None)
+def long_case(name):
+    """bursts under the knee of 6 dB, the threshold sweep and the attack steps, the release at its default: 4800 frames of memory across
+    a pass's boundary.  run: the forced run the row is meant for (None: the library's choice).  Built once: read-only"""
+    ch, n, run, seed = LONG[name]
+    c = _case(name, bursts(ch, n, seed), threshold=threshold_sweep(n), attack=attack_steps(n), knee_width=6.0)
+    for v in (c["x"], c["params"]["threshold"], c["params"]["attack"]):
+        v.setflags(write=False)
+    return dict(c, run=run)
+
+
+@functools.lru_cache(maxsize=None)
+def long_expected(name, dtype=F32):
+    """( out, c ) of a long case, computed once and shared: read-only"""
+    c = long_case(name)
     out, gain = compress(c["x"], c["sr"], c["side"], dtype, **c["params"])
     out.setflags(write=False)
     gain.setflags(write=False)

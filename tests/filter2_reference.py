@@ -9,6 +9,7 @@ _highshelf (:631-758) and filter_1pole_lowshelf / _highshelf (:431-512) restated
                              section's affine maps (built from the fp32 step values), rounded to fp32 once, then the fp32 loop over the run
     filter2()                all of it
     errors(), CASES with their two classes
+    LONG, long_case()        rows of more than 256 blocks, past one pass of the carry kernel (the windows are filter_reference's)
 
 Every transcendental (acos, cos, sin, sqrt, pow, hypot, tan) is the fp64 function of the fp32 argument rounded to fp32 once, complex
 products and quotients are the textbook forms with one rounding per operation: what the device kernels do."""
@@ -373,5 +374,54 @@ def call(c, dtype=F32, run=None, x=None):
 def expected(name, dtype=F32):
     """the sequential loop's output of a case in `dtype`, computed once and shared: treat as read-only"""
     out = call(case(name), dtype)
+    out.setflags(write=False)
+    return out
+
+
+# ---- rows longer than one pass of the carry kernel (filter_reference.py has the geometry) --------------------------------------------
+PASS_RUNS, LONG_RUN1, N_THREE_PASSES, N_LONG = R1.PASS_RUNS, R1.LONG_RUN1, R1.N_THREE_PASSES, R1.N_LONG
+windows, errors_over, figures = R1.windows, R1.errors_over, R1.figures
+MEMORY_CUTOFF, memory_inputs = R1.MEMORY_CUTOFF, R1.memory_inputs
+# A window of fewer frames than a block has no rms to speak of: the second pass of 65 537 frames is ONE frame, 3 samples, and their rms
+# is a maximum in all but name (the high shelf puts out 1.9 for a peak of 1 there).  Such a window's rms has a constant of its own:
+# measured on the MI355X 1.341e-6 (highshelf3_dcurve_p6_n65537_run1, pass 1), and the scan model on the CPU gives the same 1.341e-6;
+# at most 30 % above.  Its maximum, and both figures of every longer window, are held to REL_RMS_BOUND / REL_MAX_BOUND as they stand
+SHORT_WINDOW_REL_RMS_BOUND = 1.7e-6
+
+
+def rms_bound(lo, hi):
+    return REL_RMS_BOUND if hi - lo >= 256 else SHORT_WINDOW_REL_RMS_BOUND
+
+
+def _long_table():
+    """noise under the swept cutoff.  low2_d025: the damping and the gain are scalars, the cutoff alone is a row; highshelf3_dcurve_p6: a
+    damping row as well and a mix that reads the row m"""
+    table = {}
+    for i, n in enumerate(LONG_RUN1):
+        table["low2_d025_n%d_run1" % n] = (LOW, 2, "d025", 0.0, 3, n, 1, 1100 + i)
+        table["highshelf3_dcurve_p6_n%d_run1" % n] = (HIGHSHELF, 3, "dcurve", 6.0, 3, n, 1, 1110 + i)
+    table["low2_d025_n%d" % N_LONG] = (LOW, 2, "d025", 0.0, 2, N_LONG, None, 1120)
+    return table
+
+
+LONG = _long_table()
+LONG_IDS = list(LONG)
+
+
+@functools.lru_cache(maxsize=None)
+def long_case(name):
+    """run: the forced run the row is meant for (None: the library's choice).  Built once: read-only"""
+    kind, order, damp, gain, ch, n, run, seed = LONG[name]
+    x, cutoff, damping = noise(ch, n, seed), sweep(n), DAMPINGS[damp](n)
+    for v in (x, cutoff, damping):
+        if not np.isscalar(v):
+            v.setflags(write=False)
+    return {"name": name, "x": x, "sr": SR, "cutoff": cutoff, "damping": damping, "gain": gain, "kind": kind, "order": order, "cls": PARITY, "run": run}
+
+
+@functools.lru_cache(maxsize=None)
+def long_expected(name, dtype=F32):
+    """the sequential loop's output of a long case in `dtype`, computed once and shared: read-only"""
+    out = call(long_case(name), dtype)
     out.setflags(write=False)
     return out

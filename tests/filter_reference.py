@@ -11,6 +11,8 @@ NumPy.  DESIGN.md 4.15.
                              section's affine maps (built from the fp32 step values), rounded to fp32 once, then the fp32 loop over the run
     filter_1pole()           all of it
     errors(), CASES, stalls()
+    LONG, long_case(), windows(), figures()
+                             rows of more than 256 blocks, past one pass of the carry kernel, and the windows they are held over
 
 tan (and the cosine of R) is the fp64 function of the fp32 argument rounded to fp32 once: what the device kernels do."""
 import functools
@@ -329,3 +331,85 @@ def stalls(name):
     """a case stalls when the fp32 loop itself is more than 1e-6 (rms or max) from the truth"""
     c = case(name)
     return max(errors(expected(name, F32), expected(name, F64), c["x"])) > 1e-6
+
+
+# ---- rows longer than one pass of the carry kernel --------------------------------------------------------------------------------
+# k_scan_carry (run_scan.h) scans 256 block totals in a pass and a block is 256 runs, so a pass is 65 536 runs: 65 536 frames at a run
+# of 1, 1 048 576 at the default run.  These rows are not in CASES (which feeds the C ABI and host C++ modules and stops at N3); the
+# device tests and the tests of the scan model build them here, once.
+PASS_RUNS = 256 * 256
+# at a run of 1: 256 blocks exactly, one pass; a second pass of one block of one frame; three passes, the third of 4 blocks, the last of 17 frames
+LONG_RUN1 = (PASS_RUNS, PASS_RUNS + 1, 2 * PASS_RUNS + 3 * 256 + 17)
+N_THREE_PASSES = LONG_RUN1[2]                          # 131 857
+N_LONG = 257 * BLOCK + 16                              # 1 052 688 at the default run: 258 blocks, whole quads
+assert N_LONG % 4 == 0 and N_THREE_PASSES == 131857 and N_LONG == 1052688
+
+
+def windows(n, run):
+    """[( label, lo, hi )]: the whole row, every pass's frames, and the first block (256 runs) of every pass after the first: where a
+    state lost between passes shows before the filter has forgotten it"""
+    per_pass = PASS_RUNS * run
+    out = [("whole", 0, n)]
+    for p, lo in enumerate(range(0, n, per_pass)):
+        out.append(("pass %d" % p, lo, min(lo + per_pass, n)))
+        if p:
+            out.append(("pass %d head" % p, lo, min(lo + 256 * run, n)))
+    return out
+
+
+def errors_over(got, want, x, lo, hi):
+    """errors() over frames [lo, hi) of every row, divided by the rms and the peak of the WHOLE input: a quiet stretch cannot inflate them"""
+    d = np.asarray(got, F64)[:, lo:hi] - np.asarray(want, F64)[:, lo:hi]
+    x = np.asarray(x, F64)
+    return float(np.sqrt(np.mean(d * d))) / float(np.sqrt(np.mean(x * x))), float(np.max(np.abs(d))) / float(np.max(np.abs(x)))
+
+
+def _long_table():
+    table = {}
+    for i, n in enumerate(LONG_RUN1):
+        # order 3: a 1-pole section and a 2-pole section, so both maps cross the pass
+        table["low3_n%d_run1" % n] = (BUTTERWORTH_LOW, 3, 3, n, 1, 1000 + i)
+        table["high2_n%d_run1" % n] = (BUTTERWORTH_HIGH, 2, 3, n, 1, 1010 + i)
+    table["rlow16_n%d_run1" % LONG_RUN1[1]] = (REPEAT_LOW, 16, 3, LONG_RUN1[1], 1, 1020)
+    table["low3_n%d" % N_LONG] = (BUTTERWORTH_LOW, 3, 2, N_LONG, None, 1030)
+    return table
+
+
+LONG = _long_table()
+LONG_IDS = list(LONG)
+
+
+@functools.lru_cache(maxsize=None)
+def long_case(name):
+    """noise under the swept cutoff; run: the forced run the row is meant for (None: the library's choice).  Built once: read-only"""
+    kind, order, ch, n, run, seed = LONG[name]
+    x, cutoff = noise(ch, n, seed), sweep(n)
+    x.setflags(write=False)
+    cutoff.setflags(write=False)
+    return {"name": name, "x": x, "sr": SR, "cutoff": cutoff, "kind": kind, "order": order, "run": run}
+
+
+@functools.lru_cache(maxsize=None)
+def long_expected(name, dtype=F32):
+    """the sequential loop's output of a long case in `dtype`, computed once and shared: read-only"""
+    c = long_case(name)
+    out = filter_1pole(c["x"], c["sr"], c["cutoff"], c["kind"], c["order"], dtype)
+    out.setflags(write=False)
+    return out
+
+
+def figures(got, want, truth, x, run):
+    """per window of windows(): ( label, vs the fp32 loop ( rms, max ), vs the truth ( rms, max ), the fp32 loop vs the truth ( rms, max ) )"""
+    return [(label, errors_over(got, want, x, lo, hi), errors_over(got, truth, x, lo, hi), errors_over(want, truth, x, lo, hi))
+            for label, lo, hi in windows(np.shape(x)[1], run)]
+
+
+MEMORY_CUTOFF = 1.0                                    # Hz: the first-order low-pass forgets by exp( -2 pi / 48000 ) a frame, 1.9e-4 over a pass
+
+
+def memory_inputs():
+    """( x, other ) [3][131 857]: noise, and the same with frames [0, 256) replaced by a level of 24"""
+    x = noise(3, N_THREE_PASSES, 1040)
+    other = x.copy()
+    other[:, :256] = F32(24)
+    return x, other

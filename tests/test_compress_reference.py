@@ -22,6 +22,57 @@ def test_scan_form_equals_the_sequential_loop(name):
             assert rel_max <= 1e-12, (name, run, rel_max)
 
 
+# the condition tests/test_gpu_compress.py puts on the device against the fp64 truth
+TRUTH_FACTOR = 4.0
+TRUTH_FLOOR = 8 * 2.0 ** -23
+
+
+def _long_levels(name):
+    c = R.long_case(name)
+    return R.level(R.detector_input(c["x"], c["x"].shape[1]), c["sr"], dtype=F64, **c["params"])
+
+
+def _gain_of(y_L):
+    return R.pow10_of(-y_L / 20.0, F64)
+
+
+def test_scan_form_equals_the_sequential_loop_past_one_pass_of_the_carry():
+    """three passes of 256 run summaries at a run of 1, whole and window by window: both detectors, and the gain curve they give, which
+    then meets what tests/test_gpu_compress.py asks of the device against the truth with room to spare"""
+    name = "bursts_n131857_run1"
+    x_L, a_R, a_A = _long_levels(name)
+    y_1, y_L = R.peak_detector(x_L, a_R, a_A, F64)
+    s_1, s_L = R.peak_detector_scan(x_L, a_R, a_A, 1)
+    true_gain = R.long_expected(name, F64)[1]
+    assert np.array_equal(_gain_of(y_L), true_gain)
+    assert [w[0] for w in R.windows(x_L.size, 1)] == ["whole", "pass 0", "pass 1", "pass 1 head", "pass 2", "pass 2 head"]
+    for label, lo, hi in R.windows(x_L.size, 1):
+        for what, got, want in (("y_1", s_1, y_1), ("y_L", s_L, y_L), ("gain", _gain_of(s_L), true_gain)):
+            rel_rms, rel_max = R.errors_over(got, want, lo, hi)
+            print("%s %s %s: %.3e %.3e" % (name, label, what, rel_rms, rel_max))
+            assert rel_rms <= 1e-12 and rel_max <= 1e-12, (label, what)
+
+
+def test_a_state_lost_between_two_passes_misses_the_conditions_where_it_is_lost():
+    """the carry kernel forgetting its state at the start of its second pass: both detectors start again from 0 at frame 65 536.  The
+    gain over the first block of the pass misses the device's allowance against the truth 1e4 times over; 8192 frames on the bursts
+    and the attack (1 ms there) have let go of it (1.4e-11 is left), which is why the windows are there"""
+    name = "bursts_n131857_run1"
+    cut = R.PASS_RUNS
+    x_L, a_R, a_A = _long_levels(name)
+    n = x_L.size
+    broken = _gain_of(np.concatenate([R.peak_detector_scan(x_L[:cut], a_R[:cut], a_A[:cut], 1)[1], R.peak_detector_scan(x_L[cut:], a_R[cut:], a_A[cut:], 1)[1]]))
+    want, truth = R.long_expected(name, F32)[1], R.long_expected(name, F64)[1]
+
+    def ratio(lo, hi):
+        t, own = R.errors_over(broken, truth, lo, hi), R.errors_over(want, truth, lo, hi)
+        print("lost state, frames [%d, %d): vs truth %.3e %.3e (the fp32 loop: %.3e %.3e)" % ((lo, hi) + t + own))
+        return t[0] / max(TRUTH_FACTOR * own[0], TRUTH_FLOOR), t[1] / max(TRUTH_FACTOR * own[1], TRUTH_FLOOR)
+    assert min(ratio(cut, cut + 256)) >= 1e4
+    assert max(ratio(0, n)) > 1.0 and max(ratio(cut, 2 * cut)) > 1.0
+    assert max(ratio(cut + 8192, n)) <= 1.0
+
+
 def test_composition_handles_the_identity_and_a_zero():
     step = (0.0, 0.0, -3.0)                                        # a = 0: the step forgets the state
     assert R.then1(R.IDENTITY1, step) == step

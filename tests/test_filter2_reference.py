@@ -30,6 +30,83 @@ def test_the_scan_model_meets_the_conditions(name):
             assert p_rms <= REL_RMS_BOUND and p_max <= REL_MAX_BOUND, (name, run)
 
 
+def missed(name, n, figures):
+    """prints every window's figures of a row of n frames at a run of 1, then returns the windows that miss the conditions
+    tests/test_gpu_filter2.py puts on the device"""
+    out = []
+    for (_, lo, hi), (label, (rel_rms, rel_max), (t_rms, t_max), (own_rms, own_max)) in zip(R.windows(n, 1), figures):
+        print("%s %s: vs the fp32 loop %.3e %.3e; vs truth %.3e %.3e (the fp32 loop: %.3e %.3e)" % (name, label, rel_rms, rel_max, t_rms, t_max, own_rms, own_max))
+        if not (rel_rms <= R.rms_bound(lo, hi) and rel_max <= REL_MAX_BOUND):
+            out.append((label, "loop", rel_rms, rel_max))
+        if not (t_rms <= max(TRUTH_FACTOR * own_rms, TRUTH_FLOOR) and t_max <= max(TRUTH_FACTOR * own_max, TRUTH_FLOOR)):
+            out.append((label, "truth", t_rms, t_max, own_rms, own_max))
+    return out
+
+
+@pytest.mark.parametrize("name", ["low2_d025_n131857_run1", "highshelf3_dcurve_p6_n131857_run1", "highshelf3_dcurve_p6_n65537_run1"])
+def test_the_scan_model_meets_the_conditions_past_one_pass_of_the_carry(name):
+    """what tests/test_gpu_filter2.py asks of the device on rows of more than 256 blocks, whole and window by window, a correct scan gives"""
+    c = R.long_case(name)
+    got = R.call(c, run=1)
+    n = c["x"].shape[1]
+    assert [w[0] for w in R.windows(n, 1)] == ["whole", "pass 0", "pass 1", "pass 1 head", "pass 2", "pass 2 head"][:6 if n > 2 * R.PASS_RUNS else 4]
+    assert R.windows(R.PASS_RUNS + 1, 1)[2:] == [("pass 1", R.PASS_RUNS, R.PASS_RUNS + 1), ("pass 1 head", R.PASS_RUNS, R.PASS_RUNS + 1)]
+    assert R.rms_bound(0, 256) == REL_RMS_BOUND and R.rms_bound(0, 255) == R.SHORT_WINDOW_REL_RMS_BOUND > REL_RMS_BOUND       # the one-frame pass alone
+    failures = missed(name, n, R.figures(got, R.long_expected(name, F32), R.long_expected(name, F64), c["x"], 1))
+    assert not failures, failures
+
+
+def test_a_state_lost_between_two_passes_misses_the_conditions_where_it_is_lost():
+    """the carry kernel forgetting its state at the start of its second pass: frames from 65 536 on are filtered from zero states.  The
+    first block of the pass misses its allowance 1e4 times over; 8192 frames on the filter has forgotten"""
+    name = "low2_d025_n131857_run1"
+    c = R.long_case(name)
+    cut = R.PASS_RUNS
+    broken = np.concatenate([R.filter2(c["x"][:, :cut], c["sr"], c["cutoff"][:cut], c["damping"], c["gain"], c["kind"], c["order"], run=1),
+                             R.filter2(c["x"][:, cut:], c["sr"], c["cutoff"][cut:], c["damping"], c["gain"], c["kind"], c["order"], run=1)], axis=1)
+    want, truth = R.long_expected(name, F32), R.long_expected(name, F64)
+    by_label = {f[0]: f for f in R.figures(broken, want, truth, c["x"], 1)}
+    assert {"whole", "pass 1", "pass 1 head"} <= {m[0] for m in missed("lost state", c["x"].shape[1], by_label.values())}
+    _, (rel_rms, rel_max), (t_rms, t_max), (own_rms, own_max) = by_label["pass 1 head"]
+    assert rel_rms >= 1e4 * REL_RMS_BOUND and rel_max >= 1e4 * REL_MAX_BOUND
+    assert t_rms >= 1e4 * max(TRUTH_FACTOR * own_rms, TRUTH_FLOOR) and t_max >= 1e4 * max(TRUTH_FACTOR * own_max, TRUTH_FLOOR)
+    later = cut + 8192
+    n = c["x"].shape[1]
+    rel = R.errors_over(broken, want, c["x"], later, n)
+    t, own = R.errors_over(broken, truth, c["x"], later, n), R.errors_over(want, truth, c["x"], later, n)
+    print("lost state, from frame %d on: vs the fp32 loop %.3e %.3e; vs truth %.3e %.3e (the fp32 loop: %.3e %.3e)" % ((later,) + rel + t + own))
+    assert rel[0] <= REL_RMS_BOUND and rel[1] <= REL_MAX_BOUND
+    assert t[0] <= max(TRUTH_FACTOR * own[0], TRUTH_FLOOR) and t[1] <= max(TRUTH_FACTOR * own[1], TRUTH_FLOOR)
+
+
+def test_what_frames_0_to_255_leave_at_the_later_passes():
+    """whether new input in frames [0, 256) still moves the output at frames 65 536 and 131 072 of the damping 0.25 low-pass: it does
+    not.  Under the swept cutoff (200 Hz at frame 0, rising) a pole of damping 0.25 decays by about exp( -0.25 * 2 pi 200 / 48000 ) a frame
+    or faster, which is exp( -400 ) over a pass: the scan model gives the same bits at both frames.  So tests/test_gpu_filter2.py holds no
+    such property on this case, and tests/test_gpu_filter.py holds it on a 1 Hz low-pass, which remembers"""
+    name = "low2_d025_n131857_run1"
+    c = R.long_case(name)
+    x = c["x"].copy()
+    x[:, :256] = R.noise(3, 256, 77) * F32(3)
+    a, b = R.call(c, run=1), R.call(c, run=1, x=x)
+    assert not np.array_equal(a[:, :256], b[:, :256])
+    for frame in (R.PASS_RUNS, 2 * R.PASS_RUNS):
+        assert np.array_equal(a[:, frame].view(np.uint32), b[:, frame].view(np.uint32)), frame
+    assert np.exp(-0.25 * 2 * np.pi * 200.0 / R.SR * R.PASS_RUNS) < 1e-150
+
+
+def test_a_1_hz_low_pass_of_damping_1_remembers_frames_0_to_255_two_passes_on():
+    """the case tests/test_gpu_filter2.py uses instead: order 1 at damping 1 is one section with both poles at the cutoff.  The scan
+    model's output moves by more than 8 ulps at frames 65 536 and 131 072 in every channel"""
+    x, other = R.memory_inputs()
+    a = R.filter2(x, R.SR, R.MEMORY_CUTOFF, 1.0, 0.0, R.LOW, 1, run=1)
+    b = R.filter2(other, R.SR, R.MEMORY_CUTOFF, 1.0, 0.0, R.LOW, 1, run=1)
+    for frame in (R.PASS_RUNS, 2 * R.PASS_RUNS):
+        moved = np.abs(a[:, frame].astype(F64) - b[:, frame].astype(F64)) / np.spacing(np.abs(a[:, frame]))
+        print("frame %d: moved by %s ulps" % (frame, moved))
+        assert np.all(moved > 8.0), frame
+
+
 def test_one_run_of_the_scan_model_is_the_sequential_loop():
     for name in ("n1_low3", "n15_highshelf4", "n16_band2"):
         got = R.call(R.case(name), run=16)

@@ -27,6 +27,74 @@ def test_the_scan_model_meets_the_truth_condition(name):
         assert rms <= max(TRUTH_FACTOR * own_rms, TRUTH_FLOOR) and mx <= max(TRUTH_FACTOR * own_max, TRUTH_FLOOR), (name, run)
 
 
+# against the fp32 loop: the bounds of tests/test_gpu_filter.py
+REL_RMS_BOUND = 1.2e-7
+REL_MAX_BOUND = 6.0e-7
+
+
+def missed(name, figures):
+    """prints every window's figures, then returns the windows that miss the conditions tests/test_gpu_filter.py puts on the device"""
+    out = []
+    for label, (rel_rms, rel_max), (t_rms, t_max), (own_rms, own_max) in figures:
+        print("%s %s: vs the fp32 loop %.3e %.3e; vs truth %.3e %.3e (the fp32 loop: %.3e %.3e)" % (name, label, rel_rms, rel_max, t_rms, t_max, own_rms, own_max))
+        if not (rel_rms <= REL_RMS_BOUND and rel_max <= REL_MAX_BOUND):
+            out.append((label, "loop", rel_rms, rel_max))
+        if not (t_rms <= max(TRUTH_FACTOR * own_rms, TRUTH_FLOOR) and t_max <= max(TRUTH_FACTOR * own_max, TRUTH_FLOOR)):
+            out.append((label, "truth", t_rms, t_max, own_rms, own_max))
+    return out
+
+
+@pytest.mark.parametrize("name", ["low3_n131857_run1", "high2_n131857_run1", "low3_n1052688"])
+def test_the_scan_model_meets_the_conditions_past_one_pass_of_the_carry(name):
+    """what tests/test_gpu_filter.py asks of the device on rows of more than 256 blocks, whole and window by window, a correct scan gives"""
+    c = R.long_case(name)
+    run = c["run"] or R.RUN
+    got = R.filter_1pole(c["x"], c["sr"], c["cutoff"], c["kind"], c["order"], run=run)
+    assert [w[0] for w in R.windows(c["x"].shape[1], run)] == (["whole", "pass 0", "pass 1", "pass 1 head", "pass 2", "pass 2 head"] if c["run"] else
+                                                                 ["whole", "pass 0", "pass 1", "pass 1 head"])
+    failures = missed(name, R.figures(got, R.long_expected(name, F32), R.long_expected(name, F64), c["x"], run))
+    assert not failures, failures
+
+
+def test_a_state_lost_between_two_passes_misses_the_conditions_where_it_is_lost():
+    """the carry kernel forgetting its state at the start of its second pass: frames from 65 536 on are filtered from a zero state.  The
+    first block of the pass misses its allowance 1e4 times over; 8192 frames on the filter has forgotten, which is why the whole-signal
+    figures are not enough and the windows are there"""
+    name = "low3_n131857_run1"
+    c = R.long_case(name)
+    cut = R.PASS_RUNS
+    broken = np.concatenate([R.filter_1pole(c["x"][:, :cut], c["sr"], c["cutoff"][:cut], c["kind"], c["order"], run=1),
+                             R.filter_1pole(c["x"][:, cut:], c["sr"], c["cutoff"][cut:], c["kind"], c["order"], run=1)], axis=1)
+    want, truth = R.long_expected(name, F32), R.long_expected(name, F64)
+    by_label = {f[0]: f for f in R.figures(broken, want, truth, c["x"], 1)}
+    _, (rel_rms, rel_max), (t_rms, t_max), (own_rms, own_max) = by_label["pass 1 head"]
+    print("lost state, pass 1 head: vs the fp32 loop %.3e %.3e; vs truth %.3e %.3e (the fp32 loop: %.3e %.3e)" % (rel_rms, rel_max, t_rms, t_max, own_rms, own_max))
+    assert rel_rms >= 1e4 * REL_RMS_BOUND and rel_max >= 1e4 * REL_MAX_BOUND
+    assert t_rms >= 1e4 * max(TRUTH_FACTOR * own_rms, TRUTH_FLOOR) and t_max >= 1e4 * max(TRUTH_FACTOR * own_max, TRUTH_FLOOR)
+    assert {"whole", "pass 1", "pass 1 head"} <= {m[0] for m in missed("lost state", by_label.values())}
+    later = cut + 8192
+    n = c["x"].shape[1]
+    rel = R.errors_over(broken, want, c["x"], later, n)
+    t, own = R.errors_over(broken, truth, c["x"], later, n), R.errors_over(want, truth, c["x"], later, n)
+    print("lost state, from frame %d on: vs the fp32 loop %.3e %.3e; vs truth %.3e %.3e (the fp32 loop: %.3e %.3e)" % ((later,) + rel + t + own))
+    assert rel[0] <= REL_RMS_BOUND and rel[1] <= REL_MAX_BOUND
+    assert t[0] <= max(TRUTH_FACTOR * own[0], TRUTH_FLOOR) and t[1] <= max(TRUTH_FACTOR * own[1], TRUTH_FLOOR)
+
+
+def test_a_1_hz_low_pass_remembers_frames_0_to_255_two_passes_on():
+    """the case tests/test_gpu_filter.py uses to see the state flow through a whole pass of the carry kernel: under the swept cutoffs
+    nothing of frames [0, 256) is left at frame 65 536, under a 1 Hz first-order low-pass the state decays by exp( -2 pi / 48000 ) a
+    frame, 1.9e-4 over a pass and 3.5e-8 over two.  The scan model's output moves by more than 8 ulps at both frames in every channel"""
+    x, other = R.memory_inputs()
+    a = R.filter_1pole(x, R.SR, R.MEMORY_CUTOFF, R.BUTTERWORTH_LOW, 1, run=1)
+    b = R.filter_1pole(other, R.SR, R.MEMORY_CUTOFF, R.BUTTERWORTH_LOW, 1, run=1)
+    assert np.array_equal(x[:, 256:], other[:, 256:])
+    for frame in (R.PASS_RUNS, 2 * R.PASS_RUNS):
+        moved = np.abs(a[:, frame].astype(F64) - b[:, frame].astype(F64)) / np.spacing(np.abs(a[:, frame]))
+        print("frame %d: moved by %s ulps" % (frame, moved))
+        assert np.all(moved > 8.0), frame
+
+
 def test_one_run_of_the_scan_model_is_the_sequential_loop():
     for name in ("n1_low3_noise_sweep", "n15_high4_noise_wobble", "n16_rlow16_sine_random"):
         c = R.case(name)

@@ -166,3 +166,83 @@ def test_order_zero():
         if c["kind"] != R.NOTCH:
             assert same_bits(run_dev(c, alias=True), want), c["name"]
     assert {c["kind"] for c in R.CASES if c["order"] == 0} == set(range(9))
+
+
+# ---- rows longer than one pass of the carry kernel ---------------------------------------------------------------
+# k_scan_carry turns 256 block totals a pass into carried states; every case above is 49 blocks at the most.  The rows of
+# filter2_reference.LONG are 256 blocks exactly, 257, and 516 in three passes at a run of 1, and 258 at the default run.
+THREE_PASSES = ("low2_d025_n%d_run1" % R.N_THREE_PASSES, "highshelf3_dcurve_p6_n%d_run1" % R.N_THREE_PASSES)
+
+
+def run_long(c, x=None):
+    with fa.filter_run_forced(c["run"] or 0):
+        return run(c, x)
+
+
+def run_long_dev(c, alias=False):
+    with fa.filter_run_forced(c["run"] or 0):              # the workspace is sized for the run as well
+        copies = {k: v if np.isscalar(v) else np.array(v) for k, v in c.items() if k in ("x", "cutoff", "damping", "gain")}      # the long cases are read-only
+        return run_dev(dict(c, **copies), alias)
+
+
+@pytest.mark.parametrize("name", R.LONG_IDS)
+def test_rows_longer_than_one_pass_of_the_carry_kernel(name):
+    """the conditions of test_against_the_restatement_and_the_truth (parity cases) over the whole row, over every pass's frames and over
+    the first block of every pass after the first, each divided by the rms and the peak of the whole input"""
+    c = R.long_case(name)
+    got = run_long(c)
+    want, truth = R.long_expected(name, F32), R.long_expected(name, F64)
+    assert got.shape == want.shape and got.dtype == F32
+    failures = []
+    run_ = c["run"] or R.RUN
+    for (label, lo, hi), (_, (rel_rms, rel_max), (t_rms, t_max), (own_rms, own_max)) in zip(R.windows(got.shape[1], run_), R.figures(got, want, truth, c["x"], run_)):
+        print("%s %s: vs restatement rel_rms=%.3e rel_max=%.3e; vs truth rel_rms=%.3e rel_max=%.3e (the restatement: %.3e, %.3e)"
+              % (name, label, rel_rms, rel_max, t_rms, t_max, own_rms, own_max))
+        if not (rel_rms <= R.rms_bound(lo, hi) and rel_max <= REL_MAX_BOUND):       # a window of one frame: filter2_reference.rms_bound
+            failures.append((label, "restatement", rel_rms, rel_max))
+        if not (t_rms <= max(TRUTH_FACTOR * own_rms, TRUTH_FLOOR) and t_max <= max(TRUTH_FACTOR * own_max, TRUTH_FLOOR)):
+            failures.append((label, "truth", t_rms, t_max, own_rms, own_max))
+    assert not failures, failures
+
+
+def test_later_input_does_not_reach_an_earlier_pass_of_the_carry_kernel():
+    cut = R.PASS_RUNS
+    for name in THREE_PASSES:
+        c = R.long_case(name)
+        x = c["x"].copy()
+        x[:, cut:] = R.noise(x.shape[0], x.shape[1] - cut, 56) * F32(3)
+        a, b = run_long(c), run_long(c, x)
+        assert same_bits(a[:, :cut], b[:, :cut]), name
+        assert not np.any(a[:, cut] == b[:, cut]) and not same_bits(a[:, 2 * cut:], b[:, 2 * cut:]), name
+
+
+def test_the_state_flows_through_a_whole_pass_of_the_carry_kernel():
+    """under the swept cutoff the damping 0.25 low-pass has forgotten frames [0, 256) long before frame 65 536
+    (tests/test_filter2_reference.py), so the matrix of a pass's total is held on a 1 Hz low-pass of damping 1, two equal real poles:
+    what frames [0, 256) hold moves the output at frames 65 536 and 131 072"""
+    x, other = R.memory_inputs()
+    with fa.filter_run_forced(1):
+        a = fa.filter2(x, R.SR, R.MEMORY_CUTOFF, 1.0, 0.0, kind=R.LOW, order=1)
+        b = fa.filter2(other, R.SR, R.MEMORY_CUTOFF, 1.0, 0.0, kind=R.LOW, order=1)
+    for frame in (R.PASS_RUNS, 2 * R.PASS_RUNS):
+        assert not np.any(a[:, frame] == b[:, frame]), frame
+
+
+def test_long_rows_are_independent():
+    """k_scan_carry finds its row's totals at blockIdx.x * blocks, with 516 blocks a row"""
+    for name in THREE_PASSES:
+        c = R.long_case(name)
+        assert c["x"].shape[0] == 3
+        out = run_long(c)
+        for k in range(3):
+            assert same_bits(run_long(c, c["x"][k:k + 1])[0], out[k]), (name, k)
+        assert same_bits(run_long(c, c["x"][::-1])[::-1], out), name
+
+
+def test_long_rows_host_and_device_forms_are_bit_identical():
+    for name in THREE_PASSES:
+        c = R.long_case(name)
+        host = run_long(c)
+        assert same_bits(run_long_dev(c), host), name
+        assert same_bits(run_long_dev(c, alias=True), host), name    # out aliasing the input
+        assert same_bits(run_long(c), host), name                    # a second call
