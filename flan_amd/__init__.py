@@ -185,6 +185,15 @@ _SIGS = {
     "flanhip_audio_to_stereo_dev": (C.c_int, [_vp, _i64, _vp, _vp]),
     "flanhip_audio_to_mono_dev": (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "flanhip_audio_copy_rows_dev": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp]),
+    "flanhip_audio_local_wavelengths_count": (_i64, [_i64] * 5),
+    "flanhip_audio_local_wavelengths_workspace_bytes": (C.c_size_t, [_i64] * 5),
+    "flanhip_audio_yin_dprime_dev": (C.c_int, [_vp] + [_i64] * 5 + [_vp, _vp]),
+    "flanhip_audio_yin_pick_dev": (C.c_int, [_vp, _i64, _i64, _f32, _i64, _vp, _vp]),
+    "flanhip_audio_local_wavelengths_dev": (C.c_int, [_vp] + [_i64] * 5 + [_f32, _i64, _vp, _vp, _vp]),
+    "flanhip_audio_local_wavelength_dev": (C.c_int, [_vp, _i64, _f32, _i64, _vp, _vp]),
+    "flanhip_audio_local_wavelengths": (C.c_int, [_vp, _i64, _f32] + [_i64] * 4 + [_f32, _i64, _vp, _vp]),
+    "flanhip_wavelength_continuity": (C.c_int, [_vp, _i64, _f32, _i64]),
+    "flanhip_average_wavelength": (C.c_int, [_vp, _i64, _f32, _f32, _vp]),
 }
 
 EXPORTS = sorted(_SIGS)
@@ -1293,3 +1302,60 @@ def audio_to_mono_dev(d_audio, ch, n, d_out, stream=None):
 
 def audio_copy_rows_dev(d_src, src_stride, rows, src_frames, d_dst, dst_stride, dst_frames, stream=None):
     check(lib.flanhip_audio_copy_rows_dev(_dp(d_src), src_stride, rows, src_frames, _dp(d_dst), dst_stride, dst_frames, _vp(stream or 0)))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Audio::get_local_wavelengths and its family (the YIN pitch tracker).  x is one channel row
+# ---------------------------------------------------------------------------------------------------------------
+
+def local_wavelengths_count(num_frames, start=0, end=-1, window=2048, hop=128):
+    """the number of analysis windows; -1 for arguments the C ABI refuses as invalid"""
+    return int(lib.flanhip_audio_local_wavelengths_count(num_frames, start, end, window, hop))
+
+
+def local_wavelengths_workspace_bytes(num_frames, start=0, end=-1, window=2048, hop=128):
+    return int(lib.flanhip_audio_local_wavelengths_workspace_bytes(num_frames, start, end, window, hop))
+
+
+def yin_dprime_dev(d_x, num_frames, start, end, window, hop, d_dprime, stream=None):
+    """d_dprime: float32 [count][window // 2] on the device"""
+    check(lib.flanhip_audio_yin_dprime_dev(_dp(d_x), num_frames, start, end, window, hop, _dp(d_dprime), _vp(stream or 0)))
+
+
+def yin_pick_dev(d_dprime, count, h, absolute_cutoff, minimum_wavelength, d_out, stream=None):
+    check(lib.flanhip_audio_yin_pick_dev(_dp(d_dprime), count, h, absolute_cutoff, minimum_wavelength, _dp(d_out), _vp(stream or 0)))
+
+
+def local_wavelengths_dev(d_x, num_frames, start, end, window, hop, absolute_cutoff, minimum_wavelength, d_out, d_ws, stream=None):
+    """the raw per-window wavelengths (no continuity pass), one launch"""
+    check(lib.flanhip_audio_local_wavelengths_dev(_dp(d_x), num_frames, start, end, window, hop, absolute_cutoff, minimum_wavelength,
+                                                  _dp(d_out), _dp(d_ws), _vp(stream or 0)))
+
+
+def local_wavelength_dev(d_window, window, absolute_cutoff, minimum_wavelength, d_out, stream=None):
+    check(lib.flanhip_audio_local_wavelength_dev(_dp(d_window), window, absolute_cutoff, minimum_wavelength, _dp(d_out), _vp(stream or 0)))
+
+
+def local_wavelengths(x, sample_rate, start=0, end=-1, window=2048, hop=128, absolute_cutoff=0.2, minimum_wavelength=10, cancel=None):
+    """Audio::get_local_wavelengths.  x float32 [n] -> float32 [count], continuity pass included.  cancel: None or a ctypes.c_int"""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    count = local_wavelengths_count(x.size, start, end, window, hop)
+    out = np.empty(max(count, 0), np.float32)
+    check(lib.flanhip_audio_local_wavelengths(_ptr(x), x.size, sample_rate, start, end, window, hop, absolute_cutoff, minimum_wavelength,
+                                              _ptr(out), None if cancel is None else C.cast(C.byref(cancel), _vp)))
+    return out
+
+
+def wavelength_continuity(w, sample_rate, hop):
+    """the continuity pass of Audio::get_local_wavelengths on a copy of w"""
+    out = np.array(w, np.float32).reshape(-1)
+    check(lib.flanhip_wavelength_continuity(_ptr(out), out.size, sample_rate, hop))
+    return out
+
+
+def average_wavelength(locals_, min_active_ratio=0.0, max_length_sigma=-1.0):
+    """Audio::get_average_wavelength( locals, ... )"""
+    w = np.ascontiguousarray(locals_, np.float32).reshape(-1)
+    out = C.c_float(0.0)
+    check(lib.flanhip_average_wavelength(_ptr(w), w.size, min_active_ratio, max_length_sigma, C.cast(C.byref(out), _vp)))
+    return np.float32(out.value)

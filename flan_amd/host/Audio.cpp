@@ -1,7 +1,8 @@
 // Audio.cpp -- construction and conversions of flan::Audio over the C ABI
 // (reference: src/flan/Audio/AudioConstructors.cpp, Conversions/AudioPV.cpp:12-84, Audio/AudioConversions.cpp:14-56,
 // Audio/AudioCombination.cpp:299-352, Audio/AudioTemporal.cpp:236-299, Audio/AudioVolume.cpp:5-67, 190-278,
-// Audio/AudioFilter.cpp:280-758, 988-1263, Audio/AudioConversions.cpp:58-104, Audio/AudioChannels.cpp, Audio/AudioSpatial.cpp).
+// Audio/AudioFilter.cpp:280-758, 988-1263, Audio/AudioConversions.cpp:58-104, Audio/AudioChannels.cpp, Audio/AudioSpatial.cpp,
+// Audio/AudioInformation.cpp:138-304, 388-407).
 #include "flan/Audio.h"
 
 #include <algorithm>
@@ -841,6 +842,114 @@ Audio Audio::stereo_spatialize( const Function<Second, vec2> & position, Meter h
 		return Audio::create_null();
 	call.launch( flanhip_spatial_itd_dev( shaped, 2, n, sr, stretches.data(), count, out_frames, f.num_frames, out, ws, nullptr ) );
 	return or_null( call.finish<AudioBuffer>( f ) );                               // combine_channels( l, r ) (:280): the longer ear's length
+	}
+
+// ---- information (Audio/AudioInformation.cpp) -----------------------------------------------------------------------------------------------
+// `count` floats that launch( d_out ) leaves on the device, brought to the host; false (and `who` on std::cerr) if anything failed
+template<typename Launch>
+static bool wavelengths_call( const char * who, std::vector<float> & out, size_t ws_bytes, Launch launch )
+	{
+	DeviceCall call( who );
+	float * d_out = call.output<float>( out.size() );
+	void * ws = ws_bytes == detail::kNoWorkspace ? nullptr : call.workspace( ws_bytes );
+	if( !call.ok() || !call.launch( launch( d_out, ws ) ) || !call.sync() ) return false;
+	if( detail::download_to_host( out.data(), d_out, sizeof( float ) * out.size() ) ) return true;
+	std::cerr << "flan: " << who << ": download failed: " << flanhip_last_error() << std::endl;
+	return false;
+	}
+
+float Audio::get_local_wavelength( Channel channel, Frame start, Frame window_size, float absolute_cutoff, Frame minimum_wavelength ) const
+	{
+	if( is_null() ) return 0;                                                      // :140
+	if( channel < 0 || channel >= get_num_channels() || start < 0 || window_size < 1 || start > get_num_frames() - window_size )
+		{
+		std::cerr << "flan: get_local_wavelength: the window lies outside the signal" << std::endl;      // the reference reads past its buffer
+		return 0;
+		}
+	const float * d_x = device_data();
+	if( !d_x ) return 0;
+	std::vector<float> out( 1 );
+	const float * d_window = d_x + size_t( channel ) * size_t( get_num_frames() ) + size_t( start );     // :143 get_sample_pointer( channel, start )
+	if( !wavelengths_call( "get_local_wavelength", out, detail::kNoWorkspace, [&]( float * d_out, void * )
+		{ return flanhip_audio_local_wavelength_dev( d_window, window_size, absolute_cutoff, minimum_wavelength, d_out, nullptr ); } ) ) return 0;
+	return out[0];
+	}
+
+std::vector<fFrame> Audio::get_local_wavelengths( Channel channel, Frame start, Frame end, Frame window_size, Frame hop, float absolute_cutoff,
+	Frame minimum_wavelength, flan_CANCEL_ARG_CPP ) const
+	{
+	if( is_null() ) return std::vector<float>();                                   // :178
+	if( canceller ) return std::vector<float>();                                   // :185
+	const Frame n = get_num_frames();
+	const int64_t count = flanhip_audio_local_wavelengths_count( n, start, end, window_size, hop );      // :180-187
+	const size_t ws_bytes = flanhip_audio_local_wavelengths_workspace_bytes( n, start, end, window_size, hop );
+	if( channel < 0 || channel >= get_num_channels() || count < 0 || ws_bytes == 0 )
+		{
+		std::cerr << "flan: get_local_wavelengths: a channel, range, hop or window the device does not take (windows go up to 16384 frames)" << std::endl;
+		return std::vector<float>();
+		}
+	if( count == 0 ) return std::vector<float>();                                  // :188
+	const float * d_x = device_data();
+	if( !d_x ) return std::vector<float>();
+	std::vector<fFrame> out( static_cast<size_t>( count ) );
+	if( !wavelengths_call( "get_local_wavelengths", out, ws_bytes, [&]( float * d_out, void * ws )
+		{
+		return flanhip_audio_local_wavelengths_dev( d_x + size_t( channel ) * size_t( n ), n, start, end, window_size, hop, absolute_cutoff, minimum_wavelength,
+			d_out, ws, nullptr );
+		} ) ) return std::vector<float>();
+	if( canceller ) return std::vector<float>();
+	flanhip_wavelength_continuity( out.data(), count, get_sample_rate(), hop );    // :190-226
+	return out;
+	}
+
+float Audio::get_average_wavelength( Channel channel, float min_active_ratio, float max_length_sigma, Frame start, Frame end, Frame window_size, Frame hop,
+	flan_CANCEL_ARG_CPP ) const
+	{
+	if( is_null() ) return 0;                                                      // :241
+	return get_average_wavelength( get_local_wavelengths( channel, start, end, window_size, hop, 0.2f, 10, canceller ), min_active_ratio, max_length_sigma );
+	}
+
+float Audio::get_average_wavelength( const std::vector<float> & locals, float min_active_ratio, float max_length_sigma ) const
+	{
+	if( is_null() ) return 0;                                                      // :251
+	float mean = 0;
+	flanhip_average_wavelength( locals.data(), int64_t( locals.size() ), min_active_ratio, max_length_sigma, &mean );
+	return mean;
+	}
+
+Frequency Audio::get_local_frequency( Channel channel, Frame start, Frame window_size, flan_CANCEL_ARG_CPP ) const
+	{
+	(void) canceller;
+	const fFrame wavelength = get_local_wavelength( channel, start, window_size, 0.2f, 10 );     // :269
+	return get_sample_rate() / wavelength;                                         // a 0 gives infinity, as in the reference
+	}
+
+std::vector<Frequency> Audio::get_local_frequencies( Channel channel, Frame start, Frame end, Frame window_size, Frame hop, flan_CANCEL_ARG_CPP ) const
+	{
+	std::vector<fFrame> wavelengths = get_local_wavelengths( channel, start, end, window_size, hop, 0.2f, 10, canceller );      // :298
+	for( float & w : wavelengths ) if( w != 0 ) w = get_sample_rate() / w;         // :299-303
+	return wavelengths;
+	}
+
+Function<Second, Amplitude> Audio::get_frequency_envelope() const
+	{
+	if( is_null() ) return 0.0f;
+	const int hop_size = 128;                                                      // :391-392
+	std::vector<Frequency> frequencies = convert_to_mono().get_local_frequencies( 0, 0, -1, 2048, hop_size );
+	if( frequencies.empty() ) return 0.0f;                                         // the reference's lambda would read an empty vector
+	return [frequencies = std::move( frequencies ), sample_rate = get_sample_rate(), hop_size]( Second t )      // :394-406
+		{
+		const float x = t * sample_rate / hop_size;
+		if( 0 <= x && x < frequencies.size() - 1 )
+			{
+			const Frame x1 = std::floor( x );
+			const float y1 = frequencies[x1];
+			const float y2 = frequencies[x1 + 1];
+			const float m = ( y2 - y1 ) / 1;
+			return y1 + m * ( x - x1 );
+			}
+		else return 0.0f;
+		};
 	}
 
 } // namespace flan

@@ -243,6 +243,37 @@ public:
 	Audio stereo_spatialize( const Function<Second, vec2> & position, Meter head_width = 0.18f,
 		const Function<Second, float> & speed_limit = std::numeric_limits<float>::max() ) const;
 
+	// ---- information ----
+	/** The wavelength, in frames, of one window of one channel by the YIN method (Audio/AudioInformation.cpp:138-166): the cumulative-mean-
+	 *  normalised difference function d' of the window_size samples from start (:18-75), its valleys with parabolic interpolation
+	 *  (DSPUtility.cpp:37-147) and, among the valleys beyond minimum_wavelength, the first one within a factor 2 of the lowest, if it is below
+	 *  absolute_cutoff; 0 where nothing is found.  On the device (flanhip_audio_local_wavelength_dev): d as the sum it is defined
+	 *  as, not through the reference's fp32 FFTs, so results agree with the reference to its own accuracy, not bit for bit.  Kept quirk: on an
+	 *  exactly periodic window the lowest valley's y is 0 or below, nothing is below twice that, and the answer is 0.  window_size up to 16384.
+	 *  A null *this gives 0; so does a channel or window outside the signal, with one line on std::cerr. */
+	float get_local_wavelength( Channel channel, Frame start, Frame window_size = 2048, float absolute_cutoff = 0.2f, Frame minimum_wavelength = 10 ) const;
+	/** get_local_wavelength at start, start + hop, ... while frame + window_size < end (end == -1: the signal's end), all windows in one launch,
+	 *  then the reference's octave-continuity pass on the host (:168-229): a doubling of the wavelength that lasts at most a tenth of a second
+	 *  is halved; the first longer one ends the pass.  A null *this, no window, a raised canceller and arguments the device refuses give an
+	 *  empty vector. */
+	std::vector<float> get_local_wavelengths( Channel channel, Frame start = 0, Frame end = -1, Frame window_size = 2048, Frame hop = 128,
+		float absolute_cutoff = 0.2f, Frame minimum_wavelength = 10, flan_CANCEL_ARG ) const;
+	/** The mean of the non-zero wavelengths (:245-265), in fp32 on the host: -1 unless more than min_active_ratio of the entries differ from -1
+	 *  (kept quirk: undetected windows are 0, not -1, so they count as active and are then left out of the mean), and -1 if max_length_sigma
+	 *  != -1 and the standard deviation exceeds it.  A null *this gives 0. */
+	float get_average_wavelength( const std::vector<float> & local_wavelengths, float min_active_ratio = 0, float max_length_sigma = -1 ) const;
+	/** get_average_wavelength( get_local_wavelengths( channel, start, end, window_size, hop ), ... ) (:231-243) */
+	float get_average_wavelength( Channel channel, float min_active_ratio = 0, float max_length_sigma = -1, Frame start = 0, Frame end = -1,
+		Frame window_size = 2048, Frame hop = 128, flan_CANCEL_ARG ) const;
+	/** sample rate / get_local_wavelength( channel, start, window_size, 0.2f, 10 ) (:267-270): infinity where no wavelength is found, as in
+	 *  the reference. */
+	Frequency get_local_frequency( Channel channel, Frame start = 0, Frame window_size = 2048, flan_CANCEL_ARG ) const;
+	/** get_local_wavelengths( ..., 0.2f, 10 ) with every non-zero wavelength turned into sample rate / wavelength (:296-304); a 0 stays 0. */
+	std::vector<Frequency> get_local_frequencies( Channel channel, Frame start = 0, Frame end = -1, Frame window_size = 2048, Frame hop = 128, flan_CANCEL_ARG ) const;
+	/** convert_to_mono().get_local_frequencies( 0, 0, -1, 2048, 128 ) as a function of time, linear between the hops and 0 outside them
+	 *  (:388-407).  Where the reference would read an empty vector (a null *this, a signal of 2048 frames or fewer) the function is 0. */
+	Function<Second, Amplitude> get_frequency_envelope() const;
+
 	// the older camelCase spellings BASELINE.json's north_star uses
 	PV convertToPV( Frame window_size = 2048, Frame hop = 128, Frame dft_size = 4096, flan_CANCEL_ARG ) const;
 	};

@@ -878,6 +878,64 @@ int flanhip_audio_to_mono_dev(const float * d_audio, int64_t num_channels, int64
 int flanhip_audio_copy_rows_dev(const float * d_src, int64_t src_stride, int64_t num_rows, int64_t src_frames,
                                 float * d_dst, int64_t dst_stride, int64_t dst_frames, void * stream);
 
+/* ---- Audio::get_local_wavelength(s), get_average_wavelength (Audio/AudioInformation.cpp:18-75, 138-265; DSPUtility.h:19-20,
+ * DSPUtility.cpp:37-147, 149-185): the YIN pitch tracker (flan_amd/csrc/pitch.hip) ------------------------------------ */
+/* x: ONE channel row of num_frames floats.  Analysis windows of `window` samples begin at start, start + hop, ... while frame + window <
+ * end (:180-183); end == -1 means num_frames.  Per window, with n = window and h = n / 2:
+ *   compute_d (:18-57)        d[tau] = sum_{i<h} ( x[i] - x[i+tau] )^2 for tau < h.  The reference gets it as p0 + p_tau - 2 r[tau] from two
+ *                             fp32 FFTs; here it is the sum itself -- fp32 differences, fmaf, 32 terms chained in fp32, the chunks added in
+ *                             fp64 --, rounded to fp32 once: every term is >= 0 and nothing cancels, so it is closer to the exact sum than
+ *                             the reference is and NOT bit-identical to it
+ *   compute_d_prime (:59-75)  d'[0] = 1; a running double sum of the fp32 d; d'[tau] = float( double( d[tau] ) * ( tau / sum ) ), 1 where
+ *                             the sum is 0.  Silence and a constant give d' == 1 exactly
+ *   find_valleys( d' ) with its defaults (DSPUtility.h:19-20, DSPUtility.cpp:55-147): interior points 1 ... h - 2; a point is a valley if
+ *                             the first differing value on either side is greater (an edge reached over equal values disqualifies); of a
+ *                             plateau (right - left > 2) only the point floor( ( right + left ) * 0.5 ) counts, with x = that mean and y
+ *                             the plain value; otherwise ( x, y ) = parabolic_interpolation (:37-43) of -d' with y negated, in fp32,
+ *                             operation by operation; ordered by x
+ *   the selection (:149-165)  k = the first valley with float( minimum_wavelength ) < x (none: 0); lowest = the first minimum of y from k
+ *                             on; best = the first valley from k on with y < lowest.y * 2, or ( 0, 0 ) if there is none -- which is what
+ *                             happens when lowest.y <= 0, as on an exactly periodic signal: the reference's behaviour, kept --; the
+ *                             result is best.x if best.y < absolute_cutoff, else 0
+ * For the same d' bits flanhip_audio_yin_pick_dev gives the bits of the reference's arithmetic.  Deviation: a d' row that holds a NaN or
+ * an infinity gives 0 (the reference's walk then depends on where they lie); rows are promised while |d'| stays far inside fp32's range
+ * (d' <= h when it comes from compute_d_prime).
+ * Every form refuses, with FLANHIP_ERR_INVALID_ARG and before any device call, null pointers, hop < 1, start < 0, end > num_frames (or
+ * below -1), window < 1 and num_frames < 0; window > 16384 (a block keeps the window and its d' in LDS) is FLANHIP_ERR_UNSUPPORTED.  With
+ * h < 3 no interior point exists: zeros, without a launch. */
+/* the number of windows (pure host arithmetic); -1 for arguments the forms refuse as invalid */
+int64_t flanhip_audio_local_wavelengths_count(int64_t num_frames, int64_t start, int64_t end, int64_t window, int64_t hop);
+/* d_dprime: float[count][h], d' of every window */
+int flanhip_audio_yin_dprime_dev(const float * d_x, int64_t num_frames, int64_t start, int64_t end, int64_t window, int64_t hop,
+                                 float * d_dprime, void * stream);
+/* d_dprime: float[count][h] -> d_out: float[count], valleys and selection.  h > 8192 is FLANHIP_ERR_UNSUPPORTED */
+int flanhip_audio_yin_pick_dev(const float * d_dprime, int64_t count, int64_t h, float absolute_cutoff, int64_t minimum_wavelength,
+                               float * d_out, void * stream);
+/* bytes of device workspace flanhip_audio_local_wavelengths_dev asks for (pure host arithmetic; 0 for arguments it refuses): 16 for every
+ * shape served today -- the fused launch keeps a window's d' in LDS and leaves nothing there; the block is reserved for windows beyond LDS */
+size_t flanhip_audio_local_wavelengths_workspace_bytes(int64_t num_frames, int64_t start, int64_t end, int64_t window, int64_t hop);
+/* d_out: float[count], the RAW per-window wavelengths (no continuity pass), both steps in one launch: bit-identical to
+ * flanhip_audio_yin_dprime_dev followed by flanhip_audio_yin_pick_dev */
+int flanhip_audio_local_wavelengths_dev(const float * d_x, int64_t num_frames, int64_t start, int64_t end, int64_t window, int64_t hop,
+                                        float absolute_cutoff, int64_t minimum_wavelength, float * d_out, void * d_workspace, void * stream);
+/* Audio::get_local_wavelength (:138-166): one window, d_window[0 .. window) -> d_out[0] */
+int flanhip_audio_local_wavelength_dev(const float * d_window, int64_t window, float absolute_cutoff, int64_t minimum_wavelength,
+                                       float * d_out, void * stream);
+/* Audio::get_local_wavelengths (:168-229), host pointers: out float[count], the windows' wavelengths after the continuity pass.  Only the
+ * frames the windows read are uploaded.  `cancel` is polled before the upload, before the launch, while it runs and before the continuity pass. */
+int flanhip_audio_local_wavelengths(const float * x, int64_t num_frames, float sample_rate, int64_t start, int64_t end, int64_t window, int64_t hop,
+                                    float absolute_cutoff, int64_t minimum_wavelength, float * out, volatile int * cancel);
+/* The continuity pass (:190-226), host-only, in place, as written: minimum_num_hops = int( ( 0.1f * sample_rate ) / float( hop ) ); the
+ * hops i + 1 with 1.95 < w[i+1] / w[i] < 2.05 (w[i] != 0) are collected first; for each, the doubling's length is counted while the ratio to
+ * w[hop] stays in [.95, 1.05] (a 0 is counted and skipped: the `continue` goes to the loop's condition), up to minimum_num_hops + 1; a
+ * longer one is a new note and ENDS the pass (the `break` leaves the loop over the hops), a shorter one is halved -- so later ratios are
+ * taken against halved values.  hop < 1 or count < 0 is FLANHIP_ERR_INVALID_ARG. */
+int flanhip_wavelength_continuity(float * w, int64_t count, float sample_rate, int64_t hop);
+/* Audio::get_average_wavelength( locals, ... ) (:245-265) with mean_and_sd (DSPUtility.cpp:159-185), host-only, fp32 in order: -1 unless
+ * more than min_active_ratio * count entries differ from -1; then the mean of the entries that differ from 0 (a -1 stays in), or -1 if
+ * max_length_sigma != -1 and their standard deviation exceeds it.  No non-zero entry: mean and deviation are 0. */
+int flanhip_average_wavelength(const float * locals, int64_t count, float min_active_ratio, float max_length_sigma, float * out);
+
 /* ---- Audio::resample (Audio/AudioConversions.cpp:14-30, r8brain CDSPResampler with default parameters) --------- */
 /* AudioConversions.cpp:22: out frames = Frame( float(num_frames) * ( dst_rate / src_rate ) ) */
 int64_t flanhip_resample_out_frames(int64_t num_frames, float src_rate, float dst_rate);
