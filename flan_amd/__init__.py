@@ -194,6 +194,15 @@ _SIGS = {
     "flanhip_audio_local_wavelengths": (C.c_int, [_vp, _i64, _f32] + [_i64] * 4 + [_f32, _i64, _vp, _vp]),
     "flanhip_wavelength_continuity": (C.c_int, [_vp, _i64, _f32, _i64]),
     "flanhip_average_wavelength": (C.c_int, [_vp, _i64, _f32, _f32, _vp]),
+    "flanhip_grains_tile_frames": (_i64, []),
+    "flanhip_grains_batch_events": (_i64, []),
+    "flanhip_grains_events": (C.c_int, [_i64, _f32, _vp, _f32, _vp, _f32, C.c_uint64, _vp, _i64, _vp]),
+    "flanhip_grains_cut": (C.c_int, [_i64, _f32, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "flanhip_grains_cut_frames": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "flanhip_grains_plan": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64]),
+    "flanhip_grains_workspace_bytes": (C.c_size_t, [_i64, _i64]),
+    "flanhip_grains_mix_dev": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _f32, _vp, _vp, _vp]),
+    "flanhip_grains_mix": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _f32, _vp, _vp]),
 }
 
 EXPORTS = sorted(_SIGS)
@@ -1359,3 +1368,91 @@ def average_wavelength(locals_, min_active_ratio=0.0, max_length_sigma=-1.0):
     out = C.c_float(0.0)
     check(lib.flanhip_average_wavelength(_ptr(w), w.size, min_active_ratio, max_length_sigma, C.cast(C.byref(out), _vp)))
     return np.float32(out.value)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Audio::mix and the granular family (flan_amd/csrc/grains.hip): event tables are numpy records of GRAIN_EVENT
+# ---------------------------------------------------------------------------------------------------------------
+
+GRAIN_HANN = 1
+GRAIN_EVENT = np.dtype([("src", np.uint64), ("ch_stride", np.int64), ("src_frames", np.int64), ("o", np.int64), ("gain_offset", np.int64),
+                        ("s", np.int32), ("n", np.int32), ("channels", np.int32), ("sf", np.int32), ("ef", np.int32), ("flags", np.int32),
+                        ("gain", np.float32), ("reserved", np.int32)], align=True)      # flanhip_grain_event, 72 bytes
+
+
+def grains_tile_frames():
+    return int(lib.flanhip_grains_tile_frames())
+
+
+def grains_batch_events():
+    return int(lib.flanhip_grains_batch_events())
+
+
+def _curve(v, n):
+    """( pointer or None, scalar ) of a curve of n floats or a number; the array is returned to keep it alive"""
+    if np.ndim(v) == 0:
+        return None, None, float(v)
+    a = np.ascontiguousarray(v, np.float32).reshape(-1)
+    assert a.size == n
+    return a, _ptr(a), 0.0
+
+
+def grains_events(length_frames, sample_rate, rate, scatter=0.0, seed=0):
+    """integrate_event_rate: the event frames (int64).  rate / scatter: a number or length_frames floats"""
+    _r, rp, rs = _curve(rate, length_frames)
+    _s, sp, ss = _curve(scatter, length_frames)
+    out = np.empty(max(int(length_frames), 0), np.int64)
+    count = _i64(0)
+    check(lib.flanhip_grains_events(length_frames, sample_rate, rp, rs, sp, ss, seed, _ptr(out), out.size, C.cast(C.byref(count), _vp)))
+    return out[:count.value].copy()
+
+
+def grains_cut(num_frames, sample_rate, start_time, end_time, start_fade, end_fade, events=None):
+    """Audio::cut for a table of grains: s, n, sf, ef of the events (a fresh zeroed table unless one is given)"""
+    a = [np.ascontiguousarray(v, np.float32).reshape(-1) for v in (start_time, end_time, start_fade, end_fade)]
+    events = np.zeros(a[0].size, GRAIN_EVENT) if events is None else events
+    check(lib.flanhip_grains_cut(num_frames, sample_rate, a[0].size, _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), _ptr(events)))
+    return events
+
+
+def grains_cut_frames(num_frames, start, end, start_fade, end_fade, events=None):
+    a = [np.ascontiguousarray(v, np.int32).reshape(-1) for v in (start, end, start_fade, end_fade)]
+    events = np.zeros(a[0].size, GRAIN_EVENT) if events is None else events
+    check(lib.flanhip_grains_cut_frames(num_frames, a[0].size, _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), _ptr(events)))
+    return events
+
+
+def grains_plan(events, out_frames=0):
+    """( out_frames, tile_first, tile_last ) of an event table; out_frames 0: the reference's length, max( o + n )"""
+    events = np.ascontiguousarray(events, GRAIN_EVENT)
+    frames = _i64(out_frames)
+    check(lib.flanhip_grains_plan(_ptr(events), events.size, C.cast(C.byref(frames), _vp), None, None, 0))
+    tiles = -(-frames.value // grains_tile_frames())
+    first, last = np.empty(tiles, np.int32), np.empty(tiles, np.int32)
+    check(lib.flanhip_grains_plan(_ptr(events), events.size, C.cast(C.byref(frames), _vp), _ptr(first), _ptr(last), tiles))
+    return frames.value, first, last
+
+
+def grains_workspace_bytes(count, out_frames):
+    return int(lib.flanhip_grains_workspace_bytes(count, out_frames))
+
+
+def grains_mix_dev(events, tile_first, tile_last, d_gains, gain_floats, d_sources, sources_floats, num_channels, out_frames, sample_rate, d_out, d_ws,
+                   stream=None):
+    """events and the plan are host arrays; gains, sources, the output and the workspace live on the device"""
+    events = np.ascontiguousarray(events, GRAIN_EVENT)
+    first, last = np.ascontiguousarray(tile_first, np.int32), np.ascontiguousarray(tile_last, np.int32)
+    check(lib.flanhip_grains_mix_dev(_ptr(events), events.size, _ptr(first), _ptr(last), first.size, _dp(d_gains), gain_floats, _dp(d_sources),
+                                     sources_floats, num_channels, out_frames, sample_rate, _dp(d_out), _dp(d_ws), _vp(stream or 0)))
+
+
+def grains_mix(events, gains, sources, num_channels, out_frames, sample_rate, cancel=None):
+    """Audio::mix over host arrays: sources float32 (flat; the events' src are offsets into it) -> float32 [num_channels][out_frames]"""
+    events = np.ascontiguousarray(events, GRAIN_EVENT)
+    sources = np.ascontiguousarray(sources, np.float32).reshape(-1)
+    gains = None if gains is None else np.ascontiguousarray(gains, np.float32).reshape(-1)
+    out = np.full((num_channels, max(out_frames, 0)), np.nan, np.float32)
+    check(lib.flanhip_grains_mix(_ptr(events), events.size, None if gains is None else _ptr(gains), 0 if gains is None else gains.size,
+                                 _ptr(sources), sources.size, num_channels, out_frames, sample_rate, _ptr(out),
+                                 None if cancel is None else C.cast(C.byref(cancel), _vp)))
+    return out

@@ -2,11 +2,15 @@
 // (reference: src/flan/Audio/AudioConstructors.cpp, Conversions/AudioPV.cpp:12-84, Audio/AudioConversions.cpp:14-56,
 // Audio/AudioCombination.cpp:299-352, Audio/AudioTemporal.cpp:236-299, Audio/AudioVolume.cpp:5-67, 190-278,
 // Audio/AudioFilter.cpp:280-758, 988-1263, Audio/AudioConversions.cpp:58-104, Audio/AudioChannels.cpp, Audio/AudioSpatial.cpp,
-// Audio/AudioInformation.cpp:138-304, 388-407).
+// Audio/AudioInformation.cpp:138-304, 388-407, Audio/AudioCombination.cpp:78-237, Audio/AudioTemporal.cpp:190-234,
+// Audio/AudioSynthesis.cpp:310-473, 572-638).
 #include "flan/Audio.h"
 
 #include <algorithm>
+#include <atomic>
+#include <climits>
 #include <cmath>
+#include <ctime>
 #include <iostream>
 
 #include "device_call.h"
@@ -950,6 +954,380 @@ Function<Second, Amplitude> Audio::get_frequency_envelope() const
 			}
 		else return 0.0f;
 		};
+	}
+
+// ---- cutting, mixing and granular synthesis (Audio/AudioCombination.cpp, Audio/AudioTemporal.cpp:190-234, Audio/AudioSynthesis.cpp) ----------------
+namespace {
+
+// A table of events as the device takes it: every src a device address, the amplitudes that are not constants in one pool
+struct EventTable
+	{
+	std::vector<flanhip_grain_event> events;
+	std::vector<float> gains;
+	};
+
+flanhip_grain_event plain_event()
+	{
+	flanhip_grain_event e = {};
+	e.gain_offset = -1;
+	e.gain = 1.0f;
+	return e;
+	}
+
+// `a` as the source of an event; false if its samples cannot be had on the device
+bool point_at( const Audio & a, flanhip_grain_event & e )
+	{
+	const float * d = a.device_data();
+	if( !d ) return false;
+	e.src = uint64_t( reinterpret_cast<uintptr_t>( d ) );
+	e.ch_stride = a.get_num_frames(); e.src_frames = a.get_num_frames();
+	e.channels = a.get_num_channels();
+	return true;
+	}
+
+// `a` from its first frame on, or nothing if a is a null Audio
+bool whole_event( const Audio & a, flanhip_grain_event & e )
+	{
+	if( a.is_null() ) return true;
+	e.n = a.get_num_frames();
+	return point_at( a, e );
+	}
+
+// The sink: the table's length (AudioCombination.cpp:146-150) and plan on the host, then one launch.  Nothing to hear -- no frames, or no event
+// with any -- is the reference's null Audio
+Audio mix_events( const char * who, const EventTable & table, Channel channels, FrameRate sample_rate )
+	{
+	const int64_t count = int64_t( table.events.size() );
+	bool live = false;
+	for( const flanhip_grain_event & e : table.events ) live = live || ( e.n > 0 && e.channels > 0 );
+	int64_t frames = 0;
+	if( !live || channels < 1 || flanhip_grains_plan( table.events.data(), count, &frames, nullptr, nullptr, 0 ) != FLANHIP_OK ) return Audio::create_null();
+	if( frames < 1 || frames > INT_MAX )
+		{
+		std::cerr << "flan: " << who << ": an output of " << frames << " frames" << std::endl;
+		return Audio::create_null();
+		}
+	const int64_t tile = flanhip_grains_tile_frames(), tiles = ( frames + tile - 1 ) / tile;
+	std::vector<int32_t> first( static_cast<size_t>( tiles ) ), last( static_cast<size_t>( tiles ) );
+	if( flanhip_grains_plan( table.events.data(), count, &frames, first.data(), last.data(), tiles ) != FLANHIP_OK ) return Audio::create_null();
+	const DeviceArg gains = table.gains.empty() ? DeviceArg( 0.0f ) : DeviceArg::from_host( table.gains.data(), sizeof( float ) * table.gains.size(), "sampled amplitudes" );
+	AudioBuffer::Format f;
+	f.num_channels = channels; f.num_frames = Frame( frames ); f.sample_rate = sample_rate;
+	return audio_call( who, f, gains.ok, flanhip_grains_workspace_bytes( count, frames ), [&]( float * out, void * ws )
+		{
+		return flanhip_grains_mix_dev( table.events.data(), count, first.data(), last.data(), tiles, gains.ptr(), int64_t( table.gains.size() ), nullptr, 0,
+			channels, frames, sample_rate, out, ws, nullptr );
+		} );
+	}
+
+// a time as a frame by truncation (the reference's Frame( time_to_frame( t ) )); false for what no Frame holds
+bool frame_of( Second t, FrameRate sample_rate, Frame & frame )
+	{
+	const float f = t * sample_rate;
+	if( !( f > -2147483648.0f && f < 2147483648.0f ) ) return false;
+	frame = Frame( f );
+	return true;
+	}
+
+// Audio::mix (AudioCombination.cpp:102-170).  amplitude i is functions[i] where there are functions, else constants[i]; 1 behind the list's end
+Audio mix_core( std::vector<const Audio *> ins_unmatched, std::vector<Second> start_times, const std::vector<const Function<Second, Amplitude> *> * functions,
+	const std::vector<Amplitude> * constants )
+	{
+	if( ins_unmatched.empty() ) return Audio::create_null();                       // :109
+	for( const Audio * a : ins_unmatched ) if( !a ) return Audio::create_null();
+	const size_t num_amplitudes = functions ? functions->size() : constants ? constants->size() : 0;
+	if( functions ) for( const auto * fn : *functions ) if( !fn ) return Audio::create_null();
+	const size_t num_sources = std::max( { ins_unmatched.size(), start_times.size(), num_amplitudes } );      // :111
+
+	// match_sample_rates_or_return_null (:17-35), over the inputs that are not null Audios
+	FrameRate max_sr = 0;
+	bool all_match = true;
+	for( const Audio * a : ins_unmatched ) if( !a->is_null() ) max_sr = std::max( max_sr, a->get_sample_rate() );
+	if( max_sr <= 0 ) return Audio::create_null();                                 // nothing but null Audios
+	for( const Audio * a : ins_unmatched ) if( !a->is_null() && a->get_sample_rate() != max_sr ) all_match = false;
+	std::vector<Audio> resampled;
+	std::vector<const Audio *> ins = ins_unmatched;
+	if( !all_match )
+		{
+		for( const Audio * a : ins_unmatched ) resampled.emplace_back( a->is_null() ? Audio() : a->resample( max_sr ) );
+		for( size_t i = 0; i < resampled.size(); ++i )
+			{
+			if( resampled[i].is_null() && !ins_unmatched[i]->is_null() ) return Audio::create_null();
+			ins[i] = &resampled[i];
+			}
+		}
+	const size_t initial_num_ins = ins.size();                                     // :117-123
+	for( size_t i = ins.size(); i < num_sources; ++i ) ins.push_back( ins[i % initial_num_ins] );
+	start_times.resize( num_sources, 0 );
+
+	EventTable table;
+	table.events.resize( num_sources, plain_event() );
+	Channel channels = 0;
+	const float step = 1.0f / max_sr;                                              // frame_to_time( 1 ) (:138)
+	for( size_t i = 0; i < num_sources; ++i )
+		{
+		flanhip_grain_event & e = table.events[i];
+		Frame start = 0;
+		if( !frame_of( start_times[i], max_sr, start ) )                           // :127-129
+			{
+			std::cerr << "flan: mix: a start time no frame holds" << std::endl;
+			return Audio::create_null();
+			}
+		e.o = start;
+		if( !whole_event( *ins[i], e ) ) return Audio::create_null();
+		channels = std::max( channels, Channel( e.channels ) );                    // :144
+		if( i >= num_amplitudes ) continue;                                        // :135-137: the constant 1
+		if( constants ) { e.gain = ( *constants )[i]; continue; }
+		const Function<Second, Amplitude> & fn = *( *functions )[i];
+		if( fn.is_constant() ) { e.gain = fn.get_constant(); continue; }
+		if( e.n == 0 ) continue;
+		e.gain_offset = int64_t( table.gains.size() );                             // :138: sampled over [start, start + frames) at global time
+		table.gains.resize( table.gains.size() + size_t( e.n ) );
+		float * g = table.gains.data() + e.gain_offset;
+		detail::for_each_index( 0, e.n, fn.get_execution_policy(), [&]( int x ){ g[x] = fn( Second( ( start + x ) * step ) ); } );
+		}
+	return mix_events( "mix", table, channels, max_sr );
+	}
+
+// integrate_event_rate (AudioSynthesis.cpp:310-374): the event frames; both Functions sampled over the frames of `length` at f * ( 1.0f / sample_rate )
+std::vector<int64_t> event_frames( Second length, const Function<Second, float> & events_per_second, const Function<Second, float> & scatter, FrameRate sample_rate )
+	{
+	Frame length_frames = 0;
+	if( !( sample_rate > 0 ) || !frame_of( length, sample_rate, length_frames ) || length_frames < 1 ) return {};      // :317
+	const auto rate = events_per_second.sample( 0, length_frames, 1.0f / sample_rate );       // :319-323
+	const auto scat = scatter.sample( 0, length_frames, 1.0f / sample_rate );
+	static std::atomic<uint64_t> calls( 0 );
+	const uint64_t seed = uint64_t( std::time( nullptr ) ) * 0x100000001B3ull + calls.fetch_add( 1 );      // :342: the clock
+	std::vector<int64_t> frames( static_cast<size_t>( length_frames ) );
+	int64_t count = 0;
+	if( flanhip_grains_events( length_frames, sample_rate, rate.is_constant() ? nullptr : rate.get_vector().data(), rate.is_constant() ? rate.get_constant() : 0.0f,
+			scat.is_constant() ? nullptr : scat.get_vector().data(), scat.is_constant() ? scat.get_constant() : 0.0f, seed, frames.data(), length_frames, &count ) != FLANHIP_OK )
+		{
+		std::cerr << "flan: the event rate was refused: " << flanhip_last_error() << std::endl;
+		return {};
+		}
+	frames.resize( static_cast<size_t>( count ) );
+	return frames;
+	}
+
+std::vector<Second> event_times_of( const std::vector<int64_t> & frames, FrameRate sample_rate )
+	{
+	std::vector<Second> times( frames.size() );
+	for( size_t i = 0; i < frames.size(); ++i ) times[i] = Frame( frames[i] ) / sample_rate;       // :371
+	return times;
+	}
+
+std::vector<const Audio *> pointers_to( const std::vector<Audio> & v )
+	{
+	std::vector<const Audio *> p;
+	for( const Audio & a : v ) p.push_back( &a );
+	return p;
+	}
+
+// WindowFunctions.cpp:10-13; the unqualified cos is the double one
+float hann_window( float x ) { return float( 0.5f * ( 1.0f - std::cos( double( 2.0f * pi * x ) ) ) ); }
+
+// Audio::granulate (AudioSynthesis.cpp:572-609) over curves already sampled for the frames of `length` (a constant, or one value per frame);
+// hann: psola's window, in the kernel on the fused path and behind the mod on the general one (:621-627)
+struct SampledCurve
+	{
+	const std::vector<float> * values; float constant;
+	float at( Frame f ) const { return values ? ( *values )[size_t( f )] : constant; }
+	};
+
+Audio granulate_sampled( const Audio & me, const std::vector<int64_t> & frames, Frame sampled_frames, const SampledCurve & selection, const SampledCurve & grain_length,
+	const SampledCurve & fade, const AudioMod & mod, bool hann )
+	{
+	const FrameRate sr = me.get_sample_rate();
+	const size_t count = frames.size();
+	if( count == 0 ) return Audio::create_null();                                  // mix of no inputs (AudioCombination.cpp:109)
+	const std::vector<Second> times = event_times_of( frames, sr );
+	std::vector<float> start( count ), end( count ), fades( count );
+	EventTable table;
+	table.events.resize( count, plain_event() );
+	for( size_t i = 0; i < count; ++i )
+		{
+		Frame at = 0;                                                              // :590-592: the curves at time_to_frame( t )
+		if( !frame_of( times[i], sr, at ) || at < 0 || at >= sampled_frames ) { start[i] = 0; end[i] = 0; fades[i] = 0; at = 0; }       // (cannot happen: at <= the event's frame)
+		else { start[i] = selection.at( at ); end[i] = start[i] + grain_length.at( at ); fades[i] = fade.at( at ); }      // :593
+		table.events[i].o = at;                                                    // mix's time_to_frame( t ) (AudioCombination.cpp:127-129)
+		}
+	if( flanhip_grains_cut( me.get_num_frames(), sr, int64_t( count ), start.data(), end.data(), fades.data(), fades.data(), table.events.data() ) != FLANHIP_OK )
+		{
+		std::cerr << "flan: granulate: " << flanhip_last_error() << std::endl;
+		return Audio::create_null();
+		}
+	for( flanhip_grain_event & e : table.events ) if( !point_at( me, e ) ) return Audio::create_null();
+	if( mod.is_null() )                                                            // the fused path: every grain cut, faded and windowed in flight
+		{
+		if( hann ) for( flanhip_grain_event & e : table.events ) e.flags = FLANHIP_GRAIN_HANN;
+		return mix_events( "granulate", table, me.get_num_channels(), sr );
+		}
+	// the general path: a grain is one event mixed alone (which is cut_frames with its fades), then the mod's, then one event of the final mix
+	std::vector<Audio> grains;
+	grains.reserve( count );
+	for( size_t i = 0; i < count; ++i )
+		{
+		flanhip_grain_event e = table.events[i];
+		e.o = 0;
+		EventTable one;
+		one.events.push_back( e );
+		Audio grain = e.n > 0 ? mix_events( "granulate", one, me.get_num_channels(), sr ) : Audio();
+		mod( grain, times[i] );                                                    // :604-605
+		if( hann && !grain.is_null() )
+			grain.modify_volume_in_place( Function<Second, float>( [length = grain.get_length()]( Second t ){ return hann_window( t / length ); } ) );   // :626
+		grains.emplace_back( std::move( grain ) );
+		}
+	return mix_core( pointers_to( grains ), times, nullptr, nullptr );             // synthesize_grains' Audio::mix( grains, event_times ) (:397)
+	}
+
+// a Function of time sampled over [0, frames) at f * step as a SampledCurve over `storage`
+SampledCurve sampled_curve( const Function<Second, float> & fn, Frame frames, float step, std::vector<float> & storage )
+	{
+	if( fn.is_constant() ) return SampledCurve{ nullptr, fn.get_constant() };
+	storage.resize( size_t( std::max( frames, 0 ) ) );
+	detail::for_each_index( 0, frames, fn.get_execution_policy(), [&]( int x ){ storage[size_t( x )] = fn( Second( x * step ) ); } );
+	return SampledCurve{ &storage, 0.0f };
+	}
+
+} // namespace
+
+Audio Audio::cut( Second start_time, Second end_time, Second start_fade, Second end_fade ) const
+	{
+	if( is_null() ) return Audio::create_null();                                   // AudioTemporal.cpp:197
+	EventTable table;
+	table.events.push_back( plain_event() );
+	if( flanhip_grains_cut( get_num_frames(), get_sample_rate(), 1, &start_time, &end_time, &start_fade, &end_fade, table.events.data() ) != FLANHIP_OK
+		|| table.events[0].n <= 0 || !point_at( *this, table.events[0] ) ) return Audio::create_null();
+	return mix_events( "cut", table, get_num_channels(), get_sample_rate() );
+	}
+
+Audio Audio::cut_frames( Frame start, Frame end, Frame start_fade, Frame end_fade ) const
+	{
+	if( is_null() ) return Audio::create_null();                                   // :214
+	EventTable table;
+	table.events.push_back( plain_event() );
+	if( flanhip_grains_cut_frames( get_num_frames(), 1, &start, &end, &start_fade, &end_fade, table.events.data() ) != FLANHIP_OK
+		|| table.events[0].n <= 0 || !point_at( *this, table.events[0] ) ) return Audio::create_null();
+	return mix_events( "cut_frames", table, get_num_channels(), get_sample_rate() );
+	}
+
+Audio Audio::mix( std::vector<const Audio *> ins, std::vector<Second> start_times, std::vector<Amplitude> amplitudes )
+	{
+	return mix_core( std::move( ins ), std::move( start_times ), nullptr, &amplitudes );        // AudioCombination.cpp:78-91: constants stay scalars
+	}
+
+Audio Audio::mix( const std::vector<Audio> & ins, std::vector<Second> start_times, std::vector<Amplitude> amplitudes )
+	{
+	return mix( pointers_to( ins ), std::move( start_times ), std::move( amplitudes ) );        // :93-100
+	}
+
+Audio Audio::mix( std::vector<const Audio *> ins, std::vector<Second> start_times, const std::vector<const Function<Second, Amplitude> *> & amplitudes )
+	{
+	return mix_core( std::move( ins ), std::move( start_times ), &amplitudes, nullptr );        // :102-170
+	}
+
+Audio Audio::mix( const std::vector<Audio> & ins, const std::vector<Second> & start_times, const std::vector<Function<Second, Amplitude>> & amplitudes )
+	{
+	std::vector<const Function<Second, Amplitude> *> p;                            // :172-179
+	for( const auto & fn : amplitudes ) p.push_back( &fn );
+	return mix_core( pointers_to( ins ), start_times, &p, nullptr );
+	}
+
+Audio Audio::join( const std::vector<const Audio *> & ins, const std::vector<Second> & offsets )
+	{
+	if( ins.empty() || offsets.size() != ins.size() + 1 ) return Audio::create_null();         // :210
+	for( const Audio * a : ins ) if( !a ) return Audio::create_null();
+	std::vector<Second> start_times = { 0 };                                       // :212-218
+	for( size_t i = 0; i + 1 < ins.size(); ++i )
+		start_times.push_back( start_times.back() + ins[i]->get_length() + offsets[i + 1] );
+	return mix( ins, start_times, std::vector<Amplitude>() );
+	}
+
+Audio Audio::join( const std::vector<const Audio *> & ins, Second offset )
+	{
+	return join( ins, std::vector<Second>( ins.size() + 1, offset ) );             // :223-229
+	}
+
+Audio Audio::join( const std::vector<Audio> & ins, Second offset )
+	{
+	return join( pointers_to( ins ), offset );                                     // :231-237
+	}
+
+Audio Audio::synthesize_grains( Second length, const Function<Second, float> & grains_per_second, const Function<Second, float> & time_scatter,
+	const Function<Second, Audio> & grain_source, FrameRate sample_rate )
+	{
+	if( !( length > 0 ) ) return Audio::create_null();                             // AudioSynthesis.cpp:385
+	const std::vector<Second> times = event_times_of( event_frames( length, grains_per_second, time_scatter, sample_rate ), sample_rate );
+	std::vector<Audio> grains;                                                     // :390-395
+	grains.reserve( times.size() );
+	for( Second t : times ) grains.emplace_back( grain_source( t ) );
+	return mix( grains, times );                                                   // :397
+	}
+
+Audio Audio::texture( Second length, const Function<Second, float> & grains_per_second, const Function<Second, float> & time_scatter, const AudioMod & mod,
+	bool mod_feedback ) const
+	{
+	if( is_null() ) return Audio::create_null();                                   // :431
+	if( !( length > 0 ) ) return Audio::create_null();                             // :412
+	const std::vector<Second> times = event_times_of( event_frames( length, grains_per_second, time_scatter, get_sample_rate() ), get_sample_rate() );
+	if( times.empty() ) return Audio::create_null();
+	if( mod.is_null() )                                                            // synthesize_grains_repeat (:401-421): every event reads *this, gain 1
+		return mix( std::vector<const Audio *>( times.size(), this ), times, std::vector<Amplitude>( times.size(), 1.0f ) );
+	std::vector<Audio> modded;                                                     // :438-472
+	modded.reserve( times.size() );
+	for( size_t i = 0; i < times.size(); ++i )
+		{
+		Audio input = mod_feedback && i > 0 ? modded.back().copy() : copy();
+		mod( input, mod_feedback && i == 0 ? 0 : times[i] );                       // :443: the first of a feedback chain is modded at time 0
+		modded.emplace_back( std::move( input ) );
+		}
+	return mix( modded, times );
+	}
+
+Audio Audio::granulate( Second length, const Function<Second, float> & grains_per_second, const Function<Second, float> & time_scatter,
+	const Function<Second, Second> & time_selection, const Function<Second, Second> & grain_length, const Function<Second, Second> & fade_time,
+	const AudioMod & mod ) const
+	{
+	if( is_null() ) return Audio::create_null();                                   // :582
+	Frame sampled_frames = 0;                                                      // :584-586
+	if( !( length > 0 ) || !frame_of( length, get_sample_rate(), sampled_frames ) ) return Audio::create_null();      // synthesize_grains (:385)
+	std::vector<float> s0, s1, s2;
+	const float step = frame_to_time( 1 );
+	const SampledCurve selection = sampled_curve( time_selection, sampled_frames, step, s0 ), lengths = sampled_curve( grain_length, sampled_frames, step, s1 ),
+		fades = sampled_curve( fade_time, sampled_frames, step, s2 );
+	return granulate_sampled( *this, event_frames( length, grains_per_second, time_scatter, get_sample_rate() ), sampled_frames, selection, lengths, fades, mod, false );
+	}
+
+Audio Audio::psola( Second length, const Function<Second, Second> & time_selection, const AudioMod & mod ) const
+	{
+	if( is_null() ) return Audio::create_null();
+	const FrameRate sr = get_sample_rate();
+	const auto freq = get_frequency_envelope();                                    // :617
+	const float whole = std::ceil( time_to_frame( length ) );                      // :620
+	if( !( length > 0 ) || !( whole < 2147483648.0f ) ) return Audio::create_null();
+	const Frame selection_frames = Frame( whole );
+	std::vector<float> s0;
+	const SampledCurve selection = sampled_curve( time_selection, selection_frames, frame_to_time( 1 ), s0 );
+	// :629-636: granulate's Functions read the sampled selection at time_to_frame( t ); granulate samples them at f * frame_to_time( 1 ) and
+	// integrate_event_rate at f * ( 1.0f / sample rate ), the same float
+	Frame sampled_frames = 0;
+	if( !frame_of( length, sr, sampled_frames ) || sampled_frames < 1 ) return Audio::create_null();
+	const float step = frame_to_time( 1 );
+	std::vector<float> rate( static_cast<size_t>( sampled_frames ) ), picked( rate.size() ), lengths( rate.size() );
+	for( Frame f = 0; f < sampled_frames; ++f )
+		{
+		Frame at = 0;
+		if( !frame_of( Second( f * step ), sr, at ) || at >= selection_frames ) at = selection_frames - 1;      // (at <= f < selection_frames)
+		picked[size_t( f )] = selection.at( at );
+		rate[size_t( f )] = freq( picked[size_t( f )] );
+		lengths[size_t( f )] = 2.0f / rate[size_t( f )];                           // :634: infinite where no pitch is found
+		}
+	std::vector<int64_t> frames( rate.size() );
+	int64_t count = 0;
+	if( flanhip_grains_events( sampled_frames, sr, rate.data(), 0.0f, nullptr, 0.0f, 0, frames.data(), sampled_frames, &count ) != FLANHIP_OK ) return Audio::create_null();
+	frames.resize( static_cast<size_t>( count ) );
+	return granulate_sampled( *this, frames, sampled_frames, SampledCurve{ &picked, 0.0f }, SampledCurve{ &lengths, 0.0f }, SampledCurve{ nullptr, 0.05f }, mod, true );
 	}
 
 } // namespace flan

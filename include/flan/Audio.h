@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "flan/AudioBuffer.h"
+#include "flan/AudioMod.h"
 #include "flan/Function.h"
 #include "flan/defines.h"
 #include "flan/vec2.h"
@@ -273,6 +274,70 @@ public:
 	/** convert_to_mono().get_local_frequencies( 0, 0, -1, 2048, 128 ) as a function of time, linear between the hops and 0 outside them
 	 *  (:388-407).  Where the reference would read an empty vector (a null *this, a signal of 2048 frames or fewer) the function is 0. */
 	Function<Second, Amplitude> get_frequency_envelope() const;
+
+	// ---- cutting, mixing and granular synthesis ----
+	// Everything below ends in one kernel (flanhip_grains_mix_dev): an output sample is the fp32 sum, in the order of the inputs,
+	// of the inputs that cover it, bit for bit what the reference's loop over its inputs computes (Audio/AudioCombination.cpp:155-167); grains are
+	// cut, faded and windowed while they are read and never written anywhere.  Results stay device-resident until read.  Not offered: select,
+	// fade / fade_frames and their in-place forms as public methods, mix_in_place, texture_effect, synthesize_trainlets, synthesize_impulse,
+	// modify_boundaries.
+	/** The frames between two times, with square-root fades at either end (Audio/AudioTemporal.cpp:190-234, Audio/AudioVolume.cpp:102-135): times
+	 *  become frames by truncation; end <= start gives a null Audio, checked before start and end are clamped to [0, frames - 1] -- so the last
+	 *  frame is never part of a cut --; fades are clamped at 0 and, where together they are longer than the cut, both scaled down and floored.  A
+	 *  time no Frame holds (NaN, an infinity) gives a null Audio; so does a null *this. */
+	Audio cut( Second start_time, Second end_time, Second start_fade = 0, Second end_fade = 0 ) const;
+	Audio cut_frames( Frame start, Frame end, Frame start_fade = 0, Frame end_fade = 0 ) const;
+	/** The sum of the inputs, input i from start_times[i] on and times amplitudes[i] (Audio/AudioCombination.cpp:78-179; the overloads of
+	 *  Audio/Audio.h:876-908).  The longest of the three lists sets the number of terms: inputs loop, start times default to 0, amplitudes to 1.
+	 *  Unless all sample rates are the highest one every input is first resample()d to it; the output has the widest channel count and
+	 *  max( start frame + frames ) frames; what starts before time 0 loses its beginning.  A constant amplitude travels as a scalar; a callable one
+	 *  is sampled on the host over the input's own frames at global time, f * frame_to_time( 1 ) for f in [start, start + frames).
+	 *  No inputs give a null Audio.  Where the reference would read through a null pointer -- one among the inputs, or an amplitude -- the result
+	 *  is a null Audio.  A null Audio OBJECT among the inputs adds nothing but counts with its start for the length, as in the reference; its sample
+	 *  rate is not looked at, and if every input is one the result is a null Audio. */
+	static Audio mix( std::vector<const Audio *> ins, std::vector<Second> start_times = {}, std::vector<Amplitude> amplitudes = {} );
+	static Audio mix( const std::vector<Audio> & ins, std::vector<Second> start_times = {}, std::vector<Amplitude> amplitudes = {} );
+	static Audio mix( std::vector<const Audio *> ins, std::vector<Second> start_times, const std::vector<const Function<Second, Amplitude> *> & amplitudes );
+	static Audio mix( const std::vector<Audio> & ins, const std::vector<Second> & start_times, const std::vector<Function<Second, Amplitude>> & amplitudes );
+	template<typename ... Ts, typename = std::enable_if_t<( std::is_same_v<Ts, Audio> && ... )>>
+	static Audio mix( const Ts & ... ins )
+		{
+		std::vector<const Audio *> p_ins;
+		( p_ins.push_back( &ins ), ... );
+		return mix( p_ins );
+		}
+	/** The inputs tip to tail (:205-237): input i + 1 starts where input i ends plus offsets[i + 1]; offsets has one entry more than there are
+	 *  inputs (the first and the last are not read), else the result is a null Audio.  Start-time arithmetic in fp32 over mix. */
+	static Audio join( const std::vector<const Audio *> & ins, const std::vector<Second> & offsets );
+	static Audio join( const std::vector<const Audio *> & ins, Second offset = 0 );
+	static Audio join( const std::vector<Audio> & ins, Second offset = 0 );
+	/** Grains made by the caller's function at the times an event rate decides, mixed in one launch (Audio/AudioSynthesis.cpp:310-398).
+	 *  grains_per_second and time_scatter are sampled once per frame of `length` at f * ( 1.0f / sample_rate ) and clamped at 0; an event falls
+	 *  where the running sum of rate / sample_rate passes an integer, the first at frame 0 (flanhip_grains_events).  time_scatter moves every event
+	 *  by a normal deviate of scatter / rate seconds; the engine is seeded from the clock and a counter, as the reference's is from the clock.
+	 *  grain_source runs on the calling thread in event order, whatever its policy: its device calls share one stream.  length <= 0 gives a
+	 *  null Audio. */
+	static Audio synthesize_grains( Second length, const Function<Second, float> & grains_per_second, const Function<Second, float> & time_scatter,
+		const Function<Second, Audio> & grain_source, FrameRate sample_rate = 48000 );
+	/** *this repeated at the events (:401-473).  Without a mod nothing is copied: every event reads *this.  With one, a copy per event goes through
+	 *  mod( copy, event time ) first; with mod_feedback each copy is made from the event before's result.  The mod runs on the calling thread in
+	 *  event order. */
+	Audio texture( Second length, const Function<Second, float> & grains_per_second, const Function<Second, float> & time_scatter,
+		const AudioMod & mod = AudioMod(), bool mod_feedback = false ) const;
+	/** Granular resynthesis (:572-609): at each event time t a grain cut( selection( t ), selection( t ) + grain_length( t ), fade( t ), fade( t ) )
+	 *  of *this is placed at t.  The three Functions are sampled over the frames of `length` at f * frame_to_time( 1 ) and read at the event's
+	 *  frame.  Without a mod the grains are cut inside the mixing kernel: one launch over *this, nothing materialised.  With one, every grain is
+	 *  cut on the device into an Audio of its own, handed to mod( grain, t ) on the calling thread in event order, and the results are mixed by
+	 *  the same kernel; an identity mod gives the bits of the null mod.  If no grain has a frame the result is a null Audio. */
+	Audio granulate( Second length, const Function<Second, float> & grains_per_second, const Function<Second, float> & time_scatter,
+		const Function<Second, Second> & time_selection, const Function<Second, Second> & grain_length, const Function<Second, Second> & fade_time = 0,
+		const AudioMod & mod = AudioMod() ) const;
+	/** Pitch-synchronous overlap-add (:611-638): granulate at get_frequency_envelope()'s rate, grains two periods long with 0.05 s fades (which the
+	 *  rescale shortens to half a grain each) under a Hann window over the grain's own length, read from time_selection( t ): a time stretch that
+	 *  keeps the pitch.  Where no pitch is found the rate is 0 and the grain length 2.0f / 0: no grain.  Without a mod the window is applied in the
+	 *  mixing kernel; a mod takes granulate's general path and the window follows it (modify_volume_in_place on the grain).  The window is
+	 *  hann( x ) = 0.5f * ( 1.0f - cos( 2.0f * pi * x ) ) with the DOUBLE cos the reference's unqualified call picks (WindowFunctions.cpp:10-13). */
+	Audio psola( Second length, const Function<Second, Second> & time_selection, const AudioMod & mod = AudioMod() ) const;
 
 	// the older camelCase spellings BASELINE.json's north_star uses
 	PV convertToPV( Frame window_size = 2048, Frame hop = 128, Frame dft_size = 4096, flan_CANCEL_ARG ) const;

@@ -109,7 +109,12 @@ struct Function
 	const O & get_constant() const { return std::get<O>( f ); }
 	ExecutionPolicy get_execution_policy() const { return execution_policy; }
 
-	O operator()( I t ) const { return is_constant() ? std::get<O>( f ) : std::get<StdFuncType>( f )( t ); }
+	// (an O that cannot be copied -- Function<Second, Audio>, the grain source of Audio::synthesize_grains -- can only come from a callable)
+	O operator()( I t ) const
+		{
+		if constexpr( std::is_copy_constructible_v<O> ) { if( is_constant() ) return std::get<O>( f ); }
+		return std::get<StdFuncType>( f )( t );
+		}
 
 	// Function.h:155-171: sample on the grid x in [x_start, x_end), y in [y_start, y_end), argument ( x*x_scale, y*y_scale ),
 	// result laid out [x][y].  Only for I constructible from two floats (TF).

@@ -936,6 +936,90 @@ int flanhip_wavelength_continuity(float * w, int64_t count, float sample_rate, i
  * max_length_sigma != -1 and their standard deviation exceeds it.  No non-zero entry: mean and deviation are 0. */
 int flanhip_average_wavelength(const float * locals, int64_t count, float min_active_ratio, float max_length_sigma, float * out);
 
+/* ---- Audio::mix and the granular family over it: cut, join, texture, synthesize_grains, granulate, psola (Audio/AudioCombination.cpp:102-237,
+ * Audio/AudioSynthesis.cpp:310-473, 572-638, Audio/AudioTemporal.cpp:190-234, Audio/AudioVolume.cpp:102-135, WindowFunctions.cpp:10-13)
+ * (flan_amd/csrc/grains.hip) ----------------------------------------------------------------------------------------- */
+/* An EVENT is one term of Audio::mix (AudioCombination.cpp:102-170): n frames of a source from its frame s, added to the output from
+ * frame o on (o may be negative: what falls before frame 0 is not heard, :162), over the source's channels, times a gain.  A grain of
+ * granulate / psola is an event cut in flight: sf and ef are the fades of cut_frames (AudioTemporal.cpp:207-234), FLANHIP_GRAIN_HANN
+ * psola's window (AudioSynthesis.cpp:626).  The reference makes every grain an Audio and adds them one after another (:155-167); here
+ * every output sample out[c][g] is the sum, from +0.0f and IN ASCENDING EVENT INDEX, one fp32 addition per term, of the events with
+ * o <= g < o + n and c < channels -- the order of the reference's loop, whatever the events' start frames; a lone -0.0f comes out
+ * +0.0f, as it does after clear_buffer() (:152).  A term, with i = g - o, every step rounded to fp32:
+ *   v = src[c][s + i]
+ *   i < sf:       v *= sqrtf( float( i ) / sf )                  (AudioVolume.cpp:123-127 with Interpolator::sqrt())
+ *   i >= n - ef:  v *= sqrtf( float( n - 1 - i ) / ef )          (:128-132; sf + ef <= n, so the ramps never share a frame)
+ *   Hann:         v *= hann( ( i * ( 1.0f / sample_rate ) ) / ( n / sample_rate ) ), the grain's own time over its own length
+ *                 (sample_function_over_domain, Audio/Audio.h:37), hann( x ) = float( 0.5 * ( 1.0 - cos( double( 2.0f * pi * x ) ) ) ),
+ *                 pi = acosf( -1.0f ): WindowFunctions.cpp:10-13, whose unqualified cos is the DOUBLE one, as sine2's sin above
+ *   term = v * gain (the scalar, or gains[gain_offset + i]: the amplitude Function sampled over the event, AudioCombination.cpp:138)
+ * Without the Hann flag the result is bit-identical to the reference's loop; with it the device's double cos may differ from libm's in
+ * its last places.  No grain is written anywhere. */
+#define FLANHIP_GRAIN_HANN 1
+typedef struct flanhip_grain_event
+	{
+	uint64_t src;          /* the source's channel 0, frame 0: an offset in floats into `sources` where the call has one, else a device address */
+	int64_t ch_stride;     /* floats between the source's channels */
+	int64_t src_frames;    /* frames of a channel of the source: s + n <= src_frames */
+	int64_t o;             /* the first output frame; may be negative */
+	int64_t gain_offset;   /* >= 0: n per-frame gains from this offset of the gain pool; < 0: the scalar `gain` */
+	int32_t s;             /* the first source frame */
+	int32_t n;             /* frames; 0: an empty event (a null grain), which counts for the output's length alone */
+	int32_t channels;      /* the source's channels; output channels from this on do not hear the event */
+	int32_t sf, ef;        /* fade lengths in frames, sf + ef <= n */
+	int32_t flags;         /* FLANHIP_GRAIN_HANN or 0 */
+	float gain;
+	int32_t reserved;
+	} flanhip_grain_event;
+/* the kernel's geometry: output frames per block, and events staged through LDS per round (what tests size their cases by) */
+int64_t flanhip_grains_tile_frames(void);
+int64_t flanhip_grains_batch_events(void);
+/* integrate_event_rate (AudioSynthesis.cpp:310-374), host arithmetic: the event frames of length_frames frames.  rate / scatter: curves of
+ * length_frames floats (the Functions sampled at f * ( 1.0f / sample_rate )) or, with NULL, the scalar; both clamped at 0 (:320, :323).
+ * The fp32 accumulator starts at 1.0f, grows by rate / sample_rate per frame and drops its floor when it reaches 1 (:328-338): frame 0
+ * always holds an event, and a rate of 0 yields that one alone.  Where scatter and rate are not 0 an event moves to
+ * Frame( frame + sigma * z ), sigma = scatter / rate * sample_rate frames in fp32, z a normal deviate; events that land outside
+ * [0, length_frames) are dropped and the rest sorted (:343-366).  The reference seeds std::default_random_engine from the clock; here
+ * `seed` starts a splitmix64 stream read by Box and Muller's transform in double, so a seed names one result.  With scatter 0 nothing
+ * is drawn and the result is exact.  Event i lies at time float( frame ) / sample_rate (:371).  out_frames: room for `capacity` frames
+ * (length_frames always suffices); capacity 0 gives the count alone.  length_frames <= 0 and sample_rate <= 0 are refused. */
+int flanhip_grains_events(int64_t length_frames, float sample_rate, const float * rate, float rate_scalar, const float * scatter, float scatter_scalar,
+                          uint64_t seed, int64_t * out_frames, int64_t capacity, int64_t * out_count);
+/* Audio::cut (AudioTemporal.cpp:190-205) for a table of grains of a source of num_frames frames, host arithmetic: fills s, n, sf, ef of
+ * events[i] and nothing else.  Times become frames by time_to_frame truncated to Frame; granulate passes ( selection, selection + length,
+ * fade, fade ) (AudioSynthesis.cpp:593).  Then flanhip_grains_cut_frames.  A time that is not finite or whose frame no Frame holds -- an
+ * unvoiced psola grain is 2.0f / 0 long -- makes an EMPTY event, not an integer conversion of infinity. */
+int flanhip_grains_cut(int64_t num_frames, float sample_rate, int64_t count, const float * start_time, const float * end_time,
+                       const float * start_fade, const float * end_fade, flanhip_grain_event * events);
+/* Audio::cut_frames (AudioTemporal.cpp:207-234): end <= start is an empty event, checked before the clamp (:217); start and end clamped to
+ * [0, num_frames - 1] (:218-219), n = end - start; the fades clamped at 0 and, where sf + ef > n, both scaled by float( n ) / ( sf + ef )
+ * and floored (AudioVolume.cpp:111-118). */
+int flanhip_grains_cut_frames(int64_t num_frames, int64_t count, const int32_t * start, const int32_t * end, const int32_t * start_fade,
+                              const int32_t * end_fade, flanhip_grain_event * events);
+/* The output's length and the plan.  *out_frames on entry: 0 asks for the reference's length, max( o + n ) over ALL events from 0
+ * (AudioCombination.cpp:146-150), which is written back; a positive value is the caller's own length (events are clipped to it, :162).
+ * Unless both arrays are NULL, the plan for that length: per tile of flanhip_grains_tile_frames() output frames the first and the last
+ * event index that touch it ( ( 0, -1 ): none ).  num_tiles must be ceil( length / tile ): ask for the length first.  Host arithmetic,
+ * O( events + overlaps ). */
+int flanhip_grains_plan(const flanhip_grain_event * events, int64_t count, int64_t * out_frames, int32_t * tile_first, int32_t * tile_last,
+                        int64_t num_tiles);
+/* bytes of device workspace flanhip_grains_mix_dev asks for: the table and the plan (0 for sizes it refuses) */
+size_t flanhip_grains_workspace_bytes(int64_t count, int64_t out_frames);
+/* The mix (AudioCombination.cpp:151-169), one launch.  events, tile_first, tile_last: HOST tables (they are checked here, then copied into
+ * the workspace); d_gains: the pool of per-frame gains (NULL if no event has one); d_sources: where the events' src offsets start, or
+ * NULL if they are device addresses; d_out: float[num_channels][out_frames], every element written.  Events may come in any order of o.
+ * out_frames need not be the plan's maximum, but the plan must be made for it (num_tiles tiles).  Refused with FLANHIP_ERR_INVALID_ARG
+ * before any device call: null pointers, non-positive sizes, sample_rate <= 0, an event whose source range leaves its buffer (s < 0,
+ * s + n > src_frames, or its channels beyond sources_floats), whose fades exceed it, whose gains leave the pool, and a plan that names
+ * events the table does not hold. */
+int flanhip_grains_mix_dev(const flanhip_grain_event * events, int64_t count, const int32_t * tile_first, const int32_t * tile_last, int64_t num_tiles,
+                           const float * d_gains, int64_t gain_floats, const float * d_sources, int64_t sources_floats, int64_t num_channels,
+                           int64_t out_frames, float sample_rate, float * d_out, void * d_workspace, void * stream);
+/* Host pointers; every src is an offset into `sources`; the plan is made here.  `cancel` is polled before the uploads, before the launch
+ * and while it runs. */
+int flanhip_grains_mix(const flanhip_grain_event * events, int64_t count, const float * gains, int64_t gain_floats, const float * sources,
+                       int64_t sources_floats, int64_t num_channels, int64_t out_frames, float sample_rate, float * out, volatile int * cancel);
+
 /* ---- Audio::resample (Audio/AudioConversions.cpp:14-30, r8brain CDSPResampler with default parameters) --------- */
 /* AudioConversions.cpp:22: out frames = Frame( float(num_frames) * ( dst_rate / src_rate ) ) */
 int64_t flanhip_resample_out_frames(int64_t num_frames, float src_rate, float dst_rate);
