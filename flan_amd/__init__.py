@@ -203,6 +203,19 @@ _SIGS = {
     "flanhip_grains_workspace_bytes": (C.c_size_t, [_i64, _i64]),
     "flanhip_grains_mix_dev": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _f32, _vp, _vp, _vp]),
     "flanhip_grains_mix": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _f32, _vp, _vp]),
+    "flanhip_wavetable_snap": (C.c_int, [_vp, _i64, _i32, _f32, _i32, _vp]),
+    "flanhip_wavetable_starts": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _i64, _vp]),
+    "flanhip_wavetable_table_index": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp]),
+    "flanhip_wavetable_slots": (_i64, [_vp, _i64]),
+    "flanhip_wavetable_resample_workspace_bytes": (C.c_size_t, [_i64, _i64, _vp, _vp, _i32]),
+    "flanhip_wavetable_resample_dev": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "flanhip_wavetable_resample": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "flanhip_wavetable_synth_plan": (_i64, [_i64, _f32, _i32, _i64, _vp, _i64, _i64] + [_vp] * 10),
+    "flanhip_wavetable_synth_workspace_bytes": (C.c_size_t, [_i64, _i64, _f32, _i32, _i64, _vp, _i64]),
+    "flanhip_wavetable_synth_dev": (C.c_int, [_vp, _i64, _i64, _i32, _f32, _i64, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "flanhip_wavetable_synth": (C.c_int, [_vp, _i64, _i64, _i32, _f32, _i64, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp]),
+    "flanhip_wavetable_edit_dev": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "flanhip_wavetable_edit": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp]),
 }
 
 EXPORTS = sorted(_SIGS)
@@ -1456,3 +1469,120 @@ def grains_mix(events, gains, sources, num_channels, out_frames, sample_rate, ca
                                  _ptr(sources), sources.size, num_channels, out_frames, sample_rate, _ptr(out),
                                  None if cancel is None else C.cast(C.byref(cancel), _vp)))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# flan::Wavetable: waveform starts and table index on the host, table construction, synthesis and the in-place edits on the device
+# ---------------------------------------------------------------------------------------------------------------
+
+WT_SNAP_NONE, WT_SNAP_ZERO, WT_SNAP_LEVEL = 0, 1, 2
+WT_PITCH_NONE, WT_PITCH_LOCAL, WT_PITCH_GLOBAL = 0, 1, 2
+WT_NORMALIZE, WT_REMOVE_DC, WT_ADD_FADES, WT_REMOVE_JUMPS = 0, 1, 2, 3
+
+
+def wavetable_snap(row, frame_to_snap, snap_height, search_distance):
+    row = np.ascontiguousarray(row, np.float32)
+    out = _i32(0)
+    check(lib.flanhip_wavetable_snap(_ptr(row), row.size, frame_to_snap, snap_height, search_distance, C.cast(C.byref(out), _vp)))
+    return out.value
+
+
+def wavetable_starts(row, local_wavelengths, global_wavelength, snap_mode, pitch_mode, snap_ratio, fixed_frame):
+    """the walk of get_waveform_starts for one channel: int32 starts"""
+    row = np.ascontiguousarray(row, np.float32)
+    loc = np.ascontiguousarray([] if local_wavelengths is None else local_wavelengths, np.float32)
+    count = _i64(0)
+    args = (_ptr(row), row.size, _ptr(loc), loc.size, global_wavelength, snap_mode, pitch_mode, snap_ratio, fixed_frame, None)
+    check(lib.flanhip_wavetable_starts(*args, None, 0, C.cast(C.byref(count), _vp)))
+    out = np.empty(count.value, np.int32)
+    check(lib.flanhip_wavetable_starts(*args, _ptr(out), out.size, C.cast(C.byref(count), _vp)))
+    assert count.value == out.size
+    return out
+
+
+def wavetable_table_index(starts, num_source_frames, ratio):
+    starts = np.ascontiguousarray(starts, np.int32)
+    r = np.ascontiguousarray(ratio, np.float32)
+    out = np.empty(r.shape, np.float32)
+    check(lib.flanhip_wavetable_table_index(_ptr(starts), starts.size, num_source_frames, _ptr(r), r.size, _ptr(out)))
+    return out
+
+
+def _wt_starts(starts):
+    """a list of per-channel start lists -> ( the int32 lists one after another, int64 counts )"""
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(s, np.int32).reshape(-1) for s in starts]), np.int32)
+    return flat, np.array([len(s) for s in starts], np.int64)
+
+
+def wavetable_slots(starts):
+    _, counts = _wt_starts(starts)
+    return int(lib.flanhip_wavetable_slots(_ptr(counts), counts.size))
+
+
+def wavetable_resample_workspace_bytes(ch, n, starts, wavelength):
+    flat, counts = _wt_starts(starts)
+    return int(lib.flanhip_wavetable_resample_workspace_bytes(ch, n, _ptr(flat), _ptr(counts), wavelength))
+
+
+def wavetable_resample(audio, starts, wavelength, want_rotations=True):
+    """resample_waveforms.  audio float32 [ch][n], starts: one list per channel -> ( float32 [ch][slots * W], int32 [ch][slots] )"""
+    audio = np.ascontiguousarray(audio, np.float32)
+    ch, n = audio.shape
+    flat, counts = _wt_starts(starts)
+    slots = int(counts.max())
+    table = np.full((ch, slots * wavelength), np.nan, np.float32)
+    rot = np.full((ch, slots), -1, np.int32)
+    check(lib.flanhip_wavetable_resample(_ptr(audio), ch, n, _ptr(flat), _ptr(counts), wavelength, _ptr(table), _ptr(rot) if want_rotations else None, None))
+    return table, rot
+
+
+def wavetable_resample_dev(d_audio, ch, n, starts, wavelength, d_table, d_rot, d_ws, stream=None):
+    flat, counts = _wt_starts(starts)
+    check(lib.flanhip_wavetable_resample_dev(_dp(d_audio), ch, n, _ptr(flat), _ptr(counts), wavelength, _dp(d_table), _dp(d_rot), _dp(d_ws), _vp(stream or 0)))
+
+
+def wavetable_synth_plan(out_frames, sample_rate, wavelength, granularity_frames, freq):
+    """The resampler's block loop on the host: a dict of per-block arrays (offset, fracpos, ratio, filtpos, oversize, ideal, first_out, num_out,
+    wanted, in_start)"""
+    f = np.ascontiguousarray(freq, np.float32).reshape(-1)
+    fields = _PLAN_FIELDS + [("num_out", np.int32), ("wanted", np.int32), ("in_start", np.int64)]
+    return _block_plan(fields, lambda capacity, pointers, total: lib.flanhip_wavetable_synth_plan(
+        out_frames, sample_rate, wavelength, granularity_frames, _ptr(f), f.size, capacity, *pointers), "unused")
+
+
+def wavetable_synth_workspace_bytes(ch, out_frames, sample_rate, wavelength, granularity_frames, freq):
+    f = np.ascontiguousarray(freq, np.float32).reshape(-1)
+    return int(lib.flanhip_wavetable_synth_workspace_bytes(ch, out_frames, sample_rate, wavelength, granularity_frames, _ptr(f), f.size))
+
+
+def wavetable_synth(table, wavelength, sample_rate, out_frames, granularity_frames, freq, index, smooth=True):
+    """Wavetable::synthesize after its Functions have been sampled.  table float32 [ch][slots * W], index float32 [ch][blocks] ->
+    float32 [ch][out_frames]"""
+    table = np.ascontiguousarray(table, np.float32)
+    f = np.ascontiguousarray(freq, np.float32).reshape(-1)
+    index = np.ascontiguousarray(index, np.float32)
+    ch = table.shape[0]
+    slots = table.shape[1] // wavelength
+    out = np.full((ch, out_frames), np.nan, np.float32)
+    check(lib.flanhip_wavetable_synth(_ptr(table), ch, slots, wavelength, sample_rate, out_frames, granularity_frames, _ptr(f), f.size,
+                                      _ptr(index), index.shape[-1] if index.ndim > 1 else index.size // ch, int(smooth), _ptr(out), None))
+    return out
+
+
+def wavetable_synth_dev(d_table, ch, slots, wavelength, sample_rate, out_frames, granularity_frames, freq, index, smooth, d_out, d_ws, stream=None):
+    f = np.ascontiguousarray(freq, np.float32).reshape(-1)
+    index = np.ascontiguousarray(index, np.float32)
+    check(lib.flanhip_wavetable_synth_dev(_dp(d_table), ch, slots, wavelength, sample_rate, out_frames, granularity_frames, _ptr(f), f.size,
+                                          _ptr(index), index.size // ch, int(smooth), _dp(d_out), _dp(d_ws), _vp(stream or 0)))
+
+
+def wavetable_edit(table, wavelength, mode, fade_frames=0):
+    """the in-place edits on a copy: float32 [ch][slots * W] -> the edited table"""
+    out = np.array(table, np.float32, order="C")
+    ch = out.shape[0]
+    check(lib.flanhip_wavetable_edit(_ptr(out), ch, out.shape[1] // wavelength, wavelength, mode, fade_frames, None))
+    return out
+
+
+def wavetable_edit_dev(d_table, ch, slots, wavelength, mode, fade_frames=0, stream=None):
+    check(lib.flanhip_wavetable_edit_dev(_dp(d_table), ch, slots, wavelength, mode, fade_frames, _vp(stream or 0)))

@@ -8,3 +8,4 @@
 #include "flan/Audio.h"
 #include "flan/PV.h"
 #include "flan/SPV.h"
+#include "flan/Wavetable.h"

@@ -1068,6 +1068,94 @@ int flanhip_comm_destroy(void * comm);
  * comm may also be an ncclComm_t created elsewhere with the same RCCL. */
 int flanhip_allgather_audio(void * comm, float * d_all, int64_t count_per_rank, int rank, void * stream);
 
+/* ---- flan::Wavetable (Wavetable.cpp; WDL/resample.cpp) (flan_amd/csrc/wavetable.hip) --------------------------------- */
+/* A wavetable is float[ch][slots * W]: `slots` waveforms of W frames per channel.  slots = the largest number of waveform starts of any
+ * channel (:77-79); a channel with k starts fills k - 1 slots and the rest stay 0, as in the reference, whose synthesize reads them. */
+#define FLANHIP_WAVETABLE_SNAP_NONE 0
+#define FLANHIP_WAVETABLE_SNAP_ZERO 1
+#define FLANHIP_WAVETABLE_SNAP_LEVEL 2
+#define FLANHIP_WAVETABLE_PITCH_NONE 0
+#define FLANHIP_WAVETABLE_PITCH_LOCAL 1
+#define FLANHIP_WAVETABLE_PITCH_GLOBAL 2
+#define FLANHIP_WAVETABLE_NORMALIZE 0
+#define FLANHIP_WAVETABLE_REMOVE_DC 1
+#define FLANHIP_WAVETABLE_ADD_FADES 2
+#define FLANHIP_WAVETABLE_REMOVE_JUMPS 3
+/* snap_frame_to_sample (:19-60) on one channel row, host-only, restated literally: the two-sided search with its asymmetric limits
+ * ( left >= max( frame - distance, 0 ), right < min( frame + distance, n - 1 ) ), left + 1 on a left hit, and the fallback to the frame
+ * whose | data - height | * ( 1 + | f - frame | / distance ) is smallest.  A distance of 0 (or below) returns frame_to_snap, as the
+ * reference's NaN comparisons do.  frame_to_snap outside [0, num_frames) is FLANHIP_ERR_INVALID_ARG. */
+int flanhip_wavetable_snap(const float * row, int64_t num_frames, int32_t frame_to_snap, float snap_height, int32_t search_distance, int32_t * out);
+/* get_waveform_starts' walk for ONE channel (:181-214), host-only.  row: the UNFILTERED source row (what the snapping reads);
+ * local_wavelengths: get_local_wavelengths( c, 0, -1, W, 128, 1, 32 ) of the low-passed copy (read in Local mode only, truncated to a
+ * Frame per entry, :193); global_wavelength: get_average_wavelength truncated to a Frame (-1 stays -1; 0 when the pitch mode is None,
+ * :158); pitch_mode: the mode in force for this channel (the caller carries Global -> None over to later channels, :163-164);
+ * max_snap = Frame( snap_ratio * expected ).  The checks of :145-146 (fixed_frame < 1, snap_ratio outside ( 0, .95 )) are
+ * FLANHIP_ERR_INVALID_ARG here; the C++ constructor makes a null Wavetable of them.  out: room for `capacity` starts (capacity 0: the count
+ * alone); *out_count: how many the walk made.  Deviation: an expected wavelength below 1 (a global wavelength of 0) or a walk that makes
+ * more than 2 num_frames starts never ends in the reference; FLANHIP_ERR_UNSUPPORTED here. */
+int flanhip_wavetable_starts(const float * row, int64_t num_frames, const float * local_wavelengths, int64_t num_locals, int32_t global_wavelength,
+                             int snap_mode, int pitch_mode, float snap_ratio, int32_t fixed_frame, volatile int * cancel, int32_t * out,
+                             int64_t capacity, int64_t * out_count);
+/* ratio_to_table_index (:463-488) for one channel's starts, host-only, fp32 as written: source_frame = Frame( r * num_source_frames ),
+ * the upper_bound, the clamps.  (A product no Frame holds saturates; NaN is 0.) */
+int flanhip_wavetable_table_index(const int32_t * starts, int64_t count, int32_t num_source_frames, const float * ratio, int64_t num, float * out);
+/* the slots of a table: max counts[c] (0 for null / empty arguments) */
+int64_t flanhip_wavetable_slots(const int64_t * counts, int64_t num_channels);
+/* resample_waveforms (:67-132).  starts: the channels' start lists one after another (HOST memory in every form), counts[c] of them for
+ * channel c.  Waveform w of channel c is the n = starts[c][w+1] - starts[c][w] source frames from starts[c][w]; its slot receives
+ *   y = c2r_W( zero-padded or truncated r2c_n( x ) )    both transforms unnormalised, c2r ignoring the imaginary parts of bins 0 and W/2
+ *   zero_crossing_frame: offsets 1 ... Frame( W * 0.1f ), y[W - offset] before y[offset], the first whose ( y > 0 ) differs from y[0]'s; else 0
+ *   table[c][w W + f] = y[( zero_crossing_frame + f ) % W] / sqrtf( float( n * n ) )
+ * The forward transform is min( n/2, W/2 ) + 1 direct sums (n may be odd): fp32 products chained 32 at a time, the chunks added in fp64,
+ * with twiddles rounded from fp64; the inverse is the project's fp32 FFT.  Not bit-identical to FFTW; DESIGN.md 4.23 gives the error.
+ * rotations (nullable): int32[ch][slots], every waveform's zero_crossing_frame (0 for empty slots).  Every element of table is written.
+ * W must be a power of two in 64 ... 8192 and n <= 16384 (the samples stay in LDS), else FLANHIP_ERR_UNSUPPORTED; a waveform that
+ * leaves [0, num_frames) is FLANHIP_ERR_INVALID_ARG.  Deviations: where n/2 + 1 > W/2 + 1 the reference copies past the end of its
+ * spectrum (:100), here W/2 + 1 bins are copied; n <= 0, for which the reference plans a transform of size 0, leaves the slot 0. */
+size_t flanhip_wavetable_resample_workspace_bytes(int64_t num_channels, int64_t num_frames, const int32_t * starts, const int64_t * counts, int32_t wavelength);
+int flanhip_wavetable_resample_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, const int32_t * starts, const int64_t * counts,
+                                   int32_t wavelength, float * d_table, int32_t * d_rotations, void * d_workspace, void * stream);
+int flanhip_wavetable_resample(const float * audio, int64_t num_channels, int64_t num_frames, const int32_t * starts, const int64_t * counts,
+                               int32_t wavelength, float * table, int32_t * rotations, volatile int * cancel);
+/* Wavetable::synthesize's resampler state (:293-330 over ResamplePrepare :1218-1265 and ResampleOut :1313-1343, :1558-1566 of
+ * WDL/resample.cpp, SetMode( true, 1, true ): the 64-tap sinc, not feeding), host-only, in fp64 with the reference's own chain of
+ * srcpos += ratio.  Per block: rate_in = max( freq, 1 ), rate_out = max( sample_rate / W, 1 ) (the argument order of :307),
+ * wanted = int( ratio g ) + 4 + 64 - S after the prelude of 31 zeros of the first call.  ResampleOut is asked for ALL remaining frames, so
+ * a block delivers until its input ends (ipos >= filtlen - 1, :1343) -- about g + 3 / ratio frames, not g -- and the next block starts
+ * there: first_out[b + 1] = first_out[b] + num_out[b], and the loop ends exactly at out_frames.  freq: the frequency Function sampled at
+ * every output frame (freq[min( frame, freq_count - 1 )]; one entry for a constant); a block reads the entry of its first frame (:300).
+ * in_start[b]: input samples appended before block b, so that its phase_frame (:329) is in_start[b] % W.  Returns the number of blocks
+ * (the arrays, each nullable, are filled up to `capacity`) or a negative error: g < 1 (the reference would not end) and a frequency that
+ * is not finite are FLANHIP_ERR_INVALID_ARG; a ratio above 34 after the first block, where the reference's buffer drops below its
+ * prelude and it reads samples it no longer holds, is FLANHIP_ERR_UNSUPPORTED. */
+int64_t flanhip_wavetable_synth_plan(int64_t out_frames, float sample_rate, int32_t wavelength, int64_t granularity_frames, const float * freq,
+                                     int64_t freq_count, int64_t capacity, int64_t * offsets, double * fracpos, double * ratio, double * filtpos,
+                                     int32_t * oversize, int32_t * ideal, int64_t * first_out, int32_t * num_out, int32_t * wanted, int64_t * in_start);
+/* Wavetable::synthesize (:266-334).  table: float[ch][slots W]; freq: as above (HOST); index: float[ch][num_blocks] (HOST), the table
+ * index of every ( channel, block ) -- ratio_to_table_index of the ratio Function at the block's first frame, within [0, slots - 1] --;
+ * out: float[ch][out_frames], every element written.  Input sample t, appended by the block q with in_start[q] <= t < in_start[q] + wanted[q], is
+ *   ( 1.0f - rem ) * table[c][t % W + W left] + rem * table[c][t % W + W right]     left = floor( index ), right = ceil( index ), rem = index - left
+ * every operation rounded (:316-318), or the left term alone without `smooth` (:322-323); the output samples are the resampler's tap sums
+ * (flanhip_audio_repitch's, wdl_sinc.h) at the positions of the reference's own chain of srcpos += ratio, which one lane per block walks
+ * before the sums: what is left to differ from the reference is the rounding of a table coefficient.  num_blocks must be the plan's. */
+size_t flanhip_wavetable_synth_workspace_bytes(int64_t num_channels, int64_t out_frames, float sample_rate, int32_t wavelength,
+                                               int64_t granularity_frames, const float * freq, int64_t freq_count);
+int flanhip_wavetable_synth_dev(const float * d_table, int64_t num_channels, int64_t slots, int32_t wavelength, float sample_rate, int64_t out_frames,
+                                int64_t granularity_frames, const float * freq, int64_t freq_count, const float * index, int64_t num_blocks, int smooth,
+                                float * d_out, void * d_workspace, void * stream);
+int flanhip_wavetable_synth(const float * table, int64_t num_channels, int64_t slots, int32_t wavelength, float sample_rate, int64_t out_frames,
+                            int64_t granularity_frames, const float * freq, int64_t freq_count, const float * index, int64_t num_blocks, int smooth,
+                            float * out, volatile int * cancel);
+/* normalize_in_place (:429-451: the slot's exact max |s|, untouched below 0.001, else s / max), remove_dc_in_place (:414-427: s - sum / W,
+ * the fp32 sum in a fixed tree order, not the reference's left-to-right one), add_fades_in_place (:364-384) and remove_jumps_in_place
+ * (:386-412): fade = sinf( pi / 2.0f * ( frame + 1 ) / fade_frames ) for frame < fade_frames - 1 on wf[frame] and wf[W - 1 - frame], in
+ * the order of the frames where the two edges overlap.  In place, every slot of every channel once.  Deviations: the reference's fade
+ * loops nest a second channel loop in a parallel one and edit a slot once per channel from racing threads; frames past the waveform
+ * (fade_frames - 1 > W), which the reference writes out of bounds, are left out. */
+int flanhip_wavetable_edit_dev(float * d_table, int64_t num_channels, int64_t slots, int32_t wavelength, int mode, int32_t fade_frames, void * stream);
+int flanhip_wavetable_edit(float * table, int64_t num_channels, int64_t slots, int32_t wavelength, int mode, int32_t fade_frames, volatile int * cancel);
+
 /* ---- synthetic input + comparison utilities (bench / tests; defined by this project) -------------- */
 int flanhip_noise_dev(float * d_out, int64_t num_channels, int64_t num_audio_frames, uint32_t seed, void * stream);
 /* a plain streaming copy, 16 bytes per lane: the measured-copy yardstick bench.py quotes beside the 8 TB/s spec (count: floats, a multiple of 4) */
