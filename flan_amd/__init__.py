@@ -216,6 +216,20 @@ _SIGS = {
     "flanhip_wavetable_synth": (C.c_int, [_vp, _i64, _i64, _i32, _f32, _i64, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp]),
     "flanhip_wavetable_edit_dev": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "flanhip_wavetable_edit": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "flanhip_spectrum_bins": (_i64, [_i32, _i32, _vp, _vp, _i64]),
+    "flanhip_spectrum_num_harmonics": (_i32, [_i32]),
+    "flanhip_spectrum_phases": (C.c_int, [C.c_uint32, _vp, _i64, _vp]),
+    "flanhip_spectrum_jump": (_i32, [_i64, _i64, _i32]),
+    "flanhip_spectrum_table_workspace_bytes": (C.c_size_t, [_i32]),
+    "flanhip_spectrum_table_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "flanhip_spectrum_table": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
+    "flanhip_spectrum_synth_plan": (_i64, [_i64, C.c_double, _i64, _vp, _i64, _i64] + [_vp] * 10),
+    "flanhip_spectrum_synth_workspace_bytes": (C.c_size_t, [_i32, C.c_double, _i64, _i64, _i64, _vp, _i64]),
+    "flanhip_spectrum_synth_dev": (C.c_int, [_vp, _i32, C.c_double, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "flanhip_spectrum_synth": (C.c_int, [_vp, _i32, C.c_double, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "flanhip_audio_synthesize_spectrum_workspace_bytes": (C.c_size_t, [_i32, _i32, _i64, _i64, _i64, _vp, _i64]),
+    "flanhip_audio_synthesize_spectrum_dev": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "flanhip_audio_synthesize_spectrum": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
 }
 
 EXPORTS = sorted(_SIGS)
@@ -1586,3 +1600,108 @@ def wavetable_edit(table, wavelength, mode, fade_frames=0):
 
 def wavetable_edit_dev(d_table, ch, slots, wavelength, mode, fade_frames=0, stream=None):
     check(lib.flanhip_wavetable_edit_dev(_dp(d_table), ch, slots, wavelength, mode, fade_frames, _vp(stream or 0)))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Audio::synthesize_spectrum: bins, phases and channel jumps on the host; the table (one large inverse real FFT), the resampler loop over
+# it and the whole call on the device
+# ---------------------------------------------------------------------------------------------------------------
+
+def spectrum_bins(spectrum_size_power, fundamental_power):
+    """( int32 harmonic[B], float32 freq[B] ): the per-bin harmonic number and bin_to_frequency, B = 2^(p-1) + 1"""
+    bins = int(lib.flanhip_spectrum_bins(spectrum_size_power, fundamental_power, None, None, 0))
+    harmonic, freq = np.empty(bins, np.int32), np.empty(bins, np.float32)
+    assert lib.flanhip_spectrum_bins(spectrum_size_power, fundamental_power, _ptr(harmonic), _ptr(freq), bins) == bins
+    return harmonic, freq
+
+
+def spectrum_num_harmonics(fundamental_power):
+    return int(lib.flanhip_spectrum_num_harmonics(fundamental_power))
+
+
+def spectrum_phases(seed, harmonic):
+    """one mt19937( seed ) draw in [0, 2 pi) per bin with a harmonic, in ascending bin order; 0 elsewhere"""
+    harmonic = np.ascontiguousarray(harmonic, np.int32)
+    theta = np.empty(harmonic.size, np.float32)
+    check(lib.flanhip_spectrum_phases(seed, _ptr(harmonic), harmonic.size, _ptr(theta)))
+    return theta
+
+
+def spectrum_jump(channel, num_channels, spectrum_size_power):
+    return int(lib.flanhip_spectrum_jump(channel, num_channels, spectrum_size_power))
+
+
+def spectrum_table_workspace_bytes(spectrum_size_power):
+    return int(lib.flanhip_spectrum_table_workspace_bytes(spectrum_size_power))
+
+
+def spectrum_table(mag, theta, spectrum_size_power):
+    """float32 mag[B], theta[B] -> float32 table[2^p]: the unnormalised c2r of polar( mag, theta )"""
+    mag, theta = np.ascontiguousarray(mag, np.float32), np.ascontiguousarray(theta, np.float32)
+    bins = (1 << max(spectrum_size_power - 1, 0)) + 1
+    if mag.size != bins or theta.size != bins:
+        raise ValueError("mag and theta must hold 2^(p-1) + 1 bins")
+    table = np.full(1 << spectrum_size_power, np.nan, np.float32)
+    check(lib.flanhip_spectrum_table(_ptr(mag), _ptr(theta), spectrum_size_power, _ptr(table), None))
+    return table
+
+
+def spectrum_table_dev(d_mag, d_theta, spectrum_size_power, d_table, d_ws, stream=None):
+    check(lib.flanhip_spectrum_table_dev(_dp(d_mag), _dp(d_theta), spectrum_size_power, _dp(d_table), _dp(d_ws), _vp(stream or 0)))
+
+
+def spectrum_synth_plan(out_frames, rate_out, granularity_frames, freq):
+    """The resampler's block loop on the host, as wavetable_synth_plan gives it"""
+    f = np.ascontiguousarray(freq, np.float32).reshape(-1)
+    fields = _PLAN_FIELDS + [("num_out", np.int32), ("wanted", np.int32), ("in_start", np.int64)]
+    return _block_plan(fields, lambda capacity, pointers, total: lib.flanhip_spectrum_synth_plan(
+        out_frames, rate_out, granularity_frames, _ptr(f), f.size, capacity, *pointers), "unused")
+
+
+def spectrum_synth_workspace_bytes(table_size_power, rate_out, ch, out_frames, granularity_frames, freq):
+    f = np.ascontiguousarray(freq, np.float32).reshape(-1)
+    return int(lib.flanhip_spectrum_synth_workspace_bytes(table_size_power, rate_out, ch, out_frames, granularity_frames, _ptr(f), f.size))
+
+
+def spectrum_synth(table, rate_out, num_channels, out_frames, granularity_frames, freq):
+    """the loop of Audio::synthesize_spectrum over one table row of 2^p frames -> float32 [num_channels][out_frames]"""
+    table = np.ascontiguousarray(table, np.float32).reshape(-1)
+    power = int(table.size).bit_length() - 1
+    if table.size != 1 << power:
+        raise ValueError("the table must hold a power of two of frames")
+    f = np.ascontiguousarray(freq, np.float32).reshape(-1)
+    out = np.full((max(num_channels, 0), max(out_frames, 0)), np.nan, np.float32)
+    check(lib.flanhip_spectrum_synth(_ptr(table), power, rate_out, num_channels, out_frames, granularity_frames, _ptr(f), f.size, _ptr(out), None))
+    return out
+
+
+def spectrum_synth_dev(d_table, table_size_power, rate_out, ch, out_frames, granularity_frames, freq, d_out, d_ws, stream=None):
+    f = np.ascontiguousarray(freq, np.float32).reshape(-1)
+    check(lib.flanhip_spectrum_synth_dev(_dp(d_table), table_size_power, rate_out, ch, out_frames, granularity_frames, _ptr(f), f.size, _dp(d_out),
+                                         _dp(d_ws), _vp(stream or 0)))
+
+
+def audio_synthesize_spectrum_workspace_bytes(spectrum_size_power, fundamental_power, ch, out_frames, granularity_frames, freq):
+    f = np.ascontiguousarray(freq, np.float32).reshape(-1)
+    return int(lib.flanhip_audio_synthesize_spectrum_workspace_bytes(spectrum_size_power, fundamental_power, ch, out_frames, granularity_frames,
+                                                                     _ptr(f), f.size))
+
+
+def audio_synthesize_spectrum(mag, theta, spectrum_size_power, fundamental_power, num_channels, out_frames, granularity_frames, freq):
+    """Audio::synthesize_spectrum after its Functions have been sampled: table, loop, set_volume( 1 ) -> float32 [num_channels][out_frames]"""
+    mag, theta = np.ascontiguousarray(mag, np.float32), np.ascontiguousarray(theta, np.float32)
+    bins = (1 << max(spectrum_size_power - 1, 0)) + 1
+    if mag.size != bins or theta.size != bins:
+        raise ValueError("mag and theta must hold 2^(p-1) + 1 bins")
+    f = np.ascontiguousarray(freq, np.float32).reshape(-1)
+    out = np.full((max(num_channels, 0), max(out_frames, 0)), np.nan, np.float32)
+    check(lib.flanhip_audio_synthesize_spectrum(_ptr(mag), _ptr(theta), spectrum_size_power, fundamental_power, num_channels, out_frames,
+                                                granularity_frames, _ptr(f), f.size, _ptr(out), None))
+    return out
+
+
+def audio_synthesize_spectrum_dev(d_mag, d_theta, spectrum_size_power, fundamental_power, ch, out_frames, granularity_frames, freq, d_out, d_ws,
+                                  stream=None):
+    f = np.ascontiguousarray(freq, np.float32).reshape(-1)
+    check(lib.flanhip_audio_synthesize_spectrum_dev(_dp(d_mag), _dp(d_theta), spectrum_size_power, fundamental_power, ch, out_frames,
+                                                    granularity_frames, _ptr(f), f.size, _dp(d_out), _dp(d_ws), _vp(stream or 0)))

@@ -6,7 +6,8 @@
 //                   search by one wavefront, the rotated and scaled store
 //   k_wt_synth      synthesize (:266-334): one workgroup per ( run of output frames sharing a coefficient table, channel group ).  The
 //                   resampler's input is no buffer: stream sample s >= 31 is sample t = s - 31 of a periodic read of the table, blended
-//                   between two neighbouring waveforms with the weights of the block that appended it
+//                   between two neighbouring waveforms with the weights of the block that appended it.  With a row stride of 0 and a phase
+//                   offset per channel it is also the loop of Audio::synthesize_spectrum (flanhip_spectrum_synth; spectrum.hip makes its table)
 //   k_wt_edit       normalize / remove_dc / add_fades / remove_jumps (:364-451): one workgroup per ( channel, slot )
 // The waveform starts (:19-65, :134-218), the table index (:463-488) and the resampler's state (the plan) are host arithmetic.
 // Every sum runs in a fixed order and nothing is atomic, so two runs agree bit for bit.
@@ -331,9 +332,10 @@ int wt_synth_check( int64_t out_frames, float sr, int32_t W, int64_t g, const fl
 // The loop of :293-330 with the state of ResamplePrepare (:1218-1265) and ResampleOut (:1313-1343, :1558-1566) in fp64, the reference's own
 // chain of srcpos += ratio.  ResampleOut is asked for all the frames that remain, so a block ends where its input does
 // (ipos >= filtlen - 1, :1343), not after g frames: block b + 1 begins where block b stopped.
-int wt_synth_plan( int64_t out_frames, float sr, int32_t W, int64_t g, const float * freq, int64_t freq_count, WtPlan * plan )
+// rate_out: SetRates' second argument (:307), from the caller: max( sr / W, 1 ) for a wavetable (:299), max( fundamental, 1 ) for
+// Audio::synthesize_spectrum (AudioSynthesis.cpp:247)
+int wt_synth_plan( int64_t out_frames, double rate_out, int64_t g, const float * freq, int64_t freq_count, WtPlan * plan )
 	{
-	const double rate_out = std::max( double( sr ) / double( W ), 1.0 );         // :299, SetRates' second argument (:307)
 	double fracpos = 0.0;
 	int64_t S = 0, offset = 0, out = 0, in_total = 0;
 	bool first = true;
@@ -378,6 +380,8 @@ int wt_synth_plan( int64_t out_frames, float sr, int32_t W, int64_t g, const flo
 	plan->total_in = in_total;
 	return FLANHIP_OK;                                                           // out == out_frames: every output frame belongs to a block
 	}
+
+inline double wt_rate_out( float sr, int32_t W ) { return std::max( double( sr ) / double( W ), 1.0 ); }     // :299
 
 // the block that appended input sample t: the last q with in_start[q] <= t
 int64_t wt_owner( const std::vector<WtBlock> & blocks, int64_t t )
@@ -463,11 +467,11 @@ WtSynthLayout wt_synth_layout( int64_t ch, int64_t num_blocks, int64_t num_runs 
 	return l;
 	}
 
-// stream sample s of channel row `tab` (float[slots W]): 31 zeros, then input sample t = s - 31, appended by the last block q of
+// stream sample s of channel row `tab` (float[slots W]): 31 zeros, then input sample t = s - 31 (read at phase ( t + jump ) % W), appended by the last block q of
 // [q_lo, q_hi] with in_start[q] <= t: the blend of :316-318 (SMOOTH) or the left waveform alone (:322-323), every operation rounded
 template<bool SMOOTH>
 __device__ __forceinline__ float wt_stream( const float * __restrict__ tab, int W, const WtBlock * __restrict__ blocks, const float * __restrict__ index,
-	int64_t q_lo, int64_t q_hi, int64_t total_in, int64_t s )
+	int64_t q_lo, int64_t q_hi, int64_t total_in, int64_t s, int64_t jump )
 	{
 	const int64_t t = s - Wt::PRELUDE;
 	if( t < 0 || t >= total_in ) return 0.0f;
@@ -479,7 +483,7 @@ __device__ __forceinline__ float wt_stream( const float * __restrict__ tab, int 
 		}
 	const float idx = index[lo];
 	const float fl = floorf( idx );
-	const int phase = int( t % W );
+	const int phase = int( ( t + jump ) % W );
 	const float left = tab[phase + W * int( fl )];
 	if( !SMOOTH ) return left;
 	const float rem = __fsub_rn( idx, fl );
@@ -487,9 +491,10 @@ __device__ __forceinline__ float wt_stream( const float * __restrict__ tab, int 
 	return __fadd_rn( __fmul_rn( __fsub_rn( 1.0f, rem ), left ), __fmul_rn( rem, right ) );
 	}
 
-// grid: runs x channel groups of `cpw` channels.  table float[ch][slots W], index float[ch][num_blocks], out float[ch][out_frames].
+// grid: runs x channel groups of `cpw` channels.  table: channel c's row of slots W floats starts at c row_stride (slots W; 0: every channel reads
+// row 0), jump int32[ch] or null: the channel's phase offset, index float[ch][num_blocks], out float[ch][out_frames].
 template<bool SMOOTH>
-__global__ __launch_bounds__( WT_THREADS ) void k_wt_synth( const float * __restrict__ table, int64_t ch, int64_t slots, int W, int64_t out_frames,
+__global__ __launch_bounds__( WT_THREADS ) void k_wt_synth( const float * __restrict__ table, int64_t ch, int64_t row_stride, const int32_t * __restrict__ jump, int W, int64_t out_frames,
 	const WtBlock * __restrict__ blocks, int64_t num_blocks, int64_t total_in, const WtRun * __restrict__ runs, const float * __restrict__ index,
 	const double * __restrict__ win, int64_t groups, int cpw, float * __restrict__ out )
 	{
@@ -518,11 +523,12 @@ __global__ __launch_bounds__( WT_THREADS ) void k_wt_synth( const float * __rest
 	const int64_t c1 = c0 + cpw < ch ? c0 + cpw : ch;
 	for( int64_t c = c0; c < c1; ++c )
 		{
-		const float * tab = table + c * slots * W;
+		const float * tab = table + c * row_stride;
+		const int64_t jmp = jump ? jump[c] : 0;
 		const float * idx = index + c * num_blocks;
 		__syncthreads();                                                         // the table is whole; the last channel's reads of s_in are done
 		for( int i = lane; i < run.win_len; i += WT_THREADS )
-			s_in[i] = wt_stream<SMOOTH>( tab, W, blocks, idx, run.q_first, run.q_first + run.q_count - 1, total_in, run.win_start + i );
+			s_in[i] = wt_stream<SMOOTH>( tab, W, blocks, idx, run.q_first, run.q_first + run.q_count - 1, total_in, run.win_start + i, jmp );
 		__syncthreads();
 		for( int t = lane; t < run.num_out; t += WT_THREADS )
 			{
@@ -552,8 +558,8 @@ int wt_synth_args( const void * table, int64_t ch, int64_t slots, int32_t W, con
 	return FLANHIP_OK;
 	}
 
-int launch_wt_synth( const float * d_table, int64_t ch, int64_t slots, int32_t W, int64_t out_frames, const WtPlan & plan, const std::vector<WtRun> & runs,
-	const float * index, int smooth, float * d_out, void * d_ws, hipStream_t s )
+int launch_wt_synth( const float * d_table, int64_t ch, int64_t row_stride, const int32_t * d_jump, int32_t W, int64_t out_frames, const WtPlan & plan,
+	const std::vector<WtRun> & runs, const float * index, int smooth, float * d_out, void * d_ws, hipStream_t s )
 	{
 	const int64_t num_blocks = int64_t( plan.blocks.size() );
 	const WtSynthLayout l = wt_synth_layout( ch, num_blocks, int64_t( runs.size() ) );
@@ -574,10 +580,67 @@ int launch_wt_synth( const float * d_table, int64_t ch, int64_t slots, int32_t W
 	const WtRun * d_runs = (const WtRun*) ( ws + l.wdl.run_off );
 	const float * d_index = (const float*) ( ws + l.index_off );
 	if( smooth )
-		return launch_kernel( "wavetable_synth", k_wt_synth<true>, int64_t( runs.size() ) * groups, WT_THREADS, 0, s, d_table, ch, slots, int( W ), out_frames,
+		return launch_kernel( "wavetable_synth", k_wt_synth<true>, int64_t( runs.size() ) * groups, WT_THREADS, 0, s, d_table, ch, row_stride, d_jump, int( W ), out_frames,
 			d_blocks, num_blocks, plan.total_in, d_runs, d_index, (const double*) d_win, groups, cpw, d_out );
-	return launch_kernel( "wavetable_synth", k_wt_synth<false>, int64_t( runs.size() ) * groups, WT_THREADS, 0, s, d_table, ch, slots, int( W ), out_frames,
+	return launch_kernel( "wavetable_synth", k_wt_synth<false>, int64_t( runs.size() ) * groups, WT_THREADS, 0, s, d_table, ch, row_stride, d_jump, int( W ), out_frames,
 		d_blocks, num_blocks, plan.total_in, d_runs, d_index, (const double*) d_win, groups, cpw, d_out );
+	}
+
+// the plan's per-block arrays for the *_synth_plan entry points: each nullable, filled up to `capacity`; returns the number of blocks
+int64_t wt_plan_copy( const WtPlan & plan, int64_t capacity, int64_t * offsets, double * fracpos, double * ratio, double * filtpos, int32_t * oversize,
+	int32_t * ideal, int64_t * first_out, int32_t * num_out, int32_t * wanted, int64_t * in_start )
+	{
+	const int64_t num_blocks = int64_t( plan.blocks.size() );
+	const int64_t fill = std::min<int64_t>( std::max<int64_t>( capacity, 0 ), num_blocks );
+	for( int64_t i = 0; i < fill; ++i )
+		{
+		const WtBlock & b = plan.blocks[size_t( i )];
+		if( offsets ) offsets[i] = b.offset;
+		if( fracpos ) fracpos[i] = b.fracpos;
+		if( ratio ) ratio[i] = b.ratio;
+		if( filtpos ) filtpos[i] = b.filtpos;
+		if( oversize ) oversize[i] = b.oversize;
+		if( ideal ) ideal[i] = b.ideal;
+		if( first_out ) first_out[i] = b.first_out;
+		if( num_out ) num_out[i] = b.num_out;
+		if( wanted ) wanted[i] = b.wanted;
+		if( in_start ) in_start[i] = b.in_start;
+		}
+	return num_blocks;
+	}
+
+// Audio::synthesize_spectrum's loop: one row of W = 2^p frames shared by the channels, channel c reading it from jump_c on
+constexpr int SP_MIN_POWER = 6, SP_MAX_POWER = 22;             // the tables flanhip_spectrum_table makes
+
+int sp_synth_check( int64_t out_frames, double rate_out, int64_t ch, int32_t p, int64_t g, const float * freq, int64_t freq_count )
+	{
+	FLANHIP_REQUIRE( p >= SP_MIN_POWER && p <= SP_MAX_POWER, FLANHIP_ERR_UNSUPPORTED, "the table must hold 2^6 ... 2^22 frames" );
+	FLANHIP_REQUIRE( ch > 0, FLANHIP_ERR_INVALID_ARG, "non-positive size" );
+	FLANHIP_REQUIRE( ch <= ( 1 << 16 ), FLANHIP_ERR_UNSUPPORTED, "shape out of range" );
+	FLANHIP_REQUIRE( rate_out > 0.0 && std::isfinite( rate_out ), FLANHIP_ERR_INVALID_ARG, "output rate not positive" );
+	return wt_synth_check( out_frames, 1.0f, int32_t( 1 ) << p, g, freq, freq_count );
+	}
+
+struct SpSynthLayout { WtSynthLayout wt; size_t jump_off, total; };
+SpSynthLayout sp_synth_layout( int64_t ch, int64_t num_blocks, int64_t num_runs )
+	{
+	SpSynthLayout l;
+	l.wt = wt_synth_layout( ch, num_blocks, num_runs );
+	l.jump_off = ( l.wt.total + 15 ) & ~size_t( 15 );
+	l.total = l.jump_off + sizeof( int32_t ) * size_t( ch );
+	return l;
+	}
+
+int launch_sp_synth( const float * d_table, int32_t p, int64_t ch, int64_t out_frames, const WtPlan & plan, const std::vector<WtRun> & runs, float * d_out,
+	void * d_ws, hipStream_t s )
+	{
+	const SpSynthLayout l = sp_synth_layout( ch, int64_t( plan.blocks.size() ), int64_t( runs.size() ) );
+	std::vector<int32_t> jump( size_t( ch ), 0 );
+	for( int64_t c = 0; c < ch; ++c ) jump[size_t( c )] = flanhip_spectrum_jump( c, ch, p );
+	FLANHIP_CHECK( hipMemcpyAsync( ws_at<char>( d_ws, l.jump_off ), jump.data(), sizeof( int32_t ) * jump.size(), hipMemcpyHostToDevice, s ) );
+	FLANHIP_CHECK( hipStreamSynchronize( s ) );
+	const std::vector<float> index( size_t( ch ) * plan.blocks.size(), 0.0f );        // one slot: every block reads waveform 0
+	return launch_wt_synth( d_table, ch, 0, ws_at<int32_t>( d_ws, l.jump_off ), int32_t( 1 ) << p, out_frames, plan, runs, index.data(), 0, d_out, d_ws, s );
 	}
 
 // ------------------------------------------------------------------------------------------------------------------------------------
@@ -797,24 +860,8 @@ int64_t flanhip_wavetable_synth_plan( int64_t out_frames, float sample_rate, int
 	{
 	if( int rc = wt_synth_check( out_frames, sample_rate, wavelength, granularity_frames, freq, freq_count ) ) return rc;
 	WtPlan plan;
-	if( int rc = wt_synth_plan( out_frames, sample_rate, wavelength, granularity_frames, freq, freq_count, &plan ) ) return rc;
-	const int64_t num_blocks = int64_t( plan.blocks.size() );
-	const int64_t fill = std::min<int64_t>( std::max<int64_t>( capacity, 0 ), num_blocks );
-	for( int64_t i = 0; i < fill; ++i )
-		{
-		const WtBlock & b = plan.blocks[size_t( i )];
-		if( offsets ) offsets[i] = b.offset;
-		if( fracpos ) fracpos[i] = b.fracpos;
-		if( ratio ) ratio[i] = b.ratio;
-		if( filtpos ) filtpos[i] = b.filtpos;
-		if( oversize ) oversize[i] = b.oversize;
-		if( ideal ) ideal[i] = b.ideal;
-		if( first_out ) first_out[i] = b.first_out;
-		if( num_out ) num_out[i] = b.num_out;
-		if( wanted ) wanted[i] = b.wanted;
-		if( in_start ) in_start[i] = b.in_start;
-		}
-	return num_blocks;
+	if( int rc = wt_synth_plan( out_frames, wt_rate_out( sample_rate, wavelength ), granularity_frames, freq, freq_count, &plan ) ) return rc;
+	return wt_plan_copy( plan, capacity, offsets, fracpos, ratio, filtpos, oversize, ideal, first_out, num_out, wanted, in_start );
 	}
 
 size_t flanhip_wavetable_synth_workspace_bytes( int64_t num_channels, int64_t out_frames, float sample_rate, int32_t wavelength, int64_t granularity_frames,
@@ -823,7 +870,7 @@ size_t flanhip_wavetable_synth_workspace_bytes( int64_t num_channels, int64_t ou
 	if( num_channels <= 0 || wt_synth_check( out_frames, sample_rate, wavelength, granularity_frames, freq, freq_count ) ) return 0;
 	WtPlan plan;
 	std::vector<WtRun> runs;
-	if( wt_synth_plan( out_frames, sample_rate, wavelength, granularity_frames, freq, freq_count, &plan ) ) return 0;
+	if( wt_synth_plan( out_frames, wt_rate_out( sample_rate, wavelength ), granularity_frames, freq, freq_count, &plan ) ) return 0;
 	wt_runs( plan, &runs );
 	return wt_synth_layout( num_channels, int64_t( plan.blocks.size() ), int64_t( runs.size() ) ).total;
 	}
@@ -836,11 +883,11 @@ int flanhip_wavetable_synth_dev( const float * d_table, int64_t num_channels, in
 	FLANHIP_REQUIRE( d_workspace, FLANHIP_ERR_INVALID_ARG, "null workspace" );
 	WtPlan plan;
 	std::vector<WtRun> runs;
-	if( int rc = wt_synth_plan( out_frames, sample_rate, wavelength, granularity_frames, freq, freq_count, &plan ) ) return rc;
+	if( int rc = wt_synth_plan( out_frames, wt_rate_out( sample_rate, wavelength ), granularity_frames, freq, freq_count, &plan ) ) return rc;
 	if( int rc = wt_synth_args( d_table, num_channels, slots, wavelength, index, num_blocks, plan, d_out ) ) return rc;
 	wt_runs( plan, &runs );
 	if( int rc = require_device() ) return rc;
-	return launch_wt_synth( d_table, num_channels, slots, wavelength, out_frames, plan, runs, index, smooth, d_out, d_workspace, (hipStream_t) stream );
+	return launch_wt_synth( d_table, num_channels, slots * wavelength, nullptr, wavelength, out_frames, plan, runs, index, smooth, d_out, d_workspace, (hipStream_t) stream );
 	}
 
 int flanhip_wavetable_synth( const float * table, int64_t num_channels, int64_t slots, int32_t wavelength, float sample_rate, int64_t out_frames,
@@ -850,7 +897,7 @@ int flanhip_wavetable_synth( const float * table, int64_t num_channels, int64_t 
 	if( int rc = wt_synth_check( out_frames, sample_rate, wavelength, granularity_frames, freq, freq_count ) ) return rc;
 	WtPlan plan;
 	std::vector<WtRun> runs;
-	if( int rc = wt_synth_plan( out_frames, sample_rate, wavelength, granularity_frames, freq, freq_count, &plan ) ) return rc;
+	if( int rc = wt_synth_plan( out_frames, wt_rate_out( sample_rate, wavelength ), granularity_frames, freq, freq_count, &plan ) ) return rc;
 	if( int rc = wt_synth_args( table, num_channels, slots, wavelength, index, num_blocks, plan, out ) ) return rc;
 	wt_runs( plan, &runs );
 	if( int rc = require_device() ) return rc;
@@ -861,7 +908,66 @@ int flanhip_wavetable_synth( const float * table, int64_t num_channels, int64_t 
 	if( int rc = call.out( out, sizeof( float ) * size_t( num_channels ) * size_t( out_frames ), &d_out ) ) return rc;
 	if( int rc = call.scratch( wt_synth_layout( num_channels, int64_t( plan.blocks.size() ), int64_t( runs.size() ) ).total, &d_ws ) ) return rc;
 	if( int rc = call.ready() ) return rc;
-	if( int rc = launch_wt_synth( d_table, num_channels, slots, wavelength, out_frames, plan, runs, index, smooth, d_out, d_ws, nullptr ) ) return rc;
+	if( int rc = launch_wt_synth( d_table, num_channels, slots * wavelength, nullptr, wavelength, out_frames, plan, runs, index, smooth, d_out, d_ws, nullptr ) ) return rc;
+	return call.finish();
+	}
+
+// ---- the loop of Audio::synthesize_spectrum (AudioSynthesis.cpp:230-263): the same resampler over ONE table row of W = 2^p frames, which
+// every channel reads at its own phase offset; one slot, no blend
+
+int64_t flanhip_spectrum_synth_plan( int64_t out_frames, double rate_out, int64_t granularity_frames, const float * freq, int64_t freq_count,
+	int64_t capacity, int64_t * offsets, double * fracpos, double * ratio, double * filtpos, int32_t * oversize, int32_t * ideal, int64_t * first_out,
+	int32_t * num_out, int32_t * wanted, int64_t * in_start )
+	{
+	if( int rc = sp_synth_check( out_frames, rate_out, 1, 6, granularity_frames, freq, freq_count ) ) return rc;
+	WtPlan plan;
+	if( int rc = wt_synth_plan( out_frames, std::max( rate_out, 1.0 ), granularity_frames, freq, freq_count, &plan ) ) return rc;
+	return wt_plan_copy( plan, capacity, offsets, fracpos, ratio, filtpos, oversize, ideal, first_out, num_out, wanted, in_start );
+	}
+
+size_t flanhip_spectrum_synth_workspace_bytes( int32_t table_size_power, double rate_out, int64_t num_channels, int64_t out_frames, int64_t granularity_frames,
+	const float * freq, int64_t freq_count )
+	{
+	if( sp_synth_check( out_frames, rate_out, num_channels, table_size_power, granularity_frames, freq, freq_count ) ) return 0;
+	WtPlan plan;
+	std::vector<WtRun> runs;
+	if( wt_synth_plan( out_frames, std::max( rate_out, 1.0 ), granularity_frames, freq, freq_count, &plan ) ) return 0;
+	wt_runs( plan, &runs );
+	return sp_synth_layout( num_channels, int64_t( plan.blocks.size() ), int64_t( runs.size() ) ).total;
+	}
+
+int flanhip_spectrum_synth_dev( const float * d_table, int32_t table_size_power, double rate_out, int64_t num_channels, int64_t out_frames,
+	int64_t granularity_frames, const float * freq, int64_t freq_count, float * d_out, void * d_workspace, void * stream )
+	{
+	if( int rc = sp_synth_check( out_frames, rate_out, num_channels, table_size_power, granularity_frames, freq, freq_count ) ) return rc;
+	FLANHIP_REQUIRE( d_table && d_out, FLANHIP_ERR_INVALID_ARG, "null buffer" );
+	FLANHIP_REQUIRE( d_workspace, FLANHIP_ERR_INVALID_ARG, "null workspace" );
+	WtPlan plan;
+	std::vector<WtRun> runs;
+	if( int rc = wt_synth_plan( out_frames, std::max( rate_out, 1.0 ), granularity_frames, freq, freq_count, &plan ) ) return rc;
+	wt_runs( plan, &runs );
+	if( int rc = require_device() ) return rc;
+	return launch_sp_synth( d_table, table_size_power, num_channels, out_frames, plan, runs, d_out, d_workspace, (hipStream_t) stream );
+	}
+
+int flanhip_spectrum_synth( const float * table, int32_t table_size_power, double rate_out, int64_t num_channels, int64_t out_frames,
+	int64_t granularity_frames, const float * freq, int64_t freq_count, float * out, volatile int * cancel )
+	{
+	if( int rc = sp_synth_check( out_frames, rate_out, num_channels, table_size_power, granularity_frames, freq, freq_count ) ) return rc;
+	FLANHIP_REQUIRE( table && out, FLANHIP_ERR_INVALID_ARG, "null buffer" );
+	WtPlan plan;
+	std::vector<WtRun> runs;
+	if( int rc = wt_synth_plan( out_frames, std::max( rate_out, 1.0 ), granularity_frames, freq, freq_count, &plan ) ) return rc;
+	wt_runs( plan, &runs );
+	if( int rc = require_device() ) return rc;
+	if( cancelled( cancel ) ) return FLANHIP_ERR_CANCELLED;
+	HostCall call( cancel );
+	const float * d_table = nullptr; float * d_out = nullptr; void * d_ws = nullptr;
+	if( int rc = call.in( table, sizeof( float ) << table_size_power, &d_table ) ) return rc;
+	if( int rc = call.out( out, sizeof( float ) * size_t( num_channels ) * size_t( out_frames ), &d_out ) ) return rc;
+	if( int rc = call.scratch( sp_synth_layout( num_channels, int64_t( plan.blocks.size() ), int64_t( runs.size() ) ).total, &d_ws ) ) return rc;
+	if( int rc = call.ready() ) return rc;
+	if( int rc = launch_sp_synth( d_table, table_size_power, num_channels, out_frames, plan, runs, d_out, d_ws, nullptr ) ) return rc;
 	return call.finish();
 	}
 

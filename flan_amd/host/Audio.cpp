@@ -12,6 +12,7 @@
 #include <cmath>
 #include <ctime>
 #include <iostream>
+#include <random>
 
 #include "device_call.h"
 #include "flan/PV.h"
@@ -1328,6 +1329,77 @@ Audio Audio::psola( Second length, const Function<Second, Second> & time_selecti
 	if( flanhip_grains_events( sampled_frames, sr, rate.data(), 0.0f, nullptr, 0.0f, 0, frames.data(), sampled_frames, &count ) != FLANHIP_OK ) return Audio::create_null();
 	frames.resize( static_cast<size_t>( count ) );
 	return granulate_sampled( *this, frames, sampled_frames, SampledCurve{ &picked, 0.0f }, SampledCurve{ &lengths, 0.0f }, SampledCurve{ nullptr, 0.05f }, mod, true );
+	}
+
+// Audio/AudioSynthesis.cpp:151-268.  The spectrum's magnitudes and phases and the frequency curve are made here; the table (one inverse real FFT
+// of 2^spectrum_size_power points), the resampler loop over it and set_volume( 1 ) run on the device without coming back in between
+Audio Audio::synthesize_spectrum( Second length, const Function<Second, Frequency> & freq, const Function<Harmonic, Frequency> & spread,
+	const Function<Harmonic, Amplitude> & harmonic_scale, const Function<Frequency, Amplitude> & peak_distribution, int fundamental_power,
+	int spectrum_size_power, Channel num_channels, Second granularity_time, const std::vector<Radian> * phases )
+	{
+	if( length <= 0 || fundamental_power <= 0 || spectrum_size_power <= 0 || fundamental_power > spectrum_size_power || granularity_time <= 0 )
+		return Audio::create_null();                                               // :163-168
+	const FrameRate sr = 48000.0f;                                                 // the table's, create_empty_with_frames' default (:179)
+	AudioBuffer::Format format;                                                    // :224-228
+	format.num_channels = num_channels; format.sample_rate = sr;
+	Frame granularity = 0;
+	const int64_t bins = flanhip_spectrum_bins( spectrum_size_power, fundamental_power, nullptr, nullptr, 0 );
+	if( !frame_of( length, sr, format.num_frames ) || !frame_of( granularity_time, sr, granularity ) || format.num_frames < 1 || granularity < 1
+		|| num_channels < 1 || bins < 1 || flanhip_spectrum_table_workspace_bytes( spectrum_size_power ) == 0 || ( phases && int64_t( phases->size() ) != bins ) )
+		{
+		std::cerr << "flan: synthesize_spectrum refused: 2^" << spectrum_size_power << " table frames (6 ... 22 are served), " << format.num_frames
+		          << " output frames, a granularity of " << granularity << " frames, " << num_channels << " channels"
+		          << ( phases && int64_t( phases->size() ) != bins ? ", phases that are not one per bin" : "" ) << std::endl;
+		return Audio::create_null();
+		}
+	const Frame n = format.num_frames;
+
+	// :185-210: per-harmonic spread and scale, then one magnitude per bin with a harmonic
+	std::vector<int32_t> harmonic( static_cast<size_t>( bins ) );
+	std::vector<float> bin_frequency( harmonic.size() );
+	flanhip_spectrum_bins( spectrum_size_power, fundamental_power, harmonic.data(), bin_frequency.data(), bins );
+	const Harmonic num_harmonics = flanhip_spectrum_num_harmonics( fundamental_power );
+	const Frequency fundamental = Frequency( std::pow( 2, fundamental_power ) );
+	std::vector<Amplitude> harmonic_scale_sampled( static_cast<size_t>( num_harmonics ) ), spread_sampled( harmonic_scale_sampled.size() );
+	detail::for_each_index( 0, num_harmonics, harmonic_scale.get_execution_policy(), [&]( int h ){ harmonic_scale_sampled[size_t( h )] = harmonic_scale( h + 1 ); } );
+	detail::for_each_index( 0, num_harmonics, spread.get_execution_policy(), [&]( int h ){ spread_sampled[size_t( h )] = spread( h + 1 ); } );
+	detail::StagingVector<float> mag( harmonic.size() ), theta( harmonic.size() );
+	detail::for_each_index( 0, int( bins ), peak_distribution.get_execution_policy(), [&]( int bin )
+		{
+		const int h = harmonic[size_t( bin )];
+		mag[size_t( bin )] = 0.0f;                                                 // (the reference leaves a skipped bin uninitialised)
+		if( h <= 0 || h > num_harmonics ) return;
+		const Frequency epsilon = 0.001f;
+		const Frequency mean = fundamental * h;
+		const Frequency sd = spread_sampled[size_t( h - 1 )];
+		const Frequency x = bin_frequency[size_t( bin )];
+		mag[size_t( bin )] = ( sd <= epsilon ? x : peak_distribution( ( x - mean ) / sd ) / sd ) * harmonic_scale_sampled[size_t( h - 1 )];
+		} );
+	if( phases ) std::copy( phases->begin(), phases->end(), &theta[0] );
+	else
+		{
+		std::random_device rd;                                                     // :182-183
+		flanhip_spectrum_phases( rd(), harmonic.data(), bins, &theta[0] );
+		}
+
+	// freq at every output frame (a block reads the entry of the frame it starts on, :243); a constant is one entry
+	std::vector<float> freq_v( freq.is_constant() ? size_t( 1 ) : size_t( n ) );
+	if( freq.is_constant() ) freq_v[0] = freq.get_constant();
+	else detail::for_each_index( 0, n, freq.get_execution_policy(), [&]( int x ){ freq_v[size_t( x )] = freq( fFrame( x ) / sr ); } );
+
+	const size_t ws_bytes = flanhip_audio_synthesize_spectrum_workspace_bytes( spectrum_size_power, fundamental_power, num_channels, n, granularity, freq_v.data(),
+		int64_t( freq_v.size() ) );
+	if( ws_bytes == 0 )
+		{
+		std::cerr << "flan: synthesize_spectrum refused: " << flanhip_last_error() << std::endl;
+		return Audio::create_null();
+		}
+	const DeviceArg d_mag = upload_values( mag ), d_theta = upload_values( theta );
+	return audio_call( "synthesize_spectrum", format, d_mag.ok && d_theta.ok, ws_bytes, [&]( float * d_out, void * ws )
+		{
+		return flanhip_audio_synthesize_spectrum_dev( d_mag.ptr(), d_theta.ptr(), spectrum_size_power, fundamental_power, num_channels, n, granularity,
+			freq_v.data(), int64_t( freq_v.size() ), d_out, ws, nullptr );
+		} );
 	}
 
 } // namespace flan

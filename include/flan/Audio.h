@@ -338,6 +338,23 @@ public:
 	 *  mixing kernel; a mod takes granulate's general path and the window follows it (modify_volume_in_place on the grain).  The window is
 	 *  hann( x ) = 0.5f * ( 1.0f - cos( 2.0f * pi * x ) ) with the DOUBLE cos the reference's unqualified call picks (WindowFunctions.cpp:10-13). */
 	Audio psola( Second length, const Function<Second, Second> & time_selection, const AudioMod & mod = AudioMod() ) const;
+	/** A tone from the spectral dispersion and amplitude of each harmonic (Audio/AudioSynthesis.cpp:151-268): one period of 2^spectrum_size_power
+	 *  frames at 48000 Hz made by ONE inverse real FFT over a spectrum whose bin near harmonic h of 2^fundamental_power Hz holds
+	 *  peak_distribution( ( x - mean ) / sd ) / sd * harmonic_scale( h ) with sd = spread( h ) (the bin's own frequency where sd <= 0.001) at a
+	 *  random phase, then read through the 64-tap sinc resampler at freq( t ), channel c starting c / num_channels of a period in, and set to volume 1.
+	 *  spread and harmonic_scale are sampled once per harmonic, peak_distribution once per bin under its policy, freq at every output frame at
+	 *  frame / 48000 (a block of `granularity` seconds reads the entry of its first frame); all of that on the host, the transform, the loop and
+	 *  the normalisation on the device (flanhip_audio_synthesize_spectrum_dev).  `phases`: one angle per bin ( 2^(spectrum_size_power-1) + 1 of
+	 *  them), which makes the call deterministic; without it they come from std::mt19937 seeded from std::random_device, drawn in ascending bin
+	 *  order.  Bins without a harmonic, which the reference leaves uninitialised, are zero.  length <= 0, a power <= 0, fundamental_power >
+	 *  spectrum_size_power or granularity <= 0 give a null Audio (:163-168); a size the library does not serve ( spectrum_size_power outside
+	 *  6 ... 22 ) or a rate it refuses gives a null Audio and one line on std::cerr. */
+	static Audio synthesize_spectrum( Second length, const Function<Second, Frequency> & freq,
+		const Function<Harmonic, Frequency> & spread = []( Harmonic h ){ return Frequency( h ); },
+		const Function<Harmonic, Amplitude> & harmonic_scale = []( Harmonic h ){ return 1.0f / std::sqrt( float( h ) ); },
+		const Function<Frequency, Amplitude> & peak_distribution = []( Frequency x ){ return 1.0f / std::sqrt( pi2 ) * std::exp( -0.5f * std::pow( x, 2.0f ) ); },
+		int fundamental_power = 8, int spectrum_size_power = 20, Channel num_channels = 2, Second granularity = 0.001f,
+		const std::vector<Radian> * phases = nullptr );
 
 	// the older camelCase spellings BASELINE.json's north_star uses
 	PV convertToPV( Frame window_size = 2048, Frame hop = 128, Frame dft_size = 4096, flan_CANCEL_ARG ) const;

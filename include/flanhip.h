@@ -1156,6 +1156,59 @@ int flanhip_wavetable_synth(const float * table, int64_t num_channels, int64_t s
 int flanhip_wavetable_edit_dev(float * d_table, int64_t num_channels, int64_t slots, int32_t wavelength, int mode, int32_t fade_frames, void * stream);
 int flanhip_wavetable_edit(float * table, int64_t num_channels, int64_t slots, int32_t wavelength, int mode, int32_t fade_frames, volatile int * cancel);
 
+/* ---- Audio::synthesize_spectrum (Audio/AudioSynthesis.cpp:151-268; WDL/resample.cpp) (flan_amd/csrc/spectrum.hip) ------ */
+/* N = 2^spectrum_size_power table frames, C = N/2, B = C + 1 bins, fundamental = 2^fundamental_power, the table's sample rate 48000.
+ * Host-only helpers (no device needed), the reference's fp32 arithmetic:
+ *   bins           freq[b] = b * 48000 / float( B ) (:186 -- by B, not N) and harmonic[b] = int( round( freq[b] / fundamental ) ) (:201), each array
+ *                  nullable and filled up to `capacity`; returns B (0 for powers outside 1 ... 30 / 0 ... 30)
+ *   num_harmonics  ceil( 48000 / fundamental ) + 1 (:188): spread and harmonic_scale are sampled at harmonics 1 ... num_harmonics (:190-196)
+ *   phases         std::mt19937( seed ) and one std::uniform_real_distribution<float>( 0, 2 pi ) draw (:212) per bin with harmonic != 0 in ascending
+ *                  bin order, 0 elsewhere (the reference seeds from std::random_device and draws in the order its parallel loop reaches the bins)
+ *   jump           Frame( ( float( channel ) / num_channels ) * N ) (:236), channel c's phase offset into the table */
+int64_t flanhip_spectrum_bins(int32_t spectrum_size_power, int32_t fundamental_power, int32_t * harmonic, float * freq, int64_t capacity);
+int32_t flanhip_spectrum_num_harmonics(int32_t fundamental_power);
+int flanhip_spectrum_phases(uint32_t seed, const int32_t * harmonic, int64_t bins, float * theta);
+int32_t flanhip_spectrum_jump(int64_t channel, int64_t num_channels, int32_t spectrum_size_power);
+/* The table (:198-219): bin b holds polar( mag[b], theta[b] ) (:214), formed in fp32, and fftwf_plan_dft_c2r_1d( N ) -- unnormalised, the
+ * imaginary parts of bins 0 and C ignored -- gives
+ *   table[n] = Re X0 + (-1)^n Re X_C + 2 sum_{k=1}^{C-1} Re( X_k exp( +2 pi i k n / N ) ).
+ * mag, theta: float[B]; table: float[N].  Bins the reference skips ( harmonic == 0, :202 ) it leaves as whatever fftwf_alloc_complex
+ * returned; here they are what the caller passes, and the callers of this library pass ZERO.  6 <= spectrum_size_power <= 22, else
+ * FLANHIP_ERR_UNSUPPORTED (the reference accepts up to 31).  Up to 13 one workgroup transforms the C complex points in LDS; above, C = C1 C2
+ * in two passes through the workspace ( C1 = max( 16, C / 4096 ) ), twiddles from sincospi of exact dyadic arguments.  Fixed summation
+ * order: two runs agree bit for bit.  Workspace: 8 C bytes. */
+size_t flanhip_spectrum_table_workspace_bytes(int32_t spectrum_size_power);   /* 0 for arguments it refuses */
+int flanhip_spectrum_table_dev(const float * d_mag, const float * d_theta, int32_t spectrum_size_power, float * d_table, void * d_workspace,
+                               void * stream);
+int flanhip_spectrum_table(const float * mag, const float * theta, int32_t spectrum_size_power, float * table, volatile int * cancel);
+/* The loop (:230-263): flanhip_wavetable_synth's resampler over ONE row of W = 2^table_size_power frames, one slot, no blend, with
+ * SetRates( max( freq, 1 ), max( rate_out, 1 ) ) (:247; rate_out = the fundamental) and input sample t of channel c read at
+ * table[( t + jump_c ) % W], jump_c = flanhip_spectrum_jump( c, num_channels, table_size_power ) computed inside (:254).  freq: HOST, per
+ * output frame or one entry, as flanhip_wavetable_synth takes it; out: float[ch][out_frames].  The block plan does not depend on the channel;
+ * flanhip_spectrum_synth_plan returns it as flanhip_wavetable_synth_plan does, with the same refusals (a ratio above 34 after the first
+ * block, a granularity below one frame, a frequency that is not finite). */
+int64_t flanhip_spectrum_synth_plan(int64_t out_frames, double rate_out, int64_t granularity_frames, const float * freq, int64_t freq_count,
+                                    int64_t capacity, int64_t * offsets, double * fracpos, double * ratio, double * filtpos, int32_t * oversize,
+                                    int32_t * ideal, int64_t * first_out, int32_t * num_out, int32_t * wanted, int64_t * in_start);
+size_t flanhip_spectrum_synth_workspace_bytes(int32_t table_size_power, double rate_out, int64_t num_channels, int64_t out_frames,
+                                              int64_t granularity_frames, const float * freq, int64_t freq_count);   /* 0 for arguments it refuses */
+int flanhip_spectrum_synth_dev(const float * d_table, int32_t table_size_power, double rate_out, int64_t num_channels, int64_t out_frames,
+                               int64_t granularity_frames, const float * freq, int64_t freq_count, float * d_out, void * d_workspace, void * stream);
+int flanhip_spectrum_synth(const float * table, int32_t table_size_power, double rate_out, int64_t num_channels, int64_t out_frames,
+                           int64_t granularity_frames, const float * freq, int64_t freq_count, float * out, volatile int * cancel);
+/* Audio::synthesize_spectrum after its Functions have been sampled (:198-265), without leaving the device: flanhip_spectrum_table into the
+ * workspace, flanhip_spectrum_synth with rate_out = 2^fundamental_power, then flanhip_audio_set_volume_dev at 48000 with level 1 (:265; it
+ * does not look at the last frame).  out_frames = Frame( length * 48000.0f ), granularity_frames = Frame( granularity_time * 48000.0f )
+ * (:225-228).  fundamental_power outside 1 ... spectrum_size_power is FLANHIP_ERR_INVALID_ARG (:164-166). */
+size_t flanhip_audio_synthesize_spectrum_workspace_bytes(int32_t spectrum_size_power, int32_t fundamental_power, int64_t num_channels,
+                                                         int64_t out_frames, int64_t granularity_frames, const float * freq, int64_t freq_count);
+int flanhip_audio_synthesize_spectrum_dev(const float * d_mag, const float * d_theta, int32_t spectrum_size_power, int32_t fundamental_power,
+                                          int64_t num_channels, int64_t out_frames, int64_t granularity_frames, const float * freq,
+                                          int64_t freq_count, float * d_out, void * d_workspace, void * stream);
+int flanhip_audio_synthesize_spectrum(const float * mag, const float * theta, int32_t spectrum_size_power, int32_t fundamental_power,
+                                      int64_t num_channels, int64_t out_frames, int64_t granularity_frames, const float * freq, int64_t freq_count,
+                                      float * out, volatile int * cancel);
+
 /* ---- synthetic input + comparison utilities (bench / tests; defined by this project) -------------- */
 int flanhip_noise_dev(float * d_out, int64_t num_channels, int64_t num_audio_frames, uint32_t seed, void * stream);
 /* a plain streaming copy, 16 bytes per lane: the measured-copy yardstick bench.py quotes beside the 8 TB/s spec (count: floats, a multiple of 4) */
