@@ -5,15 +5,13 @@
 // position and how many samples stay buffered), which a host loop reproduces exactly in fp64 (repitch_plan: O( output frames )
 // additions); after that every output sample is an independent 64-tap sum (two of them, interpolated, unless the rates are "ideal")
 // over a window of one continuous stream: 31 zeros, the input, zeros.  The resampler itself -- the choice of table, the table, the tap
-// sums, the stream -- is wdl_sinc.h's, shared with spatial.hip; the plan, the runs and the kernels around them are this file's.
+// sums, the stream -- is wdl_sinc.h's, shared with spatial.hip and wavetable.hip; the plan, the runs and the kernels around them are this file's.
 //   k_wdl_window<64>   the Blackman-Harris factor of every table entry, per oversize in use, in fp64 (once per call)
 //   k_repitch_sinc     one workgroup per run of consecutive blocks that share a coefficient table: builds the table in LDS, stages the
 //                      run's input window in LDS when it fits, one output sample per thread per channel
 //   k_repitch_point    the Uninterpolated quality: in[ int( srcpos ) ]
 // Every sum runs in a fixed order and nothing is atomic, so two runs agree bit for bit.
 #include "wdl_sinc.h"
-
-#include <algorithm>
 
 namespace flanhip {
 
@@ -47,6 +45,7 @@ struct RpRun                                   // consecutive blocks that share 
 	int64_t win_start;                         // stream index of the first staged sample
 	int32_t win_len, ideal;                    // staged samples (0: read global memory)
 	};
+static_assert( sizeof( RpBlock ) == 56 && sizeof( RpRun ) == 40, "the device reads these records as the host lays them out" );
 
 struct RpPlan
 	{
@@ -123,7 +122,7 @@ void rp_runs( const RpPlan & plan, int64_t g, int quality, std::vector<RpRun> * 
 		while( k < plan.blocks.size() && int64_t( k - i ) < max_blocks )
 			{
 			const RpBlock & b = plan.blocks[k];
-			if( b.oversize != a.oversize || b.ideal != a.ideal || b.filtpos != a.filtpos ) break;
+			if( !wdl_same_table( a, b ) ) break;
 			const int64_t e = std::max( end, block_end( b ) );
 			if( e - r.win_start > RP_WINDOW_FLOATS ) break;
 			end = e; ++k;
@@ -226,13 +225,6 @@ int rp_prepare( int64_t ch, int64_t n, float sr, const float * inv, int64_t coun
 	return FLANHIP_OK;
 	}
 
-int rp_cpw( const RpPlan & plan, const std::vector<RpRun> & runs, int64_t ch, int64_t g )
-	{
-	// channels per workgroup: one where a run has work for every thread several times over, more where the table dominates
-	const int64_t per_run = std::max<int64_t>( int64_t( plan.blocks.size() ) * g / std::max<int64_t>( int64_t( runs.size() ), 1 ), 1 );
-	return int( std::clamp<int64_t>( 512 / per_run, 1, ch ) );
-	}
-
 int launch_repitch( const float * d_x, int64_t ch, int64_t n, int64_t g, int quality, const RpPlan & plan, const std::vector<RpRun> & runs,
 	float * d_out, void * d_ws, hipStream_t s )
 	{
@@ -257,14 +249,12 @@ int launch_repitch( const float * d_x, int64_t ch, int64_t n, int64_t g, int qua
 		const int64_t grid = std::min<int64_t>( ( count + RP_THREADS - 1 ) / RP_THREADS, 65536 );
 		return launch_kernel( "repitch", k_repitch_point, grid, RP_THREADS, 0, s, d_x, ch, n, g, plan.out_frames, d_blocks, num_blocks, d_out );
 		}
-	uint64_t used = 0;
-	for( const RpRun & r : runs ) used |= uint64_t( 1 ) << ( r.oversize - 1 );
-	double * d_win = (double*) ( ws + l.win_off );
-	if( int rc = launch_kernel( "repitch", k_wdl_window<RP_TAPS>, WDL_MAX_OVERSIZE, RP_THREADS, 0, s, d_win, used ) ) return rc;
-	const int cpw = rp_cpw( plan, runs, ch, g );
+	const double * d_win = nullptr;
+	if( int rc = wdl_window<RP_TAPS>( "repitch", d_ws, l, runs, s, &d_win ) ) return rc;
+	const int cpw = wdl_channels_per_group( num_blocks * g, runs.size(), ch );
 	const int64_t groups = ( ch + cpw - 1 ) / cpw;
 	return launch_kernel( "repitch", k_repitch_sinc, int64_t( runs.size() ) * groups, RP_THREADS, 0, s, d_x, ch, n, g, plan.out_frames, d_blocks,
-		(const RpRun*) ( ws + l.run_off ), (const double*) d_win, groups, cpw, d_out );
+		(const RpRun*) ( ws + l.run_off ), d_win, groups, cpw, d_out );
 	}
 
 } // namespace
@@ -291,20 +281,8 @@ int64_t flanhip_audio_repitch_plan( int64_t num_frames, float sample_rate, const
 	int64_t num_blocks = 0;
 	if( int rc = rp_plan( num_frames, sample_rate, inv_factors, count, granularity_frames, quality, capacity > 0, &plan, &num_blocks ) ) return rc;
 	if( out_frames ) *out_frames = rp_out_frames( inv_factors, count, granularity_frames );
-	const int64_t fill = std::min<int64_t>( std::max<int64_t>( capacity, 0 ), num_blocks );
-	for( int64_t i = 0; i < fill; ++i )
-		{
-		const RpBlock & b = plan.blocks[size_t( i )];
-		if( offsets ) offsets[i] = b.offset;
-		if( fracpos ) fracpos[i] = b.fracpos;
-		if( ratio ) ratio[i] = b.ratio;
-		if( filtpos ) filtpos[i] = b.filtpos;
-		if( oversize ) oversize[i] = b.oversize;
-		if( ideal ) ideal[i] = b.ideal;
-		if( first_out ) first_out[i] = b.first_out;
-		if( wanted ) wanted[i] = b.wanted;
-		}
-	return num_blocks;
+	return wdl_export_plan( plan.blocks, num_blocks, capacity, offsets, fracpos, ratio, filtpos, oversize, ideal, first_out,
+		[&]( int64_t i, const RpBlock & b ) { if( wanted ) wanted[i] = b.wanted; } );
 	}
 
 size_t flanhip_audio_repitch_workspace_bytes( int64_t num_frames, float sample_rate, const float * inv_factors, int64_t count,

@@ -18,8 +18,6 @@
 // Every sum runs in a fixed order and nothing is atomic, so two runs agree bit for bit.
 #include "wdl_sinc.h"
 
-#include <algorithm>
-
 namespace flanhip {
 
 namespace {
@@ -60,6 +58,7 @@ struct SpRun                                   // one workgroup
 	int32_t first_j, count;                    // a run of ONE block may be a slice of it: outputs [first_j, first_j + count) of the block
 	int32_t ear, pad;
 	};
+static_assert( sizeof( SpBlock ) == 56 && sizeof( SpRun ) == 64, "the device reads these records as the host lays them out" );
 
 struct SpPlan
 	{
@@ -165,7 +164,7 @@ void sp_runs( const SpPlan & plan, int ear, int64_t keep, std::vector<SpRun> * r
 		while( k < plan.blocks.size() && int64_t( k - i ) < SP_RUN_BLOCKS )
 			{
 			const SpBlock & b = plan.blocks[k];
-			if( b.oversize != a.oversize || b.ideal != a.ideal || b.filtpos != a.filtpos || b.first_out >= keep ) break;
+			if( !wdl_same_table( a, b ) || b.first_out >= keep ) break;
 			if( total + b.count > SP_RUN_OUTPUTS ) break;
 			const int64_t e = std::max( end, b.offset + b.buffered );
 			if( e - r.win_start > SP_WINDOW_FLOATS ) break;
@@ -472,12 +471,10 @@ int launch_itd( const float * d_x, int64_t ears, int64_t n, const int64_t * out_
 		FLANHIP_CHECK( hipGetLastError() );
 		}
 	if( p.runs.empty() ) return FLANHIP_OK;
-	uint64_t used = 0;
-	for( const SpRun & r : p.runs ) used |= uint64_t( 1 ) << ( r.oversize - 1 );
-	double * d_win = (double*) ( ws + l.win_off );
-	if( int rc = launch_kernel( "spatial_itd", k_wdl_window<SP_TAPS>, WDL_MAX_OVERSIZE, SP_THREADS, 0, s, d_win, used ) ) return rc;
+	const double * d_win = nullptr;
+	if( int rc = wdl_window<SP_TAPS>( "spatial_itd", d_ws, l, p.runs, s, &d_win ) ) return rc;
 	return launch_kernel( "spatial_itd", k_spat_itd, int64_t( p.runs.size() ), SP_THREADS, 0, s, d_x, n, at, out_stride,
-		(const SpBlock*) ( ws + l.block_off ), (const SpRun*) ( ws + l.run_off ), (const double*) d_win, d_out );
+		(const SpBlock*) ( ws + l.block_off ), (const SpRun*) ( ws + l.run_off ), d_win, d_out );
 	}
 
 int sp_check_ear( const void * x, const void * lp, int64_t ch, int64_t n, float sr, float head_width, int ears, const void * out )
@@ -542,21 +539,8 @@ int64_t flanhip_spatial_itd_plan( int64_t num_frames, float sample_rate, const d
 	int64_t num_blocks = 0;
 	if( int rc = sp_plan( num_frames, sample_rate, stretches, count, capacity > 0, &plan, &num_blocks ) ) return rc;
 	if( total_out ) *total_out = plan.total_out;
-	const int64_t fill = std::min<int64_t>( std::max<int64_t>( capacity, 0 ), num_blocks );
-	for( int64_t i = 0; i < fill; ++i )
-		{
-		const SpBlock & b = plan.blocks[size_t( i )];
-		if( offsets ) offsets[i] = b.offset;
-		if( fracpos ) fracpos[i] = b.fracpos;
-		if( ratio ) ratio[i] = b.ratio;
-		if( filtpos ) filtpos[i] = b.filtpos;
-		if( oversize ) oversize[i] = b.oversize;
-		if( ideal ) ideal[i] = b.ideal;
-		if( first_out ) first_out[i] = b.first_out;
-		if( delivered ) delivered[i] = b.count;
-		if( buffered ) buffered[i] = b.buffered;
-		}
-	return num_blocks;
+	return wdl_export_plan( plan.blocks, num_blocks, capacity, offsets, fracpos, ratio, filtpos, oversize, ideal, first_out,
+		[&]( int64_t i, const SpBlock & b ) { if( delivered ) delivered[i] = b.count; if( buffered ) buffered[i] = b.buffered; } );
 	}
 
 size_t flanhip_spatial_itd_workspace_bytes( int64_t num_ears, int64_t num_frames, float sample_rate, const double * stretches, int64_t count )

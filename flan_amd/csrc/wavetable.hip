@@ -14,7 +14,6 @@
 #include "wdl_sinc.h"
 #include "fft_device.h"
 
-#include <algorithm>
 #include <cstring>
 
 namespace flanhip {
@@ -316,6 +315,7 @@ struct WtRun                                   // consecutive output frames that
 	int32_t win_len, q_count;
 	int32_t oversize, ideal;
 	};
+static_assert( sizeof( WtBlock ) == 72 && sizeof( WtRun ) == 80, "the device reads these records as the host lays them out" );
 
 struct WtPlan { std::vector<WtBlock> blocks; int64_t total_in = 0; };
 
@@ -446,7 +446,7 @@ void wt_runs( const WtPlan & plan, std::vector<WtRun> * runs )
 			{
 			const WtBlock & b = bl[k];
 			if( b.num_out == 0 ) { ++k; continue; }
-			if( b.oversize != a.oversize || b.ideal != a.ideal || b.filtpos != a.filtpos ) break;
+			if( !wdl_same_table( a, b ) ) break;
 			const int64_t e = std::max( end, taps_end( b, b.last_pos ) );
 			if( outs + b.num_out > WT_RUN_OUTPUTS || e - r.win_start > WT_WINDOW_FLOATS ) break;
 			end = e; outs += b.num_out; ++k;
@@ -568,45 +568,26 @@ int launch_wt_synth( const float * d_table, int64_t ch, int64_t row_stride, cons
 	FLANHIP_CHECK( hipMemcpyAsync( ws + l.wdl.run_off, runs.data(), sizeof( WtRun ) * runs.size(), hipMemcpyHostToDevice, s ) );
 	FLANHIP_CHECK( hipMemcpyAsync( ws + l.index_off, index, sizeof( float ) * size_t( ch * num_blocks ), hipMemcpyHostToDevice, s ) );
 	FLANHIP_CHECK( hipStreamSynchronize( s ) );                                  // the host arrays may go once the copies have read them
-	uint64_t used = 0;
-	for( const WtRun & r : runs ) used |= uint64_t( 1 ) << ( r.oversize - 1 );
-	double * d_win = (double*) ( ws + l.wdl.win_off );
-	if( int rc = launch_kernel( "wavetable_synth", k_wdl_window<WT_TAPS>, WDL_MAX_OVERSIZE, WT_THREADS, 0, s, d_win, used ) ) return rc;
-	// channels per workgroup: one where a run has work for every thread several times over, more where the table dominates
-	const int64_t per_run = std::max<int64_t>( out_frames / std::max<int64_t>( int64_t( runs.size() ), 1 ), 1 );
-	const int cpw = int( std::clamp<int64_t>( 512 / per_run, 1, ch ) );
+	const double * d_win = nullptr;
+	if( int rc = wdl_window<WT_TAPS>( "wavetable_synth", d_ws, l.wdl, runs, s, &d_win ) ) return rc;
+	const int cpw = wdl_channels_per_group( out_frames, runs.size(), ch );
 	const int64_t groups = ( ch + cpw - 1 ) / cpw;
 	const WtBlock * d_blocks = (const WtBlock*) ( ws + l.wdl.block_off );
 	const WtRun * d_runs = (const WtRun*) ( ws + l.wdl.run_off );
 	const float * d_index = (const float*) ( ws + l.index_off );
 	if( smooth )
 		return launch_kernel( "wavetable_synth", k_wt_synth<true>, int64_t( runs.size() ) * groups, WT_THREADS, 0, s, d_table, ch, row_stride, d_jump, int( W ), out_frames,
-			d_blocks, num_blocks, plan.total_in, d_runs, d_index, (const double*) d_win, groups, cpw, d_out );
+			d_blocks, num_blocks, plan.total_in, d_runs, d_index, d_win, groups, cpw, d_out );
 	return launch_kernel( "wavetable_synth", k_wt_synth<false>, int64_t( runs.size() ) * groups, WT_THREADS, 0, s, d_table, ch, row_stride, d_jump, int( W ), out_frames,
-		d_blocks, num_blocks, plan.total_in, d_runs, d_index, (const double*) d_win, groups, cpw, d_out );
+		d_blocks, num_blocks, plan.total_in, d_runs, d_index, d_win, groups, cpw, d_out );
 	}
 
 // the plan's per-block arrays for the *_synth_plan entry points: each nullable, filled up to `capacity`; returns the number of blocks
 int64_t wt_plan_copy( const WtPlan & plan, int64_t capacity, int64_t * offsets, double * fracpos, double * ratio, double * filtpos, int32_t * oversize,
 	int32_t * ideal, int64_t * first_out, int32_t * num_out, int32_t * wanted, int64_t * in_start )
 	{
-	const int64_t num_blocks = int64_t( plan.blocks.size() );
-	const int64_t fill = std::min<int64_t>( std::max<int64_t>( capacity, 0 ), num_blocks );
-	for( int64_t i = 0; i < fill; ++i )
-		{
-		const WtBlock & b = plan.blocks[size_t( i )];
-		if( offsets ) offsets[i] = b.offset;
-		if( fracpos ) fracpos[i] = b.fracpos;
-		if( ratio ) ratio[i] = b.ratio;
-		if( filtpos ) filtpos[i] = b.filtpos;
-		if( oversize ) oversize[i] = b.oversize;
-		if( ideal ) ideal[i] = b.ideal;
-		if( first_out ) first_out[i] = b.first_out;
-		if( num_out ) num_out[i] = b.num_out;
-		if( wanted ) wanted[i] = b.wanted;
-		if( in_start ) in_start[i] = b.in_start;
-		}
-	return num_blocks;
+	return wdl_export_plan( plan.blocks, int64_t( plan.blocks.size() ), capacity, offsets, fracpos, ratio, filtpos, oversize, ideal, first_out,
+		[&]( int64_t i, const WtBlock & b ) { if( num_out ) num_out[i] = b.num_out; if( wanted ) wanted[i] = b.wanted; if( in_start ) in_start[i] = b.in_start; } );
 	}
 
 // Audio::synthesize_spectrum's loop: one row of W = 2^p frames shared by the channels, channel c reading it from jump_c on

@@ -1,5 +1,5 @@
 // wdl_sinc.h -- WDL_Resampler's windowed-sinc mode (WDL/resample.cpp, SetMode( true, 0, true, TAPS )) as far as it does not depend on who
-// feeds it, written ONCE: repitch.hip uses it at 64 taps, spatial.hip (head_itd) at 32.  DESIGN.md section 4.13.
+// feeds it, written ONCE: repitch.hip and wavetable.hip use it at 64 taps, spatial.hip (head_itd) at 32.  DESIGN.md section 4.13.
 //
 // A caller's host plan reproduces the resampler's state block by block and hands every block a ( filtpos, oversize, ideal ) table
 // (wdl_table_shape) and a read position (wdl_hand_over).  On the device k_wdl_window leaves the Blackman-Harris factor of every table
@@ -8,6 +8,9 @@
 // Every sum runs in a fixed order, so two runs agree bit for bit.
 #pragma once
 #include "flanhip_internal.h"
+
+#include <algorithm>
+#include <vector>
 
 namespace flanhip {
 
@@ -66,6 +69,38 @@ inline int64_t wdl_hand_over( double srcpos, int64_t S, int ideal, int oversize,
 	return isrcpos;
 	}
 
+// the same columns for a *_plan entry point: each array nullable, filled up to `capacity`; extra( i, block ) adds the caller's own
+template<class Block, class Extra>
+inline int64_t wdl_export_plan( const std::vector<Block> & blocks, int64_t num_blocks, int64_t capacity, int64_t * offsets, double * fracpos, double * ratio,
+	double * filtpos, int32_t * oversize, int32_t * ideal, int64_t * first_out, Extra extra )
+	{
+	const int64_t fill = std::min<int64_t>( std::max<int64_t>( capacity, 0 ), num_blocks );
+	for( int64_t i = 0; i < fill; ++i )
+		{
+		const Block & b = blocks[size_t( i )];
+		if( offsets ) offsets[i] = b.offset;
+		if( fracpos ) fracpos[i] = b.fracpos;
+		if( ratio ) ratio[i] = b.ratio;
+		if( filtpos ) filtpos[i] = b.filtpos;
+		if( oversize ) oversize[i] = b.oversize;
+		if( ideal ) ideal[i] = b.ideal;
+		if( first_out ) first_out[i] = b.first_out;
+		extra( i, b );
+		}
+	return num_blocks;
+	}
+
+// runs are consecutive blocks that read one table
+template<class A, class B>
+inline bool wdl_same_table( const A & a, const B & b ) { return a.oversize == b.oversize && a.ideal == b.ideal && a.filtpos == b.filtpos; }
+
+// channels per workgroup: one where a run has work for every thread several times over, more where the table dominates
+inline int wdl_channels_per_group( int64_t outputs, size_t num_runs, int64_t ch )
+	{
+	const int64_t per_run = std::max<int64_t>( outputs / std::max<int64_t>( int64_t( num_runs ), 1 ), 1 );
+	return int( std::clamp<int64_t>( 512 / per_run, 1, ch ) );
+	}
+
 // the workspace of a call: the window factors, then the block records, then the run records
 struct WdlLayout { size_t win_off, block_off, run_off, total; };
 template<int TAPS>
@@ -105,6 +140,16 @@ __global__ __launch_bounds__( WDL_THREADS ) void k_wdl_window( double * __restri
 		const double windowpos = dwindowpos * xfrac;
 		w[e] = 0.35875 - 0.48829 * cos( windowpos ) + 0.14128 * cos( 2 * windowpos ) - 0.01168 * cos( 3 * windowpos );   // :1185
 		}
+	}
+
+// k_wdl_window for every oversize the runs use.  *d_win: where it leaves the factors.
+template<int TAPS, class Run>
+inline int wdl_window( const char * who, void * d_ws, const WdlLayout & l, const std::vector<Run> & runs, hipStream_t s, const double ** d_win )
+	{
+	*d_win = ws_at<double>( d_ws, l.win_off );
+	uint64_t used = 0;
+	for( const Run & r : runs ) used |= uint64_t( 1 ) << ( r.oversize - 1 );
+	return launch_kernel( who, k_wdl_window<TAPS>, WDL_MAX_OVERSIZE, WDL_THREADS, 0, s, ws_at<double>( d_ws, l.win_off ), used );
 	}
 
 // The table of one ( filtpos, oversize ) in LDS (BuildLowPass :1157-1202), by a whole workgroup of WDL_THREADS: window x sinc in fp64
