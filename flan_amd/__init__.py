@@ -230,6 +230,22 @@ _SIGS = {
     "flanhip_audio_synthesize_spectrum_workspace_bytes": (C.c_size_t, [_i32, _i32, _i64, _i64, _i64, _vp, _i64]),
     "flanhip_audio_synthesize_spectrum_dev": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "flanhip_audio_synthesize_spectrum": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "flanhip_loud_workspace_bytes": (C.c_size_t, [_i64, _i64]),
+    "flanhip_loud_summary_dev": (C.c_int, [_vp, _i64, _i64, _f32, _i64, _vp, _vp, _vp]),
+    "flanhip_loud_chunks_dev": (C.c_int, [_i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "flanhip_loud_chunks": (C.c_int, [_vp, _i64, _i64, _f32, _i64, _vp, _i64, _vp, _vp]),
+    "flanhip_loud_debug_run": (None, [_i32]),
+    "flanhip_loud_run_frames": (_i64, []),
+    "flanhip_loud_block_frames": (_i64, []),
+    "flanhip_loud_carry_pass_blocks": (_i64, []),
+    "flanhip_audio_reverse_dev": (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
+    "flanhip_audio_reverse": (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
+    "flanhip_loud_chunks_fades": (C.c_int, [_i64, _f32, _vp, _i64, _f32, _i32, _vp, _vp]),
+    "flanhip_edge_silence_cut": (C.c_int, [_i64, _f32, _i64, _i64, _f32, _vp]),
+    "flanhip_split_frames": (C.c_int, [_i64, _f32, _vp, _i64, _vp, _i64, _vp]),
+    "flanhip_rearrange_order": (C.c_int, [_i64, C.c_uint64, _vp]),
+    "flanhip_random_chunks_frames": (_i64, [_f32, _f32]),
+    "flanhip_random_chunks_plan": (C.c_int, [_i64, _f32, _f32, _vp, _f32, _vp, _f32, C.c_uint64, _vp, _vp, _vp, _i64, _vp]),
 }
 
 EXPORTS = sorted(_SIGS)
@@ -1705,3 +1721,120 @@ def audio_synthesize_spectrum_dev(d_mag, d_theta, spectrum_size_power, fundament
     f = np.ascontiguousarray(freq, np.float32).reshape(-1)
     check(lib.flanhip_audio_synthesize_spectrum_dev(_dp(d_mag), _dp(d_theta), spectrum_size_power, fundamental_power, ch, out_frames,
                                                     granularity_frames, _ptr(f), f.size, _dp(d_out), _dp(d_ws), _vp(stream or 0)))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Audio silence removal and slicing (flan_amd/csrc/temporal.hip): the loud-chunk scan, reverse and the host plans
+# ---------------------------------------------------------------------------------------------------------------
+
+def loud_workspace_bytes(ch, n):
+    return int(lib.flanhip_loud_workspace_bytes(ch, n))
+
+
+def loud_run_frames():
+    return int(lib.flanhip_loud_run_frames())
+
+
+def loud_block_frames():
+    return int(lib.flanhip_loud_block_frames())
+
+
+def loud_carry_pass_blocks():
+    return int(lib.flanhip_loud_carry_pass_blocks())
+
+
+class loud_run_forced:
+    """with loud_run_forced(frames): the detection's kernels give every lane `frames` frames (1 ... 64) -- a test hook"""
+
+    def __init__(self, frames):
+        self.frames = int(frames)
+
+    def __enter__(self):
+        lib.flanhip_loud_debug_run(self.frames)
+        return self
+
+    def __exit__(self, *exc):
+        lib.flanhip_loud_debug_run(0)
+        return False
+
+
+def loud_summary_dev(d_audio, ch, n, level, gap_frames, d_summary, d_ws, stream=None):
+    check(lib.flanhip_loud_summary_dev(_dp(d_audio), ch, n, level, gap_frames, _dp(d_summary), _dp(d_ws), _vp(stream or 0)))
+
+
+def loud_chunks_dev(ch, n, gap_frames, count, d_chunks, capacity, d_ws, stream=None):
+    check(lib.flanhip_loud_chunks_dev(ch, n, gap_frames, count, _dp(d_chunks), capacity, _dp(d_ws), _vp(stream or 0)))
+
+
+def loud_chunks(audio, level, gap_frames, cancel=None):
+    """get_loud_chunks_base's chunk frames: audio float32 [ch][n] -> ( int32 [count][2], summary int64[4] )"""
+    audio = np.ascontiguousarray(audio, np.float32)
+    ch, n = audio.shape
+    cancel_p = None if cancel is None else C.cast(C.byref(cancel), _vp)
+    summary = np.full(4, -7, np.int64)
+    bound = n if gap_frames < 0 else (n - 1) // (gap_frames + 2) + 1      # one call: a table no count exceeds (chunk starts lie gap + 2 apart)
+    chunks = np.full((bound, 2), -7, np.int32)
+    check(lib.flanhip_loud_chunks(_ptr(audio), ch, n, level, gap_frames, _ptr(chunks), bound, _ptr(summary), cancel_p))
+    assert np.all(chunks[int(summary[0]):] == -7)
+    return chunks[:int(summary[0])].copy(), summary
+
+
+def audio_reverse(audio, cancel=None):
+    audio = np.ascontiguousarray(audio, np.float32)
+    ch, n = audio.shape
+    out = np.full((ch, n), np.nan, np.float32)
+    check(lib.flanhip_audio_reverse(_ptr(audio), ch, n, _ptr(out), None if cancel is None else C.cast(C.byref(cancel), _vp)))
+    return out
+
+
+def audio_reverse_dev(d_audio, ch, n, d_out, stream=None):
+    check(lib.flanhip_audio_reverse_dev(_dp(d_audio), ch, n, _dp(d_out), _vp(stream or 0)))
+
+
+def loud_chunks_fades(num_frames, sample_rate, chunks, fade_in_time, join=False):
+    """( events, offsets ) of get_loud_chunks_base's cuts; join: the events' o as remove_silence places them"""
+    chunks = np.ascontiguousarray(chunks, np.int32).reshape(-1, 2)
+    events = np.zeros(chunks.shape[0], GRAIN_EVENT)
+    events["gain_offset"], events["gain"] = -1, 1.0
+    offsets = np.full(chunks.shape[0] + 1, np.nan, np.float32)
+    check(lib.flanhip_loud_chunks_fades(num_frames, sample_rate, _ptr(chunks), chunks.shape[0], fade_in_time, 1 if join else 0, _ptr(events), _ptr(offsets)))
+    return events, offsets
+
+
+def edge_silence_cut(num_frames, sample_rate, first_noisy, last_noisy, fade_time):
+    out = np.zeros(4, np.int32)
+    check(lib.flanhip_edge_silence_cut(num_frames, sample_rate, first_noisy, last_noisy, fade_time, _ptr(out)))
+    return tuple(int(v) for v in out)
+
+
+def split_frames(num_frames, sample_rate, times):
+    times = np.ascontiguousarray(times, np.float32).reshape(-1)
+    out = np.zeros(times.size + 2, np.int32)
+    count = _i64(0)
+    check(lib.flanhip_split_frames(num_frames, sample_rate, _ptr(times), times.size, _ptr(out), out.size, C.cast(C.byref(count), _vp)))
+    return out[:count.value].copy()
+
+
+def rearrange_order(count, seed):
+    out = np.zeros(max(count, 0), np.int32)
+    check(lib.flanhip_rearrange_order(count, seed, _ptr(out)))
+    return out
+
+
+def random_chunks_frames(sample_rate, length):
+    return int(lib.flanhip_random_chunks_frames(sample_rate, length))
+
+
+def random_chunks_plan(num_frames, sample_rate, length, chunk_length, fade, seed):
+    """( events, chunk_starts, offsets ); chunk_length: a number or random_chunks_frames() floats, fade: a number or one float more"""
+    frames = random_chunks_frames(sample_rate, length)
+    _c, cp, cs = _curve(chunk_length, frames)
+    _f, fp, fs = _curve(fade, frames + 1)
+    count = _i64(0)
+    check(lib.flanhip_random_chunks_plan(num_frames, sample_rate, length, cp, cs, fp, fs, seed, None, None, None, 0, C.cast(C.byref(count), _vp)))
+    events = np.zeros(count.value, GRAIN_EVENT)
+    events["gain_offset"], events["gain"] = -1, 1.0
+    starts, offsets = np.zeros(count.value, np.int32), np.zeros(count.value + 1, np.float32)
+    check(lib.flanhip_random_chunks_plan(num_frames, sample_rate, length, cp, cs, fp, fs, seed, _ptr(events), _ptr(starts), _ptr(offsets), count.value,
+                                         C.cast(C.byref(count), _vp)))
+    return events, starts, offsets

@@ -2,7 +2,7 @@
 // (reference: src/flan/Audio/AudioConstructors.cpp, Conversions/AudioPV.cpp:12-84, Audio/AudioConversions.cpp:14-56,
 // Audio/AudioCombination.cpp:299-352, Audio/AudioTemporal.cpp:236-299, Audio/AudioVolume.cpp:5-67, 190-278,
 // Audio/AudioFilter.cpp:280-758, 988-1263, Audio/AudioConversions.cpp:58-104, Audio/AudioChannels.cpp, Audio/AudioSpatial.cpp,
-// Audio/AudioInformation.cpp:138-304, 388-407, Audio/AudioCombination.cpp:78-237, Audio/AudioTemporal.cpp:190-234,
+// Audio/AudioInformation.cpp:138-304, 388-407, Audio/AudioCombination.cpp:78-237, Audio/AudioTemporal.cpp:10-234, 301-546,
 // Audio/AudioSynthesis.cpp:310-473, 572-638).
 #include "flan/Audio.h"
 
@@ -994,14 +994,14 @@ bool whole_event( const Audio & a, flanhip_grain_event & e )
 	return point_at( a, e );
 	}
 
-// The sink: the table's length (AudioCombination.cpp:146-150) and plan on the host, then one launch.  Nothing to hear -- no frames, or no event
+// The sink: the table's length (AudioCombination.cpp:146-150), or the caller's, and plan on the host, then one launch.  Nothing to hear -- no frames, or no event
 // with any -- is the reference's null Audio
-Audio mix_events( const char * who, const EventTable & table, Channel channels, FrameRate sample_rate )
+Audio mix_events( const char * who, const EventTable & table, Channel channels, FrameRate sample_rate, int64_t out_frames = 0 )
 	{
 	const int64_t count = int64_t( table.events.size() );
 	bool live = false;
 	for( const flanhip_grain_event & e : table.events ) live = live || ( e.n > 0 && e.channels > 0 );
-	int64_t frames = 0;
+	int64_t frames = std::max<int64_t>( out_frames, 0 );                           // 0: the table's own length; else the caller's (events are clipped to it)
 	if( !live || channels < 1 || flanhip_grains_plan( table.events.data(), count, &frames, nullptr, nullptr, 0 ) != FLANHIP_OK ) return Audio::create_null();
 	if( frames < 1 || frames > INT_MAX )
 		{
@@ -1329,6 +1329,361 @@ Audio Audio::psola( Second length, const Function<Second, Second> & time_selecti
 	if( flanhip_grains_events( sampled_frames, sr, rate.data(), 0.0f, nullptr, 0.0f, 0, frames.data(), sampled_frames, &count ) != FLANHIP_OK ) return Audio::create_null();
 	frames.resize( static_cast<size_t>( count ) );
 	return granulate_sampled( *this, frames, sampled_frames, SampledCurve{ &picked, 0.0f }, SampledCurve{ &lengths, 0.0f }, SampledCurve{ nullptr, 0.05f }, mod, true );
+	}
+
+// ---- silence removal and slicing (Audio/AudioTemporal.cpp:10-188, 301-546) ----------------------------------------------------
+namespace {
+
+// The detection on the device: the summary { count, first, last, 0 } and, if wanted, the chunk table
+struct LoudScan
+	{
+	bool ok = false;
+	int64_t summary[4] = { 0, -1, -1, 0 };
+	std::vector<int32_t> chunks;                                               // [count][2]
+	};
+
+LoudScan loud_scan( const Audio & me, Amplitude level, Frame gap, bool want_table, const char * who )
+	{
+	LoudScan r;
+	const int64_t ch = me.get_num_channels(), n = me.get_num_frames();
+	const size_t ws_bytes = flanhip_loud_workspace_bytes( ch, n );
+	if( ws_bytes == 0 )
+		{
+		std::cerr << "flan: " << who << " refused the shape: " << ch << " x " << n << std::endl;
+		return r;
+		}
+	const float * d_x = me.device_data();
+	if( !d_x ) return r;
+	DeviceCall call( who );
+	int64_t * d_summary = static_cast<int64_t*>( call.scratch( sizeof( r.summary ) ) );
+	void * ws = call.workspace( ws_bytes );
+	if( !call.ok() || !call.launch( flanhip_loud_summary_dev( d_x, ch, n, level, gap, d_summary, ws, nullptr ) ) || !call.sync() ) return r;
+	if( !detail::download_to_host( r.summary, d_summary, sizeof( r.summary ) ) )      // the one read-back: the count sizes the table
+		{
+		std::cerr << "flan: " << who << ": download failed: " << flanhip_last_error() << std::endl;
+		return r;
+		}
+	const int64_t count = r.summary[0];
+	if( want_table && count > 0 )
+		{
+		r.chunks.resize( size_t( count ) * 2 );
+		DeviceCall table( who );                                               // declared after `call`: its blocks go first, the workspace outlives the launch
+		int32_t * d_chunks = static_cast<int32_t*>( table.scratch( sizeof( int32_t ) * r.chunks.size() ) );
+		if( !table.ok() || !table.launch( flanhip_loud_chunks_dev( ch, n, gap, count, d_chunks, count, ws, nullptr ) ) || !table.sync() ) return r;
+		if( !detail::download_to_host( r.chunks.data(), d_chunks, sizeof( int32_t ) * r.chunks.size() ) )
+			{
+			std::cerr << "flan: " << who << ": download failed: " << flanhip_last_error() << std::endl;
+			return r;
+			}
+		}
+	r.ok = true;
+	return r;
+	}
+
+// get_loud_chunks_base (:10-86) up to its cuts: the chunks of `me` as events over `me` itself (join: placed as remove_silence joins them) and the
+// offsets -2 * fade_ins[i].  false: nothing to return -- a null *this, nothing noisy, or a failure that has been reported
+bool loud_events( const Audio & me, Amplitude level, Second minimum_gap, Second fade_in_time, bool join, EventTable & table, std::vector<Second> & offsets,
+	const char * who )
+	{
+	if( me.is_null() ) return false;
+	Frame gap = 0;
+	if( !frame_of( minimum_gap, me.get_sample_rate(), gap ) )                  // :17
+		{
+		std::cerr << "flan: " << who << ": a minimum gap no frame holds" << std::endl;
+		return false;
+		}
+	const LoudScan scan = loud_scan( me, level, gap, true, who );
+	if( !scan.ok || scan.summary[0] == 0 ) return false;                       // :50
+	const int64_t count = scan.summary[0];
+	table.events.assign( size_t( count ), plain_event() );
+	offsets.assign( size_t( count ) + 1, 0.0f );
+	if( flanhip_loud_chunks_fades( me.get_num_frames(), me.get_sample_rate(), scan.chunks.data(), count, fade_in_time, join ? 1 : 0, table.events.data(),
+			offsets.data() ) != FLANHIP_OK )
+		{
+		std::cerr << "flan: " << who << ": " << flanhip_last_error() << std::endl;
+		return false;
+		}
+	for( flanhip_grain_event & e : table.events ) if( !point_at( me, e ) ) return false;
+	return true;
+	}
+
+// every event of a table mixed alone from frame 0: cut_frames with its fades, the way granulate_sampled's general path makes a grain.  An empty
+// event is a null Audio
+std::vector<Audio> materialised( const char * who, const EventTable & table, Channel channels, FrameRate sample_rate )
+	{
+	std::vector<Audio> out;
+	out.reserve( table.events.size() );
+	for( flanhip_grain_event e : table.events )
+		{
+		e.o = 0;
+		EventTable one;
+		one.events.push_back( e );
+		out.emplace_back( e.n > 0 ? mix_events( who, one, channels, sample_rate ) : Audio() );
+		}
+	return out;
+	}
+
+// Audio::join's places (AudioCombination.cpp:212-218, then mix's time_to_frame, :127-129) for events that are whole inputs of n frames
+bool place_joined( EventTable & table, const std::vector<Second> & offsets, FrameRate sample_rate )
+	{
+	Second start_time = 0;
+	for( size_t i = 0; i < table.events.size(); ++i )
+		{
+		Frame o = 0;
+		if( !frame_of( start_time, sample_rate, o ) ) return false;
+		table.events[i].o = o;
+		start_time = start_time + table.events[i].n / sample_rate + offsets[i + 1];
+		}
+	return true;
+	}
+
+// split_at_times' frames (:416-429) through the C ABI; empty on a refusal, which is reported
+std::vector<int32_t> split_frames_of( const Audio & me, const std::vector<Second> & times, const char * who )
+	{
+	std::vector<int32_t> frames( times.size() + 2 );
+	int64_t count = 0;
+	if( flanhip_split_frames( me.get_num_frames(), me.get_sample_rate(), times.data(), int64_t( times.size() ), frames.data(), int64_t( frames.size() ), &count ) != FLANHIP_OK )
+		{
+		std::cerr << "flan: " << who << ": " << flanhip_last_error() << std::endl;
+		return {};
+		}
+	frames.resize( size_t( count ) );
+	return frames;
+	}
+
+// split_with_lengths' times (:445-449) and split_with_equal_lengths' lengths (:458-459); false for a count no vector should hold
+void lengths_to_times( std::vector<Second> & lengths )
+	{
+	for( Second & t : lengths ) if( t < 0 ) t = 0;
+	for( size_t i = 1; i < lengths.size(); ++i ) lengths[i] = lengths[i - 1] + lengths[i];      // std::partial_sum in fp32
+	}
+bool equal_lengths( const Audio & me, Second slice_length, std::vector<Second> & lengths, const char * who )
+	{
+	const float count = std::ceil( me.get_length() / slice_length );
+	if( !( count < float( 1 << 28 ) ) )
+		{
+		std::cerr << "flan: " << who << ": " << count << " slices" << std::endl;
+		return false;
+		}
+	lengths.assign( size_t( std::max( count, 0.0f ) ), slice_length );
+	return true;
+	}
+
+} // namespace
+
+uint64_t Audio::random_seed() { return std::random_device()(); }
+
+Audio Audio::modify_boundaries_frames( Frame start, Frame end ) const
+	{
+	if( is_null() ) return Audio::create_null();                                   // :101
+	const int64_t out_frames = -int64_t( start ) + get_num_frames() + int64_t( end );      // :103
+	if( out_frames <= 0 ) return Audio::create_null();
+	if( out_frames > INT_MAX )
+		{
+		std::cerr << "flan: modify_boundaries: an output of " << out_frames << " frames" << std::endl;
+		return Audio::create_null();
+		}
+	EventTable table;
+	table.events.push_back( plain_event() );
+	Frame o = 0;
+	if( !frame_of( -frame_to_time( fFrame( start ) ), get_sample_rate(), o ) || !whole_event( *this, table.events[0] ) ) return Audio::create_null();      // :111
+	table.events[0].o = o;
+	return mix_events( "modify_boundaries", table, get_num_channels(), get_sample_rate(), out_frames );
+	}
+
+Audio Audio::modify_boundaries( Second start, Second end ) const
+	{
+	if( is_null() ) return Audio::create_null();
+	Frame s = 0, e = 0;
+	if( !frame_of( start, get_sample_rate(), s ) || !frame_of( end, get_sample_rate(), e ) ) return Audio::create_null();      // :121
+	return modify_boundaries_frames( s, e );
+	}
+
+Audio Audio::remove_edge_silence( Amplitude non_silent_level, Second fade_time ) const
+	{
+	if( is_null() ) return Audio::create_null();
+	const LoudScan scan = loud_scan( *this, non_silent_level, 0, false, "remove_edge_silence" );      // :129-147: the summary's first and last
+	if( !scan.ok ) return Audio::create_null();
+	int32_t cut[4];
+	if( flanhip_edge_silence_cut( get_num_frames(), get_sample_rate(), scan.summary[1], scan.summary[2], fade_time, cut ) != FLANHIP_OK )
+		{
+		std::cerr << "flan: remove_edge_silence: " << flanhip_last_error() << std::endl;
+		return Audio::create_null();
+		}
+	return cut_frames( cut[0], cut[1], cut[2], cut[3] );                          // :152
+	}
+
+std::vector<Audio> Audio::get_loud_chunks( Amplitude non_silent_level, Second minimum_gap, Second fade_in_time ) const
+	{
+	EventTable table;
+	std::vector<Second> offsets;
+	if( !loud_events( *this, non_silent_level, minimum_gap, fade_in_time, false, table, offsets, "get_loud_chunks" ) ) return {};
+	return materialised( "get_loud_chunks", table, get_num_channels(), get_sample_rate() );
+	}
+
+Audio Audio::remove_silence( Amplitude non_silent_level, Second minimum_gap, Second fade_in_time ) const
+	{
+	EventTable table;
+	std::vector<Second> offsets;
+	if( !loud_events( *this, non_silent_level, minimum_gap, fade_in_time, true, table, offsets, "remove_silence" ) ) return Audio::create_null();
+	return mix_events( "remove_silence", table, get_num_channels(), get_sample_rate() );
+	}
+
+Audio Audio::remove_silence_unfused( Amplitude non_silent_level, Second minimum_gap, Second fade_in_time ) const
+	{
+	EventTable table;
+	std::vector<Second> offsets;
+	if( !loud_events( *this, non_silent_level, minimum_gap, fade_in_time, false, table, offsets, "remove_silence" ) ) return Audio::create_null();
+	const std::vector<Audio> chunks = materialised( "remove_silence", table, get_num_channels(), get_sample_rate() );
+	return Audio::join( pointers_to( chunks ), offsets );                          // :170-171
+	}
+
+Audio Audio::reverse() const
+	{
+	if( is_null() ) return Audio::create_null();                                   // :177
+	const float * d_x = device_data();
+	if( !d_x ) return Audio::create_null();
+	return audio_call( "reverse", get_format(), true, detail::kNoWorkspace, [&]( float * out, void * )
+		{ return flanhip_audio_reverse_dev( d_x, get_num_channels(), get_num_frames(), out, nullptr ); } );
+	}
+
+Audio Audio::iterate( int32_t num_iterations, Second crossfade_time, const AudioMod & mod, bool feedback ) const
+	{
+	if( is_null() ) return Audio::create_null();                                   // :308-309
+	if( num_iterations < 1 ) return Audio::create_null();
+	if( mod.is_null() ) return Audio::join( std::vector<const Audio *>( size_t( num_iterations ), this ), -crossfade_time );      // :312-313
+	std::vector<Audio> modified;                                                   // :316-321, on the calling thread in order
+	modified.reserve( size_t( num_iterations ) );
+	for( int32_t i = 0; i < num_iterations; ++i )
+		{
+		Audio input = i > 0 && feedback ? modified.back().copy() : copy();
+		mod( input, i * get_length() );
+		modified.emplace_back( std::move( input ) );
+		}
+	return Audio::join( modified, -crossfade_time );                               // :323
+	}
+
+Audio Audio::delay( Second added_length, const Function<Second, Second> & delay_time, const Function<Second, float> & decay, const AudioMod & mod ) const
+	{
+	if( is_null() ) return Audio::create_null();                                   // :333
+	added_length = std::max( 0.0f, added_length );                                 // :335-336
+	const Second length = get_length() + added_length;
+	Frame frames = 0;
+	if( !frame_of( length, get_sample_rate(), frames ) || frames < 1 ) return Audio::create_null();
+	const auto delay_time_sampled = delay_time.sample( 0, frames, frame_to_time( 1 ) );      // :338-339
+	const auto decay_sampled = decay.sample( 0, frames, frame_to_time( 1 ) );
+	const FrameRate sr = get_sample_rate();
+	const auto at = [frames, sr]( const auto & sampled, Second t )                // sampled[ time_to_frame( t ) ], held inside the samples
+		{
+		if( sampled.is_constant() ) return sampled.get_constant();
+		Frame f = 0;
+		if( !frame_of( t, sr, f ) ) f = 0;
+		return sampled.get_vector()[size_t( std::clamp( f, 0, frames - 1 ) )];
+		};
+	const Function<Second, float> events_per_second( [&]( Second t )                // :341-346
+		{
+		const Second delay_time_c = at( delay_time_sampled, t );
+		if( delay_time_c <= 0 ) return 1.0f / float( sr );
+		return 1.0f / delay_time_c;
+		} );
+	const AudioMod delay_mod( [&]( Audio & in, Second t )                          // :348-358
+		{
+		if( t == 0 ) return;
+		if( !mod.is_null() ) mod( in, t );
+		in.modify_volume_in_place( at( decay_sampled, t ) );                       // one fp32 product per sample by a constant
+		} );
+	return texture( length, events_per_second, 0, delay_mod, true );                 // :360
+	}
+
+std::vector<Audio> Audio::split_at_times( std::vector<Second> split_times, Second fade ) const
+	{
+	if( is_null() ) return {};                                                     // :414
+	Frame fade_frames = 0;
+	if( !frame_of( fade, get_sample_rate(), fade_frames ) ) return {};             // :416
+	const std::vector<int32_t> frames = split_frames_of( *this, split_times, "split_at_times" );
+	std::vector<Audio> outs;
+	for( size_t i = 0; i + 1 < frames.size(); ++i ) outs.emplace_back( cut_frames( frames[i], frames[i + 1], fade_frames, fade_frames ) );      // :434
+	return outs;
+	}
+
+std::vector<Audio> Audio::split_with_lengths( std::vector<Second> split_lengths, Second fade ) const
+	{
+	lengths_to_times( split_lengths );                                             // :445-449
+	return split_at_times( std::move( split_lengths ), fade );
+	}
+
+std::vector<Audio> Audio::split_with_equal_lengths( Second slice_length, Second fade ) const
+	{
+	if( is_null() || !( slice_length > 0 ) ) return {};                            // :458
+	std::vector<Second> lengths;
+	if( !equal_lengths( *this, slice_length, lengths, "split_with_equal_lengths" ) ) return {};
+	return split_with_lengths( std::move( lengths ), fade );
+	}
+
+Audio Audio::rearrange( Second slice_length, Second fade, uint64_t seed ) const
+	{
+	if( is_null() ) return Audio::create_null();                                   // :468
+	Frame fade_frames = 0;
+	std::vector<Second> times;
+	if( !( slice_length + fade > 0 ) || !frame_of( fade, get_sample_rate(), fade_frames ) || !equal_lengths( *this, slice_length + fade, times, "rearrange" ) )
+		return Audio::create_null();                                               // :471: split_with_equal_lengths( slice_length + fade, fade )
+	lengths_to_times( times );
+	const std::vector<int32_t> frames = split_frames_of( *this, times, "rearrange" );
+	if( frames.size() < 3 ) return Audio::create_null();                           // :472-473: fewer than 2 pieces
+	const size_t count = frames.size() - 2;                                        // :475: without the last piece
+	std::vector<int32_t> order( count ), start( count ), end( count ), fades( count, fade_frames );
+	if( flanhip_rearrange_order( int64_t( count ), seed, order.data() ) != FLANHIP_OK ) return Audio::create_null();
+	for( size_t i = 0; i < count; ++i ) { start[i] = frames[size_t( order[i] )]; end[i] = frames[size_t( order[i] ) + 1]; }
+	EventTable table;
+	table.events.assign( count, plain_event() );
+	if( flanhip_grains_cut_frames( get_num_frames(), int64_t( count ), start.data(), end.data(), fades.data(), fades.data(), table.events.data() ) != FLANHIP_OK
+		|| !place_joined( table, std::vector<Second>( count + 1, -fade ), get_sample_rate() ) ) return Audio::create_null();      // :481
+	for( flanhip_grain_event & e : table.events ) if( !point_at( *this, e ) ) return Audio::create_null();
+	return mix_events( "rearrange", table, get_num_channels(), get_sample_rate() );
+	}
+
+Audio Audio::random_chunks( Second length, const Function<Second, Second> & chunk_length, const Function<Second, Second> & fade, const AudioMod & mod,
+	uint64_t seed ) const
+	{
+	if( is_null() || !( length > 0 ) ) return Audio::create_null();                // :491
+	const FrameRate sr = get_sample_rate();
+	const int64_t loop_frames = flanhip_random_chunks_frames( sr, length );
+	if( loop_frames < 1 || loop_frames >= INT_MAX ) return Audio::create_null();
+	std::vector<float> lengths, fades;                                             // the Functions at frame_to_time( f ) (:505, :519)
+	if( !chunk_length.is_constant() )
+		{
+		lengths.resize( size_t( loop_frames ) );
+		detail::for_each_index( 0, int( loop_frames ), chunk_length.get_execution_policy(), [&]( int f ){ lengths[size_t( f )] = chunk_length( frame_to_time( fFrame( f ) ) ); } );
+		}
+	if( !fade.is_constant() )
+		{
+		fades.resize( size_t( loop_frames ) + 1 );
+		detail::for_each_index( 0, int( loop_frames ) + 1, fade.get_execution_policy(), [&]( int f ){ fades[size_t( f )] = fade( frame_to_time( fFrame( f ) ) ); } );
+		}
+	const float * lp = lengths.empty() ? nullptr : lengths.data(), * fp = fades.empty() ? nullptr : fades.data();
+	const float ls = chunk_length.is_constant() ? chunk_length.get_constant() : 0.0f, fs = fade.is_constant() ? fade.get_constant() : 0.0f;
+	int64_t count = 0;
+	EventTable table;
+	std::vector<int32_t> starts;
+	std::vector<Second> offsets;
+	bool planned = flanhip_random_chunks_plan( get_num_frames(), sr, length, lp, ls, fp, fs, seed, nullptr, nullptr, nullptr, 0, &count ) == FLANHIP_OK;
+	if( planned )
+		{
+		table.events.assign( size_t( count ), plain_event() );
+		starts.resize( size_t( count ) );
+		offsets.resize( size_t( count ) + 1 );
+		planned = flanhip_random_chunks_plan( get_num_frames(), sr, length, lp, ls, fp, fs, seed, table.events.data(), starts.data(), offsets.data(), count, &count ) == FLANHIP_OK;
+		}
+	if( !planned )
+		{
+		std::cerr << "flan: random_chunks: " << flanhip_last_error() << std::endl;
+		return Audio::create_null();
+		}
+	for( flanhip_grain_event & e : table.events ) if( !point_at( *this, e ) ) return Audio::create_null();
+	if( mod.is_null() ) return mix_events( "random_chunks", table, get_num_channels(), sr );       // fused: every chunk read from *this in the mix
+	std::vector<Audio> chunks = materialised( "random_chunks", table, get_num_channels(), sr );   // :529-539
+	for( size_t i = 0; i < chunks.size(); ++i ) mod( chunks[i], frame_to_time( fFrame( starts[i] ) ) );
+	return Audio::join( pointers_to( chunks ), offsets );                          // :545
 	}
 
 // Audio/AudioSynthesis.cpp:151-268.  The spectrum's magnitudes and phases and the frequency curve are made here; the table (one inverse real FFT

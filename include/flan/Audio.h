@@ -279,8 +279,7 @@ public:
 	// Everything below ends in one kernel (flanhip_grains_mix_dev): an output sample is the fp32 sum, in the order of the inputs,
 	// of the inputs that cover it, bit for bit what the reference's loop over its inputs computes (Audio/AudioCombination.cpp:155-167); grains are
 	// cut, faded and windowed while they are read and never written anywhere.  Results stay device-resident until read.  Not offered: select,
-	// fade / fade_frames and their in-place forms as public methods, mix_in_place, texture_effect, synthesize_trainlets, synthesize_impulse,
-	// modify_boundaries.
+	// fade / fade_frames and their in-place forms as public methods, mix_in_place, texture_effect, synthesize_trainlets, synthesize_impulse.
 	/** The frames between two times, with square-root fades at either end (Audio/AudioTemporal.cpp:190-234, Audio/AudioVolume.cpp:102-135): times
 	 *  become frames by truncation; end <= start gives a null Audio, checked before start and end are clamped to [0, frames - 1] -- so the last
 	 *  frame is never part of a cut --; fades are clamped at 0 and, where together they are longer than the cut, both scaled down and floored.  A
@@ -355,6 +354,61 @@ public:
 		const Function<Frequency, Amplitude> & peak_distribution = []( Frequency x ){ return 1.0f / std::sqrt( pi2 ) * std::exp( -0.5f * std::pow( x, 2.0f ) ); },
 		int fundamental_power = 8, int spectrum_size_power = 20, Channel num_channels = 2, Second granularity = 0.001f,
 		const std::vector<Radian> * phases = nullptr );
+
+	// ---- silence removal and slicing (Audio/AudioTemporal.cpp:10-188, 301-546) ----
+	// The loud chunks are found by one scan on the device (flanhip_loud_summary_dev, flanhip_loud_chunks_dev); the fades, splits and plans are
+	// host arithmetic behind the C ABI; everything ends in the mixing kernel above, so without the Hann flag results are the reference's bit for
+	// bit.  Not offered: texture_effect, select, the public fade* family, mix_in_place, and the commented-out stereo_delay.
+	/** What std::random_device gives: the default seed of rearrange and random_chunks, as the reference seeds its engines (:477, :522). */
+	static uint64_t random_seed();
+	/** *this with -start frames of silence put before it and end frames after it; negative amounts cut (:96-114 over mix_in_place,
+	 *  AudioCombination.cpp:181-203): one event into a cleared output of -start + frames + end frames, placed at
+	 *  Frame( time_to_frame( -frame_to_time( start ) ) ), the fp32 round trip included.  (The reference adds the float time_to_frame( start time )
+	 *  to every source frame before it truncates, which lands elsewhere only where that round trip is inexact and start > 0.)  A result of
+	 *  <= 0 frames and a null *this give a null Audio. */
+	Audio modify_boundaries_frames( Frame start, Frame end ) const;
+	Audio modify_boundaries( Second start, Second end ) const;
+	/** The cut from the first to the last frame with a sample above non_silent_level in any channel, widened by fade_time on either side where
+	 *  the signal has room and faded over it (:124-153).  The compare is signed, and false for a NaN.  The two frames come from the device's
+	 *  summary.  Nothing noisy cuts from the last frame to frame 0: a null Audio unless the fade reaches over. */
+	Audio remove_edge_silence( Amplitude non_silent_level, Second fade_time = 0 ) const;
+	/** The stretches where some channel is above non_silent_level, each closed by more than minimum_gap of quiet, each widened by fade_in_time
+	 *  and faded, with the reference's fade arithmetic and its quirks (:10-86, flanhip_loud_chunks_fades): a chunk that reaches the end loses its last
+	 *  frame to cut_frames' clamp.  Every chunk is cut on the device.  A chunk that cuts to nothing -- one noisy frame and no fade -- is a null
+	 *  Audio in the vector.  Nothing noisy, and a null *this, give an empty vector. */
+	std::vector<Audio> get_loud_chunks( Amplitude non_silent_level, Second minimum_gap, Second fade_in_time = 0 ) const;
+	/** join( get_loud_chunks( ... ), offsets -2 fade ) (:164-172) as ONE launch over *this: the scan, the fades plan, then one event per chunk read
+	 *  from *this directly; no chunk is written.  A chunk that cuts to nothing is an empty event: it adds nothing and counts with its place for
+	 *  the length alone, which is what mix does with a null Audio among its inputs.  remove_silence_unfused is the general path -- the chunks
+	 *  made, then joined -- and gives the same bits. */
+	Audio remove_silence( Amplitude non_silent_level, Second minimum_gap, Second fade_in_time = 0 ) const;
+	Audio remove_silence_unfused( Amplitude non_silent_level, Second minimum_gap, Second fade_in_time = 0 ) const;
+	/** out[c][f] = in[c][frames - 1 - f] (:174-188), on the device. */
+	Audio reverse() const;
+	/** *this num_iterations times, tip to tail with crossfade_time of overlap (:301-324).  Without a mod nothing is copied: every event reads
+	 *  *this.  With one, iteration i is a copy gone through mod( copy, i * get_length() ), made from iteration i - 1's result under feedback; the mod
+	 *  runs on the calling thread in order.  num_iterations < 1 gives a null Audio. */
+	Audio iterate( int32_t num_iterations, Second crossfade_time = 0, const AudioMod & mod = AudioMod(), bool feedback = false ) const;
+	/** A decaying echo (:326-361): texture( length + added_length, 1 / delay_time, 0, delay_mod, true ), where delay_mod leaves the event at
+	 *  time 0 alone and gives every later one the user's mod and then one fp32 product per sample by decay at the event's time.  Both Functions are
+	 *  sampled over the frames of the length at f * frame_to_time( 1 ); delay_time <= 0 gives a rate of 1 / sample rate. */
+	Audio delay( Second added_length, const Function<Second, Second> & delay_time, const Function<Second, float> & decay = .5f, const AudioMod & mod = AudioMod() ) const;
+	/** The pieces between the sorted split times, each cut_frames with `fade` at both ends (:409-438, flanhip_split_frames): times at or before
+	 *  frame 0 are skipped and the first at or beyond the end stops the list.  split_with_lengths: the times are the fp32 running sum of the
+	 *  lengths, negative ones counting as 0 (:440-451).  split_with_equal_lengths: ceil( length / slice_length ) equal lengths (:453-461);
+	 *  slice_length <= 0 gives an empty vector.  Every piece loses the frame at frames - 1 if it reaches it (cut_frames' clamp). */
+	std::vector<Audio> split_at_times( std::vector<Second> split_times, Second fade = 0 ) const;
+	std::vector<Audio> split_with_lengths( std::vector<Second> split_lengths, Second fade = 0 ) const;
+	std::vector<Audio> split_with_equal_lengths( Second slice_length, Second fade = 0 ) const;
+	/** split_with_equal_lengths( slice_length + fade, fade ) without its last piece, in a random order, joined with -fade (:463-482), as one event
+	 *  table over *this.  The order is flanhip_rearrange_order( pieces, seed ) -- a Fisher-Yates over std::mt19937 the library defines, where the
+	 *  reference's std::shuffle is the standard library's own --, so a seed names one result.  Fewer than 2 pieces give a null Audio. */
+	Audio rearrange( Second slice_length, Second fade = 0, uint64_t seed = random_seed() ) const;
+	/** Chunks of *this from random places, chunk_length( t ) long, crossfaded over fade( t ), for `length` seconds (:484-546,
+	 *  flanhip_random_chunks_plan).  Without a mod it is one event table over *this; with one every chunk is cut into an Audio, handed to
+	 *  mod( chunk, its start time ) on the calling thread in order, and the results are joined.  The places come from std::mt19937( seed ). */
+	Audio random_chunks( Second length, const Function<Second, Second> & chunk_length, const Function<Second, Second> & fade = 0,
+		const AudioMod & mod = AudioMod(), uint64_t seed = random_seed() ) const;
 
 	// the older camelCase spellings BASELINE.json's north_star uses
 	PV convertToPV( Frame window_size = 2048, Frame hop = 128, Frame dft_size = 4096, flan_CANCEL_ARG ) const;

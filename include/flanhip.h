@@ -1020,6 +1020,77 @@ int flanhip_grains_mix_dev(const flanhip_grain_event * events, int64_t count, co
 int flanhip_grains_mix(const flanhip_grain_event * events, int64_t count, const float * gains, int64_t gain_floats, const float * sources,
                        int64_t sources_floats, int64_t num_channels, int64_t out_frames, float sample_rate, float * out, volatile int * cancel);
 
+/* ---- Audio silence removal and slicing: get_loud_chunks, remove_silence, remove_edge_silence, reverse, the splits, rearrange, random_chunks
+ * (Audio/AudioTemporal.cpp:10-188, 409-546) (flan_amd/csrc/temporal.hip) ------------------------------------------------ */
+/* The loud chunks of get_loud_chunks_base (AudioTemporal.cpp:20-48).  Frame f is NOISY when sample( c, f ) > level for some channel c: a
+ * signed compare (a loud negative sample is not noisy), false for a NaN.  A chunk starts at a noisy frame met in a quiet sector and is closed
+ * by the first frame more than gap_frames after the last noisy one, with that last noisy frame as its end (:41-45); a chunk still open after
+ * the last frame ends at num_frames (:47-48).  A negative gap makes every noisy frame a chunk { f, f }.  On the device the loop is a scan of
+ * maps ( first, last, inner chunk starts ) over runs of frames: results do not depend on the run.
+ * summary: int64[4] = { chunk count, first noisy frame, last noisy frame, 0 }, the frames -1 when nothing is noisy.
+ * chunks: int32[count][2] = { start, end }.
+ * flanhip_loud_summary_dev launches the detection and leaves the summary; flanhip_loud_chunks_dev, on the same workspace and with the same
+ * num_channels, num_frames and gap_frames, writes the table: `count` is what the caller read from the summary and the kernel's own limit --
+ * nothing is ever written at or past entry `count` --, and a capacity (the entries d_chunks has room for) below it is refused.  Refused with FLANHIP_ERR_INVALID_ARG before any device call: null pointers, sizes
+ * <= 0, num_frames > INT32_MAX. */
+size_t flanhip_loud_workspace_bytes(int64_t num_channels, int64_t num_frames);
+int flanhip_loud_summary_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, float level, int64_t gap_frames, int64_t * d_summary,
+                             void * d_workspace, void * stream);
+int flanhip_loud_chunks_dev(int64_t num_channels, int64_t num_frames, int64_t gap_frames, int64_t count, int32_t * d_chunks, int64_t capacity,
+                            void * d_workspace, void * stream);
+/* Host pointers, the whole call: the summary always; the table if capacity > 0, which must then hold the count (capacity 0 asks for the
+ * summary alone).  `cancel` is polled before the uploads, before the launches and while they run. */
+int flanhip_loud_chunks(const float * audio, int64_t num_channels, int64_t num_frames, float level, int64_t gap_frames, int32_t * chunks,
+                        int64_t capacity, int64_t * summary, volatile int * cancel);
+/* test hook: frames per lane of the detection's kernels for the calling thread (1 ... 64; 0: the library's choice), which also sizes the
+ * workspace; and the geometry in force: frames per lane and per block, and the blocks the carry kernel takes per pass (what tests size
+ * their cases by) */
+void flanhip_loud_debug_run(int frames);
+int64_t flanhip_loud_run_frames(void);
+int64_t flanhip_loud_block_frames(void);
+int64_t flanhip_loud_carry_pass_blocks(void);
+/* Audio::reverse (AudioTemporal.cpp:174-188): out[c][f] = in[c][num_frames - 1 - f].  16-byte stores on the output's own boundaries whatever
+ * num_frames and the rows' alignment are.  The two buffers must not overlap at all: an output that shares any byte with the input is
+ * refused with FLANHIP_ERR_INVALID_ARG. */
+int flanhip_audio_reverse_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, float * d_out, void * stream);
+int flanhip_audio_reverse(const float * audio, int64_t num_channels, int64_t num_frames, float * out, volatile int * cancel);
+/* The fades and cuts of get_loud_chunks_base (AudioTemporal.cpp:52-83), host arithmetic, quirks kept: fade_ins has count + 1 entries, all
+ * fade_in_time at first; iteration i reads fade_ins[i] AFTER iteration i - 1 overwrote it (:57 after :61), sets fade_ins[i] to the chunk's start
+ * where the fade would reach before frame 0 and fade_ins[i + 1] to num_frames - end where it would reach num_frames, every value going through
+ * frame_to_time and back through time_to_frame in fp32; chunk i is cut_frames( start - left, end + right, left, right ) by
+ * flanhip_grains_cut_frames' rules -- whose clamp of the end to num_frames - 1 costs a chunk that reaches the end its last frame --, filling s,
+ * n, sf, ef of events[i].  offsets (count + 1 floats, or NULL): -2 * fade_ins[i] (:82-83).  join != 0: also every event's o, by Audio::join's
+ * fp32 running sum ( start + n / sample_rate ) + offsets[i + 1] (AudioCombination.cpp:205-221) and mix's time_to_frame (:127-129): the table of
+ * remove_silence.  chunks: int32[count][2] inside [0, num_frames].  Refused: null pointers, sizes <= 0, num_frames > INT32_MAX,
+ * sample_rate <= 0, a count flanhip_grains_workspace_bytes refuses, a fade no Frame holds. */
+int flanhip_loud_chunks_fades(int64_t num_frames, float sample_rate, const int32_t * chunks, int64_t count, float fade_in_time, int join,
+                              flanhip_grain_event * events, float * offsets);
+/* remove_edge_silence's cut (AudioTemporal.cpp:149-152) from the summary's first and last noisy frame (both -1: nothing noisy, which the
+ * reference's loops turn into start num_frames and end 0): out4 = { start - fade, end + fade, start fade, end fade } for cut_frames, with
+ * start = first, end = last + 1 and the fades shortened where they would leave the signal. */
+int flanhip_edge_silence_cut(int64_t num_frames, float sample_rate, int64_t first_noisy, int64_t last_noisy, float fade_time, int32_t * out4);
+/* split_at_times' frames (AudioTemporal.cpp:416-429): 0, then the frames of the SORTED times, skipping frames <= 0 and stopping at the first
+ * >= num_frames, then num_frames; piece i is cut_frames( frames[i], frames[i + 1], fade, fade ).  *out_count: the number of frames (pieces + 1);
+ * capacity 0 gives the count alone (count + 2 always suffices).  A NaN time is refused. */
+int flanhip_split_frames(int64_t num_frames, float sample_rate, const float * times, int64_t count, int32_t * frames, int64_t capacity,
+                         int64_t * out_count);
+/* rearrange's order (AudioTemporal.cpp:477-479).  The reference calls std::shuffle, whose draws the standard does not fix; here the permutation
+ * is this Fisher-Yates: order = 0 ... count - 1, g = std::mt19937( uint32( seed ) ), and for i = count - 1 down to 1: swap( order[i],
+ * order[g() % ( i + 1 )] ).  Output slot i plays slice order[i].  A seed names one result on every platform. */
+int flanhip_rearrange_order(int64_t count, uint64_t seed, int32_t * order);
+/* random_chunks' plan (AudioTemporal.cpp:493-533).  flanhip_random_chunks_frames: the iterations L of the loop at :496, which compares a Frame
+ * with the float time_to_frame( length ) (so a fractional end counts one more frame); -1 for what it refuses.  chunk_length: L floats, the
+ * Function at frame_to_time( f ), or NULL for the scalar; fade: L + 1 floats, or NULL.  The accumulator is a double and starts at 1; a chunk's
+ * length is clamped to [ frame_to_time( 32 ), num_frames / sample_rate ] in fp32; the starts end with Frame( time_to_frame( length ) ).  Chunk i is
+ * cut_frames( start, start + desired, left, right ) with desired = its frames + time_to_frame( ( fade_i + fade_i+1 ) / 2 ) and start = 0 where
+ * desired >= num_frames, else std::mt19937( uint32( seed ) )() % ( num_frames - desired ), drawn in chunk order: portable, so a seed names one
+ * result.  events: s, n, sf, ef and o (join with offsets[i] = -fade_i, as above); chunk_starts: the chunks' output frames (the mod's times);
+ * offsets: count + 1 floats.  capacity 0 gives the count alone. */
+int64_t flanhip_random_chunks_frames(float sample_rate, float length);
+int flanhip_random_chunks_plan(int64_t num_frames, float sample_rate, float length, const float * chunk_length, float chunk_length_scalar,
+                               const float * fade, float fade_scalar, uint64_t seed, flanhip_grain_event * events, int32_t * chunk_starts,
+                               float * offsets, int64_t capacity, int64_t * out_count);
+
 /* ---- Audio::resample (Audio/AudioConversions.cpp:14-30, r8brain CDSPResampler with default parameters) --------- */
 /* AudioConversions.cpp:22: out frames = Frame( float(num_frames) * ( dst_rate / src_rate ) ) */
 int64_t flanhip_resample_out_frames(int64_t num_frames, float src_rate, float dst_rate);
