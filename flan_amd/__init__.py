@@ -246,6 +246,26 @@ _SIGS = {
     "flanhip_rearrange_order": (C.c_int, [_i64, C.c_uint64, _vp]),
     "flanhip_random_chunks_frames": (_i64, [_f32, _f32]),
     "flanhip_random_chunks_plan": (C.c_int, [_i64, _f32, _f32, _vp, _f32, _vp, _f32, C.c_uint64, _vp, _vp, _vp, _i64, _vp]),
+    "flanhip_audio_ring_modulate_dev": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "flanhip_fade_frames_plan": (C.c_int, [_i64, C.c_int32, C.c_int32, _vp]),
+    "flanhip_audio_fade_dev": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "flanhip_waveform_dev": (C.c_int, [_i32, _vp, _i64, _vp, _vp]),
+    "flanhip_waveform_host": (C.c_int, [_i32, _vp, _i64, _vp]),
+    "flanhip_audio_moisture_dev": (C.c_int, [_vp, _i64, _i64, _f32, _i64, _f32, _vp, _f32, _vp, _f32, _vp, _f32, _i32, _vp, _vp]),
+    "flanhip_audio_energy_workspace_bytes": (C.c_size_t, [_i64, _i64]),
+    "flanhip_audio_energy_dev": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "flanhip_audio_rectify_dev": (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
+    "flanhip_synthesize_waveform_frames": (_i64, [_f32, _f32, _i32, _vp, _vp]),
+    "flanhip_osc_workspace_bytes": (C.c_size_t, [_i64]),
+    "flanhip_osc_phase_dev": (C.c_int, [_vp, _f32, _i64, C.c_double, _vp, _vp, _i32, _vp, _vp]),
+    "flanhip_osc_debug_run": (None, [_i32]),
+    "flanhip_osc_run_frames": (_i64, []),
+    "flanhip_osc_block_frames": (_i64, []),
+    "flanhip_osc_carry_pass_blocks": (_i64, []),
+    "flanhip_oneshot_resample_dev": (C.c_int, [_vp, _i64, C.c_double, C.c_double, _vp, _i64, _vp]),
+    "flanhip_audio_synthesize_waveform_workspace_bytes": (C.c_size_t, [_f32, _f32, _i32]),
+    "flanhip_audio_synthesize_waveform_dev": (C.c_int, [_i32, _vp, _f32, _f32, _f32, _i32, _vp, _vp, _vp]),
+    "flanhip_white_noise_draw": (C.c_int, [C.c_uint64, _i64, _vp]),
 }
 
 EXPORTS = sorted(_SIGS)
@@ -1838,3 +1858,123 @@ def random_chunks_plan(num_frames, sample_rate, length, chunk_length, fade, seed
     check(lib.flanhip_random_chunks_plan(num_frames, sample_rate, length, cp, cs, fp, fs, seed, _ptr(events), _ptr(starts), _ptr(offsets), count.value,
                                          C.cast(C.byref(count), _vp)))
     return events, starts, offsets
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Audio volume, waveforms, the oscillator and the energies (flan_amd/csrc/volume.hip).  Curves are floats or device arrays
+# ---------------------------------------------------------------------------------------------------------------
+
+WAVEFORM_SINE, WAVEFORM_SQUARE, WAVEFORM_SAW, WAVEFORM_TRIANGLE = 0, 1, 2, 3
+
+
+def _dev_curve(v):
+    """( device pointer or None, scalar ) of a float or a device array"""
+    scalar = isinstance(v, (int, float, np.floating))
+    return (None, float(v)) if scalar else (_dp(v), 0.0)
+
+
+def audio_ring_modulate_dev(d_audio, ch, n, d_other, other_ch, other_n, d_out, stream=None):
+    check(lib.flanhip_audio_ring_modulate_dev(_dp(d_audio), ch, n, _dp(d_other), other_ch, other_n, _dp(d_out), _vp(stream or 0)))
+
+
+def fade_frames_plan(num_frames, start, end):
+    """fade_frames_in_place's validation: ( start, end ) after the clamp at 0 and the proportional shrink"""
+    out = np.zeros(2, np.int32)
+    check(lib.flanhip_fade_frames_plan(num_frames, start, end, _ptr(out)))
+    return int(out[0]), int(out[1])
+
+
+def audio_fade_dev(d_audio, ch, n, d_start_gain, start, d_end_gain, end, d_out, stream=None):
+    check(lib.flanhip_audio_fade_dev(_dp(d_audio), ch, n, _dp(d_start_gain), start, _dp(d_end_gain), end, _dp(d_out), _vp(stream or 0)))
+
+
+def waveform_dev(kind, d_t, count, d_out, stream=None):
+    check(lib.flanhip_waveform_dev(kind, _dp(d_t), count, _dp(d_out), _vp(stream or 0)))
+
+
+def waveform_host(kind, t):
+    t = np.ascontiguousarray(t, np.float32).reshape(-1)
+    out = np.empty_like(t)
+    check(lib.flanhip_waveform_host(kind, _ptr(t), t.size, _ptr(out)))
+    return out
+
+
+def audio_moisture_dev(d_over, ch, n_over, over_rate, n, sample_rate, amount, frequency, skew, kind, d_out, stream=None):
+    """add_moisture's shaper over the oversampled block; amount, frequency, skew: floats or device arrays of n floats"""
+    (ap, a), (fp, f), (kp, k) = _dev_curve(amount), _dev_curve(frequency), _dev_curve(skew)
+    check(lib.flanhip_audio_moisture_dev(_dp(d_over), ch, n_over, over_rate, n, sample_rate, ap, a, fp, f, kp, k, kind, _dp(d_out), _vp(stream or 0)))
+
+
+def audio_energy_workspace_bytes(ch, n):
+    return int(lib.flanhip_audio_energy_workspace_bytes(ch, n))
+
+
+def audio_energy_dev(d_audio, ch, n, d_energy, d_ws, stream=None):
+    check(lib.flanhip_audio_energy_dev(_dp(d_audio), ch, n, _dp(d_energy), _dp(d_ws), _vp(stream or 0)))
+
+
+def audio_rectify_dev(d_audio, ch, n, d_out, stream=None):
+    check(lib.flanhip_audio_rectify_dev(_dp(d_audio), ch, n, _dp(d_out), _vp(stream or 0)))
+
+
+def synthesize_waveform_frames(length, sample_rate, oversample):
+    """( output frames, input frames, input rate ) of synthesize_waveform, or None where it returns a null Audio"""
+    n_in, rate = _i64(0), C.c_double(0)
+    n = int(lib.flanhip_synthesize_waveform_frames(length, sample_rate, oversample, C.cast(C.byref(n_in), _vp), C.cast(C.byref(rate), _vp)))
+    return None if n < 0 else (n, int(n_in.value), float(rate.value))
+
+
+def osc_workspace_bytes(n_in):
+    return int(lib.flanhip_osc_workspace_bytes(n_in))
+
+
+def osc_run_frames():
+    return int(lib.flanhip_osc_run_frames())
+
+
+def osc_block_frames():
+    return int(lib.flanhip_osc_block_frames())
+
+
+def osc_carry_pass_blocks():
+    return int(lib.flanhip_osc_carry_pass_blocks())
+
+
+class osc_run_forced:
+    """with osc_run_forced(frames): the oscillator's scan gives every lane `frames` frames (1 ... 64) -- a test hook"""
+
+    def __init__(self, frames):
+        self.frames = int(frames)
+
+    def __enter__(self):
+        lib.flanhip_osc_debug_run(self.frames)
+        return self
+
+    def __exit__(self, *exc):
+        lib.flanhip_osc_debug_run(0)
+        return False
+
+
+def osc_phase_dev(freq, n_in, in_rate, d_phases, d_wave, kind, d_ws, stream=None):
+    """freq: a float or a device array of n_in floats; d_phases / d_wave: either may be None"""
+    fp, f = _dev_curve(freq)
+    check(lib.flanhip_osc_phase_dev(fp, f, n_in, in_rate, _dp(d_phases), _dp(d_wave), kind, _dp(d_ws), _vp(stream or 0)))
+
+
+def oneshot_resample_dev(d_in, n_in, src_rate, dst_rate, d_out, n_out, stream=None):
+    check(lib.flanhip_oneshot_resample_dev(_dp(d_in), n_in, src_rate, dst_rate, _dp(d_out), n_out, _vp(stream or 0)))
+
+
+def audio_synthesize_waveform_workspace_bytes(length, sample_rate, oversample):
+    return int(lib.flanhip_audio_synthesize_waveform_workspace_bytes(length, sample_rate, oversample))
+
+
+def audio_synthesize_waveform_dev(kind, freq, length, sample_rate, oversample, d_out, d_ws, stream=None):
+    fp, f = _dev_curve(freq)
+    check(lib.flanhip_audio_synthesize_waveform_dev(kind, fp, f, length, sample_rate, oversample, _dp(d_out), _dp(d_ws), _vp(stream or 0)))
+
+
+def white_noise_draw(seed, count):
+    out = np.zeros(max(count, 0), np.float32)
+    check(lib.flanhip_white_noise_draw(seed, count, _ptr(out)))
+    return out

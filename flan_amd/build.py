@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libflanhip.so")
-SOURCES = ["core.hip", "conversions.hip", "team.hip", "sub.hip", "processors.hip", "processors_ext.hip", "processors_arrange.hip", "resample.hip", "utility.hip", "collective.hip", "transfer.hip", "spv.hip", "conv.hip", "repitch.hip", "compress.hip", "filter.hip", "halfband.hip", "comb.hip", "multinotch.hip", "spatial.hip", "pitch.hip", "grains.hip", "wavetable.hip", "spectrum.hip", "temporal.hip"]
+SOURCES = ["core.hip", "conversions.hip", "team.hip", "sub.hip", "processors.hip", "processors_ext.hip", "processors_arrange.hip", "resample.hip", "utility.hip", "collective.hip", "transfer.hip", "spv.hip", "conv.hip", "repitch.hip", "compress.hip", "filter.hip", "halfband.hip", "comb.hip", "multinotch.hip", "spatial.hip", "pitch.hip", "grains.hip", "wavetable.hip", "spectrum.hip", "temporal.hip", "volume.hip"]
 # -ffp-contract=off: the per-bin phase-vocoder arithmetic must round every fp32 operation individually, like the
 # reference; the FFT butterflies call fmaf explicitly where a fused multiply-add is wanted.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
@@ -20,7 +20,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # on the bench shape the synthesis kernel is 18 % faster without it (0.152 -> 0.125 ms), dft 4096 9 % (profiles/r02_e_*); same IEEE
 # operations either way, results bit-identical.
 NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA = {"conversions.hip": NO_PK, "team.hip": NO_PK, "sub.hip": NO_PK, "spv.hip": NO_PK, "conv.hip": NO_PK, "repitch.hip": NO_PK, "compress.hip": NO_PK, "filter.hip": NO_PK, "halfband.hip": NO_PK, "comb.hip": NO_PK, "multinotch.hip": NO_PK, "spatial.hip": NO_PK, "pitch.hip": NO_PK, "grains.hip": NO_PK, "wavetable.hip": NO_PK, "spectrum.hip": NO_PK, "temporal.hip": NO_PK}
+EXTRA = {"conversions.hip": NO_PK, "team.hip": NO_PK, "sub.hip": NO_PK, "spv.hip": NO_PK, "conv.hip": NO_PK, "repitch.hip": NO_PK, "compress.hip": NO_PK, "filter.hip": NO_PK, "halfband.hip": NO_PK, "comb.hip": NO_PK, "multinotch.hip": NO_PK, "spatial.hip": NO_PK, "pitch.hip": NO_PK, "grains.hip": NO_PK, "wavetable.hip": NO_PK, "spectrum.hip": NO_PK, "temporal.hip": NO_PK, "volume.hip": NO_PK}
 
 
 def kernel_source_hash():

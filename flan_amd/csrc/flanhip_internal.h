@@ -198,6 +198,12 @@ void note_workspace_producer( const void * d_ws, int kind, int epoch = 0 );   //
 int workspace_producer( const void * d_ws, int * epoch = nullptr );
 int synth_layout( int64_t ch, int64_t F, int bins, float sr, float ar, int W, SynthLayout * out );
 
+// r8brain's chain for two rates (resample.hip) as ONE oneshot of total_in samples into exactly total_out: what CDSPResampler( src, dst,
+// total_in ).oneshot( in, total_in, out, total_out ) writes (Audio/AudioSynthesis.cpp:65-66), where Audio::resample derives the length itself.
+// Equal rates are not a chain (served: false): r8brain passes the samples through (CDSPResampler.h:133-136)
+bool resample_chain_served( double src, double dst );
+int resample_chain_dev( const float * d_in, int64_t total_in, double src, double dst, float * d_out, int64_t total_out, hipStream_t s );
+
 // Interpolators: a named kind (FLANHIP_INTERP_LINEAR .. _SINE) or a live table registered with flanhip_interp_table_create (processors_ext.hip)
 bool valid_interp( int kind );
 float interp_eval_host( int kind, float x );            // one value on the host (get_frame): named kinds like Utility/Interpolator.cpp, tables like the device

@@ -1054,6 +1054,17 @@ static int resample_stages_dev( const float * d_in, int64_t total_in, int64_t ch
 	return FLANHIP_OK;
 	}
 
+// flanhip_internal.h: the chain with the caller's own output length, for the callers of CDSPResampler::oneshot other than Audio::resample
+bool resample_chain_served( double src, double dst )
+	{
+	std::vector<Stage> probe;
+	return build_stages( src, dst, probe );
+	}
+int resample_chain_dev( const float * d_in, int64_t total_in, double src, double dst, float * d_out, int64_t total_out, hipStream_t s )
+	{
+	return resample_stages_dev( d_in, total_in, total_in, src, dst, d_out, total_out, s );
+	}
+
 } // namespace flanhip
 
 using namespace flanhip;

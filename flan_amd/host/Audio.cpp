@@ -1,9 +1,9 @@
 // Audio.cpp -- construction and conversions of flan::Audio over the C ABI
 // (reference: src/flan/Audio/AudioConstructors.cpp, Conversions/AudioPV.cpp:12-84, Audio/AudioConversions.cpp:14-56,
-// Audio/AudioCombination.cpp:299-352, Audio/AudioTemporal.cpp:236-299, Audio/AudioVolume.cpp:5-67, 190-278,
+// Audio/AudioCombination.cpp:299-352, Audio/AudioTemporal.cpp:236-299, Audio/AudioVolume.cpp (all of it),
 // Audio/AudioFilter.cpp:280-758, 988-1263, Audio/AudioConversions.cpp:58-104, Audio/AudioChannels.cpp, Audio/AudioSpatial.cpp,
-// Audio/AudioInformation.cpp:138-304, 388-407, Audio/AudioCombination.cpp:78-237, Audio/AudioTemporal.cpp:10-234, 301-546,
-// Audio/AudioSynthesis.cpp:310-473, 572-638).
+// Audio/AudioInformation.cpp:121-304, 320-407, Audio/AudioCombination.cpp:78-237, Audio/AudioTemporal.cpp:10-234, 301-546,
+// Audio/AudioSynthesis.cpp:25-89, 310-473, 572-638).
 #include "flan/Audio.h"
 
 #include <algorithm>
@@ -1755,6 +1755,227 @@ Audio Audio::synthesize_spectrum( Second length, const Function<Second, Frequenc
 		return flanhip_audio_synthesize_spectrum_dev( d_mag.ptr(), d_theta.ptr(), spectrum_size_power, fundamental_power, num_channels, n, granularity,
 			freq_v.data(), int64_t( freq_v.size() ), d_out, ws, nullptr );
 		} );
+	}
+
+// ---- the rest of Audio/AudioVolume.cpp (:15-30, 69-188, 280-321), the energies and the amplitude envelope of Audio/AudioInformation.cpp
+// (:121-136, 320-363) and the oscillator and white noise of Audio/AudioSynthesis.cpp (:25-89); DESIGN.md 4.26 ------------------------------
+
+Audio Audio::ring_modulate( const Audio & other ) const
+	{
+	if( is_null() || other.is_null() ) return Audio::create_null();                // :19
+	const float * d_x = device_data();
+	const float * d_o = other.device_data();
+	if( !d_x || !d_o ) return Audio::create_null();
+	return audio_call( "ring_modulate", get_format(), true, detail::kNoWorkspace, [&]( float * out, void * )
+		{ return flanhip_audio_ring_modulate_dev( d_x, get_num_channels(), get_num_frames(), d_o, other.get_num_channels(), other.get_num_frames(), out, nullptr ); } );
+	}
+
+Audio Audio::fade( Second start, Second end, const Interpolator & interp ) const
+	{
+	if( is_null() ) return Audio::create_null();                                   // :75
+	return fade_frames( Frame( time_to_frame( start ) ), Frame( time_to_frame( end ) ), interp );
+	}
+
+Audio & Audio::fade_in_place( Second start, Second end, const Interpolator & interp )
+	{
+	if( is_null() ) { std::cout << "Null input" << std::endl; return *this; }     // :85
+	return fade_frames_in_place( Frame( time_to_frame( start ) ), Frame( time_to_frame( end ) ), interp );
+	}
+
+Audio Audio::fade_frames( Frame start, Frame end, const Interpolator & interp ) const
+	{
+	if( is_null() ) return Audio::create_null();                                   // :96
+	int32_t plan[2];
+	if( flanhip_fade_frames_plan( get_num_frames(), start, end, plan ) != FLANHIP_OK ) return Audio::create_null();      // :111-118
+	start = plan[0]; end = plan[1];
+	if( start == 0 && end == 0 ) return copy();                                    // :119
+	const float * d_x = device_data();
+	if( !d_x ) return Audio::create_null();
+	// the interpolator where the two loops evaluate it (:125, :130): exact for every one, named or callable
+	detail::StagingVector<float> start_gain( static_cast<size_t>( start ) ), end_gain( static_cast<size_t>( end ) );
+	for( Frame frame = 0; frame < start; ++frame ) start_gain[size_t( frame )] = interp( float( frame ) / start );
+	for( Frame frame = 0; frame < end; ++frame ) end_gain[size_t( frame )] = interp( float( frame ) / end );
+	const DeviceArg s = start ? upload_values( start_gain ) : DeviceArg(), e = end ? upload_values( end_gain ) : DeviceArg();
+	return audio_call( "fade_frames", get_format(), s.ok && e.ok, detail::kNoWorkspace, [&]( float * out, void * )
+		{ return flanhip_audio_fade_dev( d_x, get_num_channels(), get_num_frames(), s.ptr(), start, e.ptr(), end, out, nullptr ); } );
+	}
+
+Audio & Audio::fade_frames_in_place( Frame start, Frame end, const Interpolator & interp )
+	{
+	if( is_null() ) { std::cout << "Null input" << std::endl; return *this; }     // :108
+	Audio out = fade_frames( start, end, interp );
+	if( !out.is_null() ) *this = std::move( out );
+	return *this;
+	}
+
+Audio Audio::invert_phase() const
+	{
+	if( is_null() ) return Audio::create_null();                                   // :140
+	const float * d_x = device_data();
+	if( !d_x ) return Audio::create_null();
+	return audio_call( "invert_phase", get_format(), true, detail::kNoWorkspace, [&]( float * out, void * )
+		{ return flanhip_audio_gain_dev( d_x, get_num_channels(), get_num_frames(), nullptr, -1.0f, out, nullptr ); } );
+	}
+
+Audio Audio::waveshape( const Function<std::pair<Second, Sample>, Sample> & shaper, uint16_t oversample_factor ) const
+	{
+	if( is_null() ) return Audio::create_null();                                   // :151
+	Audio oversampled = resample( get_sample_rate() * oversample_factor );         // :153
+	if( oversampled.is_null() ) return Audio::create_null();
+	std::vector<float> & samples = oversampled.get_buffer();                       // the one download; the host copy is the truth from here
+	for( Channel channel = 0; channel < oversampled.get_num_channels(); ++channel )           // :154-164
+		detail::for_each_index( 0, oversampled.get_num_frames(), shaper.get_execution_policy(), [&]( int frame )
+			{
+			Sample & s = samples[oversampled.get_buffer_pos( channel, frame )];
+			s = shaper( std::pair<Second, Sample>( oversampled.frame_to_time( frame ), s ) );
+			} );
+	return oversampled.resample( get_sample_rate() );                              // :165
+	}
+
+Audio Audio::add_moisture( const Function<Second, Amplitude> & amount, const Function<Second, Frequency> & frequency, const Function<Second, float> & skew,
+	const Waveform & waveform ) const
+	{
+	if( is_null() ) return Audio::create_null();
+	const Frame n = get_num_frames();
+	const float sr = get_sample_rate();
+	if( waveform.kind() < 0 )                                                      // :175-187 as written, on the host
+		{
+		const auto amount_sampled = amount.sample( 0, n, 1.0f / sr ), frequency_sampled = frequency.sample( 0, n, 1.0f / sr ), skew_sampled = skew.sample( 0, n, 1.0f / sr );
+		const auto at = [n]( const auto & sampled, Frame i ) { return sampled.is_constant() ? sampled.get_constant() : sampled.get_vector()[size_t( std::clamp( i, 0, n - 1 ) )]; };
+		return waveshape( Function<std::pair<Second, Sample>, Sample>( [&]( std::pair<Second, Sample> ts ) -> Sample
+			{
+			const Frame i = Frame( time_to_frame( ts.first ) );
+			const float amount_c = at( amount_sampled, i ), frequency_c = at( frequency_sampled, i ), skew_c = at( skew_sampled, i );
+			const float power = ts.second >= 0 ? std::pow( ts.second, skew_c ) : -std::pow( -ts.second, skew_c );
+			return ts.second + amount_c * ts.second * waveform( pi2 * frequency_c * power );
+			}, waveform.get_execution_policy() ) );
+		}
+	const Audio oversampled = resample( sr * uint16_t( 4 ) );                       // :153 with the default factor
+	if( oversampled.is_null() ) return Audio::create_null();
+	const float * d_over = oversampled.device_data();
+	if( !d_over ) return Audio::create_null();
+	const DeviceArg a = upload_curve( amount, n, 1.0f / sr ), f = upload_curve( frequency, n, 1.0f / sr ), k = upload_curve( skew, n, 1.0f / sr );
+	const Audio shaped = audio_call( "add_moisture", oversampled.get_format(), a.ok && f.ok && k.ok, detail::kNoWorkspace, [&]( float * out, void * )
+		{
+		return flanhip_audio_moisture_dev( d_over, oversampled.get_num_channels(), oversampled.get_num_frames(), oversampled.get_sample_rate(), n, sr,
+			a.ptr(), a.scalar, f.ptr(), f.scalar, k.ptr(), k.scalar, waveform.kind(), out, nullptr );
+		} );
+	if( shaped.is_null() ) return Audio::create_null();
+	return shaped.resample( sr );                                                  // :165
+	}
+
+Audio Audio::apply_adsr_envelope( Second attack_time, Second decay_time, Second sustain_time, Second release_time, Amplitude sustain_level,
+	float attack_exponent, float decay_exponent, float release_exponent ) const
+	{
+	return modify_volume( ADSR( attack_time, decay_time, sustain_time, release_time, sustain_level, attack_exponent, decay_exponent, release_exponent ) );
+	}
+
+Audio Audio::apply_ar_envelope( Second attack_time, Second release_time, float attack_exponent, float release_exponent ) const
+	{
+	return modify_volume( ADSR( attack_time, 0, 0, release_time, 1, attack_exponent, 1, release_exponent ) );
+	}
+
+std::vector<float> Audio::get_total_energy() const
+	{
+	if( is_null() ) return std::vector<float>();
+	const float * d_x = device_data();
+	const size_t ws_bytes = flanhip_audio_energy_workspace_bytes( get_num_channels(), get_num_frames() );
+	if( !d_x || ws_bytes == 0 ) return std::vector<float>();
+	std::vector<float> energies( static_cast<size_t>( get_num_channels() ) );
+	if( !wavelengths_call( "get_total_energy", energies, ws_bytes, [&]( float * d_out, void * ws )
+		{ return flanhip_audio_energy_dev( d_x, get_num_channels(), get_num_frames(), d_out, ws, nullptr ); } ) ) return std::vector<float>();
+	return energies;
+	}
+
+std::vector<float> Audio::get_energy_difference( const Audio & other ) const
+	{
+	if( is_null() || other.is_null() ) return std::vector<float>();
+	const Audio resampled = get_sample_rate() == other.get_sample_rate() ? Audio() : other.resample( get_sample_rate() );      // :133
+	const Audio * sr_correct_source = get_sample_rate() == other.get_sample_rate() ? &other : &resampled;
+	return Audio::mix( std::vector<const Audio *>{ this, sr_correct_source }, { 0, 0 }, { 1, -1 } ).get_total_energy();        // :135
+	}
+
+Function<Second, Amplitude> Audio::get_amplitude_envelope( Second window_width ) const
+	{
+	if( is_null() ) return 0;                                                      // :324
+	if( window_width <= 0 ) return 0;                                              // :326
+	const Audio mono = convert_to_mono();                                          // :328
+	const float * d_mono = mono.is_null() ? nullptr : mono.device_data();
+	if( !d_mono ) return 0;
+	const Audio rectified = audio_call( "get_amplitude_envelope", mono.get_format(), true, detail::kNoWorkspace, [&]( float * out, void * )
+		{ return flanhip_audio_rectify_dev( d_mono, 1, mono.get_num_frames(), out, nullptr ); } );        // :331-333
+	if( rectified.is_null() ) return 0;
+	const fFrame window_width_frames = time_to_frame( window_width );              // :335
+	const Frame window_frames = Frame( window_width_frames );                      // :337: create_empty_with_frames takes a Frame
+	if( window_frames <= 0 ) return 0;
+	std::vector<float> window( static_cast<size_t>( window_frames ) );
+	float hann_integral = 0;
+	for( Frame i = 0; i < window_frames; ++i )                                      // :339-343
+		{
+		const float x = float( i ) / ( window_width_frames - 1 );
+		// Windows::hann (WindowFunctions.cpp:10-13): the fp32 argument, then the DOUBLE cos its unqualified call picks, narrowed on return
+		window[size_t( i )] = float( 0.5 * ( 1.0 - std::cos( double( 2.0f * pi * x ) ) ) );
+		hann_integral += window[size_t( i )];
+		}
+	const Audio hann_window = Audio::create_from_buffer( std::move( window ), 1, get_sample_rate() );
+	Audio convolved = rectified.convolve( hann_window, false );                    // :345
+	if( convolved.is_null() ) return 0;
+	convolved.modify_volume_in_place( pi / 2.0f / hann_integral );                 // :346
+	std::vector<float> ys = convolved.get_buffer();                                // :350
+	return Function<Second, Amplitude>( [ys = std::move( ys ), sr = get_sample_rate()]( float t )      // :351-363
+		{
+		const float x = t * sr;
+		if( 0 <= x && x < ys.size() - 1 )
+			{
+			const Frame x1 = Frame( std::floor( x ) );
+			const float y1 = ys[size_t( x1 )];
+			const float y2 = ys[size_t( x1 ) + 1];
+			return y1 + ( y2 - y1 ) * ( x - x1 );
+			}
+		else return 0.0f;
+		} );
+	}
+
+Audio Audio::synthesize_waveform( const Waveform & wave, Second length, const Function<Second, Frequency> & freq, FrameRate sample_rate, int oversample )
+	{
+	int64_t n_in = 0;
+	double in_sample_rate = 0;
+	const int64_t num_frames = flanhip_synthesize_waveform_frames( length, sample_rate, oversample, &n_in, &in_sample_rate );      // :33-44
+	if( num_frames <= 0 ) return Audio::create_null();
+	AudioBuffer::Format format;
+	format.num_channels = 1;
+	format.num_frames = Frame( num_frames );
+	format.sample_rate = sample_rate;
+	const DeviceArg f = upload_curve( freq, Frame( n_in ), float( 1.0f / in_sample_rate ) );     // :46 (a float over a double, narrowed by sample's float scale)
+	if( wave.kind() >= 0 )
+		{
+		const size_t ws_bytes = flanhip_audio_synthesize_waveform_workspace_bytes( length, sample_rate, oversample );
+		if( ws_bytes == 0 ) return Audio::create_null();
+		return audio_call( "synthesize_waveform", format, f.ok, ws_bytes, [&]( float * out, void * ws )
+			{ return flanhip_audio_synthesize_waveform_dev( wave.kind(), f.ptr(), f.scalar, length, sample_rate, oversample, out, ws, nullptr ); } );
+		}
+	// any other wave: the phases come to the host, the wave is evaluated there under its policy (:61-62), the samples go back for the chain
+	const size_t ws_bytes = flanhip_osc_workspace_bytes( n_in );
+	if( ws_bytes == 0 || !f.ok ) return Audio::create_null();
+	detail::StagingVector<float> wave_samples( static_cast<size_t>( n_in ) );
+	{
+	std::vector<float> phases( static_cast<size_t>( n_in ) );
+	if( !wavelengths_call( "synthesize_waveform", phases, ws_bytes, [&]( float * d_phases, void * ws )
+		{ return flanhip_osc_phase_dev( f.ptr(), f.scalar, n_in, in_sample_rate, d_phases, nullptr, -1, ws, nullptr ); } ) ) return Audio::create_null();
+	detail::for_each_index( 0, int( n_in ), wave.get_execution_policy(), [&]( int i ){ wave_samples[size_t( i )] = wave( phases[size_t( i )] ); } );
+	}
+	const DeviceArg w = upload_values( wave_samples );
+	return audio_call( "synthesize_waveform", format, w.ok, detail::kNoWorkspace, [&]( float * out, void * )
+		{ return flanhip_oneshot_resample_dev( w.ptr(), n_in, in_sample_rate, double( sample_rate ), out, num_frames, nullptr ); } );      // :65-66
+	}
+
+Audio Audio::synthesize_white_noise( Second length, FrameRate sample_rate, int oversample, uint64_t seed )
+	{
+	if( oversample < 1 || length <= 0 || sample_rate <= 0 ) return Audio::create_null();      // :77-78
+	Audio out = Audio::create_empty_with_length( length, 1, sample_rate * oversample );       // :84
+	if( out.is_null() ) return Audio::create_null();
+	if( flanhip_white_noise_draw( seed, out.get_num_frames(), out.get_buffer().data() ) != FLANHIP_OK ) return Audio::create_null();      // :80-86
+	return out.resample( sample_rate );                                            // :88
 	}
 
 } // namespace flan

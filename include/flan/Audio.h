@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <limits>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "flan/AudioBuffer.h"
@@ -86,6 +87,39 @@ public:
 	Audio compress( const Function<Second, Decibel> & threshold, const Function<Second, float> & compression_ratio = 3.0f,
 		const Function<Second, Second> & attack = 5.0f / 1000.0f, const Function<Second, Second> & release = 100.0f / 1000.0f,
 		const Function<Second, Decibel> & knee_width = Decibel( 0 ), const Audio * sidechain_source = nullptr ) const;
+	/** Every sample times the modulator's, whose channels and frames both wrap: out[c][f] = in[c][f] * other[c % channels][f % frames]
+	 *  (Audio/AudioVolume.cpp:15-30), on the device (flanhip_audio_ring_modulate_dev), exact.  The modulator's sample rate is not
+	 *  looked at.  A null *this or other gives a null Audio. */
+	Audio ring_modulate( const Audio & other ) const;
+	/** Fades over the first `start` and the last `end` frames (:69-135): frame f < start times interp( float( f ) / start ), frame frames - 1 - k,
+	 *  k < end, times interp( float( k ) / end ).  Negative lengths are 0; lengths that together exceed the frames are both scaled by
+	 *  float( frames ) / ( start + end ) and floored (flanhip_fade_frames_plan); a frame both fades reach is multiplied twice, the start's gain
+	 *  first.  The interpolator, named or callable, is evaluated on the host into two small tables, so every one is exact; the frames are
+	 *  multiplied on the device (flanhip_audio_fade_dev).  fade / fade_in_place: the times through time_to_frame, truncated.  Both fades 0
+	 *  return a copy.  A null *this gives a null Audio; the in-place forms print "Null input" and leave it. */
+	Audio fade( Second start = 16.0f / 48000.0f, Second end = 16.0f / 48000.0f, const Interpolator & interp = Interpolator::sqrt() ) const;
+	Audio & fade_in_place( Second start = 16.0f / 48000.0f, Second end = 16.0f / 48000.0f, const Interpolator & interp = Interpolator::sqrt() );
+	Audio fade_frames( Frame start = 16, Frame end = 16, const Interpolator & interp = Interpolator::sqrt() ) const;
+	Audio & fade_frames_in_place( Frame start = 16, Frame end = 16, const Interpolator & interp = Interpolator::sqrt() );
+	/** Every sample negated (:137-144): flanhip_audio_gain_dev with -1, an exact fp32 product. */
+	Audio invert_phase() const;
+	/** shaper( ( time, sample ) ) over every sample at oversample_factor times the sample rate (:146-166): resample( sr * k ) on the device,
+	 *  ONE download, the shaper on the host over every ( channel, frame ) with ( oversampled.frame_to_time( frame ), s ) under the shaper's
+	 *  policy, an upload, resample( sr ) on the device.  Equal bit for bit to that composition of the public methods.  A null *this, and
+	 *  oversample_factor 0 (a sample rate of 0), give a null Audio. */
+	Audio waveshape( const Function<std::pair<Second, Sample>, Sample> & shaper, uint16_t oversample_factor = 4 ) const;
+	/** The moisture effect (:168-188): waveshape, factor 4, with s -> s + amount * s * waveform( pi2 * frequency * power ), power = s >= 0 ?
+	 *  pow( s, skew ) : -pow( -s, skew ), the three Functions sampled once per ORIGINAL frame and read at Frame( time * sample rate ).  With a named
+	 *  waveform (waveforms::sine, the default, square, saw, triangle) nothing leaves the device: the up-chain, flanhip_audio_moisture_dev, the
+	 *  down-chain; a constant travels as a scalar.  Any other waveform takes waveshape with the reference's shaper on the host.  Stated
+	 *  deviation: the curve index is clamped to frames - 1, where the reference's fp32 arithmetic can reach `frames` and read past its vector.
+	 *  pow and sin are the correctly rounded fp32 functions on the device, the C library's on the host.  A null *this gives a null Audio. */
+	Audio add_moisture( const Function<Second, Amplitude> & amount = .5f, const Function<Second, Frequency> & frequency = 96,
+		const Function<Second, float> & skew = 4, const Waveform & waveform = waveforms::sine ) const;
+	/** modify_volume( ADSR( ... ) ) (:280-301), and the same with no decay, no sustain and a sustain level of 1 (:304-321). */
+	Audio apply_adsr_envelope( Second attack_time, Second decay_time, Second sustain_time, Second release_time, Amplitude sustain_level,
+		float attack_exponent = 1, float decay_exponent = 1, float release_exponent = 1 ) const;
+	Audio apply_ar_envelope( Second attack_time, Second release_time, float attack_exponent = 1, float release_exponent = 1 ) const;
 
 	// ---- filters ----
 	/** The Butterworth low-pass of any order with a cutoff that may change every frame (Audio/AudioFilter.cpp:327-378; Zavalishin, The
@@ -274,12 +308,24 @@ public:
 	/** convert_to_mono().get_local_frequencies( 0, 0, -1, 2048, 128 ) as a function of time, linear between the hops and 0 outside them
 	 *  (:388-407).  Where the reference would read an empty vector (a null *this, a signal of 2048 frames or fewer) the function is 0. */
 	Function<Second, Amplitude> get_frequency_envelope() const;
+	/** The sum of every channel's squared samples (Audio/AudioInformation.cpp:121-129), on the device (flanhip_audio_energy_dev):
+	 *  the squares exact in fp64, summed in fp64 in a fixed order without atomics, rounded to fp32 once.  That is the correctly rounded sum to
+	 *  within one ulp, the same bits on every run -- not the rounding sequence of the reference's sequential fp32 loop.  A null *this gives an
+	 *  empty vector. */
+	std::vector<float> get_total_energy() const;
+	/** mix( { this, other }, { 0, 0 }, { 1, -1 } ).get_total_energy(), other first resample()d to this sample rate if it differs (:131-136). */
+	std::vector<float> get_energy_difference( const Audio & other ) const;
+	/** The rectified mono signal smoothed by a Hann window window_width long, as a function of time (:320-363): convert_to_mono, a rectifier
+	 *  (flanhip_audio_rectify_dev), convolve( window, false ) and the gain pi / 2 / ( the window's fp32 running sum ), all on the device; the
+	 *  window is made on the host.  The Function owns the downloaded samples, is linear between frames and 0 outside [0, ( size - 1 ) / sr ).
+	 *  A null *this, window_width <= 0 and a window of no frames give the constant 0. */
+	Function<Second, Amplitude> get_amplitude_envelope( Second window_width = 0.1f ) const;
 
 	// ---- cutting, mixing and granular synthesis ----
 	// Everything below ends in one kernel (flanhip_grains_mix_dev): an output sample is the fp32 sum, in the order of the inputs,
 	// of the inputs that cover it, bit for bit what the reference's loop over its inputs computes (Audio/AudioCombination.cpp:155-167); grains are
 	// cut, faded and windowed while they are read and never written anywhere.  Results stay device-resident until read.  Not offered: select,
-	// fade / fade_frames and their in-place forms as public methods, mix_in_place, texture_effect, synthesize_trainlets, synthesize_impulse.
+	// mix_in_place, texture_effect, synthesize_trainlets, synthesize_impulse.
 	/** The frames between two times, with square-root fades at either end (Audio/AudioTemporal.cpp:190-234, Audio/AudioVolume.cpp:102-135): times
 	 *  become frames by truncation; end <= start gives a null Audio, checked before start and end are clamped to [0, frames - 1] -- so the last
 	 *  frame is never part of a cut --; fades are clamped at 0 and, where together they are longer than the cut, both scaled down and floored.  A
@@ -354,11 +400,24 @@ public:
 		const Function<Frequency, Amplitude> & peak_distribution = []( Frequency x ){ return 1.0f / std::sqrt( pi2 ) * std::exp( -0.5f * std::pow( x, 2.0f ) ); },
 		int fundamental_power = 8, int spectrum_size_power = 20, Channel num_channels = 2, Second granularity = 0.001f,
 		const std::vector<Radian> * phases = nullptr );
+	/** An oscillator (Audio/AudioSynthesis.cpp:25-69): wave( phase ) at oversample times the sample rate, phase the running sum of freq over the
+	 *  oversampled frames modulo 1 cycle, then r8brain's chain down into exactly Frame( length * sample_rate ) frames, one channel.  freq is
+	 *  sampled once per oversampled frame at i * ( 1.0f / ( sample_rate * oversample ) ); a constant travels as a scalar.  The phases are a scan
+	 *  on the device carried in fp64 (flanhip_osc_phase_dev: within 2^-23 of a cycle of the exact modular sum; the reference's fp32 scan has no
+	 *  defined grouping and drifts).  A named waveform is evaluated inside the scan and nothing leaves the device; any other is evaluated on the
+	 *  host at the downloaded phases under its policy.  oversample 1 copies the wave samples, as r8brain does for equal rates.  oversample < 1,
+	 *  length <= 0, sample_rate <= 0, no output frame, or more oversampled frames than a Frame counts give a null Audio. */
+	static Audio synthesize_waveform( const Waveform & wave, Second length, const Function<Second, Frequency> & freq, FrameRate sample_rate = 48000,
+		int oversample = 16 );
+	/** Uniform noise in [-1, 1) drawn at oversample times the sample rate on the host -- std::mt19937( seed ) through
+	 *  std::uniform_real_distribution<>( -1.0f, 1.0f ), :80-86 --, then resample( sample_rate ) (:71-89).  A seed names one result; the default
+	 *  is random_seed(), as the reference seeds from std::random_device. */
+	static Audio synthesize_white_noise( Second length, FrameRate sample_rate = 48000, int oversample = 16, uint64_t seed = random_seed() );
 
 	// ---- silence removal and slicing (Audio/AudioTemporal.cpp:10-188, 301-546) ----
 	// The loud chunks are found by one scan on the device (flanhip_loud_summary_dev, flanhip_loud_chunks_dev); the fades, splits and plans are
 	// host arithmetic behind the C ABI; everything ends in the mixing kernel above, so without the Hann flag results are the reference's bit for
-	// bit.  Not offered: texture_effect, select, the public fade* family, mix_in_place, and the commented-out stereo_delay.
+	// bit.  Not offered: texture_effect, select, mix_in_place, and the commented-out stereo_delay.
 	/** What std::random_device gives: the default seed of rearrange and random_chunks, as the reference seeds its engines (:477, :522). */
 	static uint64_t random_seed();
 	/** *this with -start frames of silence put before it and end frames after it; negative amounts cut (:96-114 over mix_in_place,

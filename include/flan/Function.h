@@ -202,4 +202,50 @@ private:
 	std::function<float( float )> f_;
 	};
 
+// The reference's waveforms::sine / square / saw / triangle (Function.cpp:32-39) are plain std::functions whose identity is lost once they are
+// inside a Function.  Here a Waveform carries a kind the device can evaluate (FLANHIP_WAVEFORM_* in flanhip.h), as an Interpolator does; one
+// built from a callable has kind -1 and is evaluated on the host under its policy.  Each named one is fmod( t, 1.0f ), which keeps the sign
+// of t, followed by the reference's expression.
+class Waveform
+	{
+public:
+	static Waveform sine()     { return Waveform( 0, []( Second t ){ const Second t0 = std::fmod( t, 1.0f ); return std::sin( pi2 * t0 ); } ); }
+	static Waveform square()   { return Waveform( 1, []( Second t ){ const Second t0 = std::fmod( t, 1.0f ); return t0 < 0.5f ? -1.0f : 1.0f; } ); }
+	static Waveform saw()      { return Waveform( 2, []( Second t ){ const Second t0 = std::fmod( t, 1.0f ); return -1.0f + 2.0f * t0; } ); }
+	static Waveform triangle() { return Waveform( 3, []( Second t ){ const Second t0 = std::fmod( t, 1.0f ); return t0 < 0.5f ? -1.0f + 4.0f * t0 : 3.0f - 4.0f * t0; } ); }
+	template<typename T, std::enable_if_t<std::is_convertible_v<T, std::function<Amplitude( Second )>> && !std::is_same_v<std::decay_t<T>, Waveform>, int> = 0>
+	Waveform( T && fn, ExecutionPolicy policy = ExecutionPolicy::Parallel_Unsequenced ) : kind_( -1 ), f_( std::forward<T>( fn ) ), policy_( policy ) {}
+	Amplitude operator()( Second t ) const { return f_( t ); }
+	int kind() const { return kind_; }                                            // FLANHIP_WAVEFORM_*, or -1
+	ExecutionPolicy get_execution_policy() const { return policy_; }
+private:
+	Waveform( int kind, std::function<Amplitude( Second )> fn ) : kind_( kind ), f_( std::move( fn ) ), policy_( ExecutionPolicy::Parallel_Unsequenced ) {}
+	int kind_;
+	std::function<Amplitude( Second )> f_;
+	ExecutionPolicy policy_;
+	};
+
+namespace waveforms {
+inline const Waveform sine = Waveform::sine();
+inline const Waveform square = Waveform::square();
+inline const Waveform saw = Waveform::saw();
+inline const Waveform triangle = Waveform::triangle();
+}
+
+/** The envelope of Function.cpp:11-30: 0 outside [0, a + d + s + r]; ( t / a )^aExp while attacking; ( 1 - ( t - a ) / d )^dExp * ( 1 - sLvl ) + sLvl
+ *  while decaying; sLvl while sustaining; ( 1 - ( t - a - d - s ) / r )^rExp * sLvl while releasing; 0 at t == a + d + s + r exactly.  Every
+ *  operation in fp32, in that order. */
+inline Function<Second, Amplitude> ADSR( Second a, Second d, Second s, Second r, Amplitude sLvl, float aExp = 1, float dExp = 1, float rExp = 1 )
+	{
+	return Function<Second, Amplitude>( [a, d, s, r, sLvl, aExp, dExp, rExp]( Second t ) -> Amplitude
+		{
+		if( t < 0 || t > a + d + s + r ) return 0.0f;
+		else if( t < a ) return std::pow( t / a, aExp );
+		else if( t < a + d ) return std::pow( 1.0f - ( t - a ) / d, dExp ) * ( 1.0f - sLvl ) + sLvl;
+		else if( t < a + d + s ) return sLvl;
+		else if( t < a + d + s + r ) return std::pow( 1.0f - ( t - a - d - s ) / r, rExp ) * sLvl;
+		else return 0.0f;
+		} );
+	}
+
 } // namespace flan

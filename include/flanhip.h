@@ -1280,6 +1280,86 @@ int flanhip_audio_synthesize_spectrum(const float * mag, const float * theta, in
                                       int64_t num_channels, int64_t out_frames, int64_t granularity_frames, const float * freq, int64_t freq_count,
                                       float * out, volatile int * cancel);
 
+/* ---- Audio::ring_modulate, the fades, add_moisture's nonlinearity, the named waveforms and get_total_energy (Audio/AudioVolume.cpp:15-30,
+ * 69-188, Function.cpp:32-39, Audio/AudioInformation.cpp:121-129) (flan_amd/csrc/volume.hip) ---------------------------- */
+/* The pointwise entry points below store 16 bytes per lane on the output's own 16-byte boundaries whatever num_frames and the rows' alignment
+ * are.  d_out may be the input block itself; an output that shares bytes with an input without being it, or with a table, is refused.
+ * Refused with FLANHIP_ERR_INVALID_ARG before any device call: null pointers, sizes <= 0, num_frames > INT32_MAX. */
+/* Audio::ring_modulate (AudioVolume.cpp:15-30): out[c][f] = audio[c][f] * other[c % other_channels][f % other_frames], one fp32 product. */
+int flanhip_audio_ring_modulate_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, const float * d_other, int64_t other_channels,
+                                    int64_t other_frames, float * d_out, void * stream);
+/* fade_frames_in_place's validation (:111-118), host arithmetic: negative lengths become 0; where start + end > num_frames both are scaled by
+ * float( num_frames ) / ( start + end ) in fp32 and floored.  out2 = { start, end }.  (The sum is formed in 64 bits; each result is kept at
+ * num_frames at most.) */
+int flanhip_fade_frames_plan(int64_t num_frames, int32_t start, int32_t end, int32_t * out2);
+/* The two loops of fade_frames_in_place (:121-133) for every channel: frame f < start times d_start_gain[f], then frame num_frames - 1 - k,
+ * k < end, times d_end_gain[k]; a frame in both ranges is multiplied twice, the start's gain first; every other frame is copied.  The tables
+ * are what the host evaluated: interp( float( f ) / start ) and interp( float( k ) / end ).  A table may be NULL where its length is 0. */
+int flanhip_audio_fade_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, const float * d_start_gain, int64_t start,
+                           const float * d_end_gain, int64_t end, float * d_out, void * stream);
+/* The named waveforms (Function.cpp:32-39): t0 = fmod( t, 1.0f ) (which keeps t's sign), then sine sin( pi2 * t0 ), square t0 < 0.5f ? -1 : 1,
+ * saw -1 + 2 t0, triangle t0 < 0.5f ? -1 + 4 t0 : 3 - 4 t0.  On the device the sine is the fp32 product pi2 * t0 and then the correctly
+ * rounded fp32 sine (evaluated in fp64, rounded once); the other three are exact in fp32.  flanhip_waveform_host: the same on the host with
+ * the C library's sinf. */
+#define FLANHIP_WAVEFORM_SINE     0
+#define FLANHIP_WAVEFORM_SQUARE   1
+#define FLANHIP_WAVEFORM_SAW      2
+#define FLANHIP_WAVEFORM_TRIANGLE 3
+int flanhip_waveform_dev(int waveform_kind, const float * d_t, int64_t count, float * d_out, void * stream);
+int flanhip_waveform_host(int waveform_kind, const float * t, int64_t count, float * out);
+/* The shaper of Audio::add_moisture (:179-187) over the OVERSAMPLED block float[ch][oversampled_frames] at oversampled_rate, between the two
+ * chains of Audio::waveshape (:153, :165).  Per sample s at oversampled frame F: t = float( F ) / oversampled_rate (:161); the curves are read
+ * at i = Frame( t * sample_rate ), the ORIGINAL Audio's time_to_frame (:181-183), clamped to num_frames - 1 -- a stated deviation: for long
+ * inputs the reference's fp32 arithmetic reaches num_frames and reads past its vector --; power = s >= 0 ? pow( s, skew ) : -pow( -s, skew );
+ * out = s + amount * s * waveform( pi2 * frequency * power ), every product an fp32 product in that order, none contracted.  pow is
+ * evaluated in fp64 and rounded once.  d_amount, d_frequency, d_skew: float[num_frames], or NULL for the scalar beside it. */
+int flanhip_audio_moisture_dev(const float * d_oversampled, int64_t num_channels, int64_t oversampled_frames, float oversampled_rate,
+                               int64_t num_frames, float sample_rate, const float * d_amount, float amount, const float * d_frequency,
+                               float frequency, const float * d_skew, float skew, int waveform_kind, float * d_out, void * stream);
+/* Audio::get_total_energy (AudioInformation.cpp:121-129): d_energy[c] = the sum of the channel's squares.  The squares are exact in fp64 and
+ * are summed in fp64 in a fixed order (lane, wavefront, block, then the blocks by a second one-block launch), no atomics: two runs give the
+ * same bits.  The sum is rounded to fp32 once: the result is the correctly rounded sum to within one ulp, NOT the rounding sequence of the
+ * reference's sequential fp32 x + s * s (which its compiler may contract); a sum beyond fp32's range is inf. */
+size_t flanhip_audio_energy_workspace_bytes(int64_t num_channels, int64_t num_frames);      /* 0 for a shape it refuses */
+int flanhip_audio_energy_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, float * d_energy, void * d_workspace, void * stream);
+/* The rectifier of Audio::get_amplitude_envelope (AudioInformation.cpp:331-333): s < 0 ? s * -1 : s; -0 and a NaN stay as they are. */
+int flanhip_audio_rectify_dev(const float * d_audio, int64_t num_channels, int64_t num_frames, float * d_out, void * stream);
+
+/* ---- Audio::synthesize_waveform and synthesize_white_noise (Audio/AudioSynthesis.cpp:25-89) (volume.hip) ------------- */
+/* Validation and sizes (:33-46): the output's frames Frame( length * sample_rate ), and through the pointers (either may be NULL) the input's
+ * frames, that times oversample, and its rate, the fp32 product sample_rate * oversample as a double.  -1 for oversample < 1, length <= 0,
+ * sample_rate <= 0, no output frame, or more input frames than a Frame counts. */
+int64_t flanhip_synthesize_waveform_frames(float length, float sample_rate, int oversample, int64_t * num_in_frames, double * in_sample_rate);
+/* The phases (:51-58): phase[i] = ( the sum of frequency[j], j < i, modulo M ) / M, M = in_sample_rate, a negative sum wrapping upward as
+ * fmod_fixed does.  The reference forms them by std::exclusive_scan of fmod_fixed( a + b, M ) in fp32 under a parallel policy, whose grouping
+ * is not defined; here the scan is carried in fp64 (a lane's run is one "add c modulo M" map, the maps are composed over the block and the
+ * blocks), and phase = float( p / M ), one rounding: within 2^-23 of a cycle of the exact modular sum, which the reference's fp32 sums are not.
+ * d_freq: float[num_in_frames] (the frequency Function sampled at i * ( 1.0f / M ), :46) or NULL for the scalar.  d_phases and d_wave:
+ * float[num_in_frames]; either may be NULL; d_wave takes waveform( phase ) of the named kind.  The run -- frames per lane -- changes results
+ * by fp64 rounding of the sums only. */
+size_t flanhip_osc_workspace_bytes(int64_t num_in_frames);
+int flanhip_osc_phase_dev(const float * d_freq, float freq, int64_t num_in_frames, double in_sample_rate, float * d_phases, float * d_wave,
+                          int waveform_kind, void * d_workspace, void * stream);
+/* test hook: frames per lane of the oscillator's scan for the calling thread (1 ... 64; 0: the library's choice), which also sizes the
+ * workspace; and the geometry in force */
+void flanhip_osc_debug_run(int frames);
+int64_t flanhip_osc_run_frames(void);
+int64_t flanhip_osc_block_frames(void);
+int64_t flanhip_osc_carry_pass_blocks(void);
+/* r8b::CDSPResampler( src_rate, dst_rate, num_in_frames ).oneshot( in, num_in_frames, out, num_out_frames ) (:65-66): the chain of
+ * flanhip_resample_dev with the CALLER's output length.  Equal rates have no chain: the samples pass through (CDSPResampler.h:133-136),
+ * zeros behind the input's end. */
+int flanhip_oneshot_resample_dev(const float * d_in, int64_t num_in_frames, double src_rate, double dst_rate, float * d_out,
+                                 int64_t num_out_frames, void * stream);
+/* Audio::synthesize_waveform with a named waveform, without leaving the device: the scan with the waveform fused into its replay, then
+ * flanhip_oneshot_resample_dev into exactly Frame( length * sample_rate ) frames.  d_freq as flanhip_osc_phase_dev takes it. */
+size_t flanhip_audio_synthesize_waveform_workspace_bytes(float length, float sample_rate, int oversample);      /* 0 for arguments it refuses */
+int flanhip_audio_synthesize_waveform_dev(int waveform_kind, const float * d_freq, float freq, float length, float sample_rate, int oversample,
+                                          float * d_out, void * d_workspace, void * stream);
+/* synthesize_white_noise's draw (:80-86), host: std::mt19937( seed ) through std::uniform_real_distribution<>( -1.0f, 1.0f ), each value
+ * narrowed to fp32.  (The distribution is the C++ library's: two engine outputs per value in libstdc++.) */
+int flanhip_white_noise_draw(uint64_t seed, int64_t count, float * out);
+
 /* ---- synthetic input + comparison utilities (bench / tests; defined by this project) -------------- */
 int flanhip_noise_dev(float * d_out, int64_t num_channels, int64_t num_audio_frames, uint32_t seed, void * stream);
 /* a plain streaming copy, 16 bytes per lane: the measured-copy yardstick bench.py quotes beside the 8 TB/s spec (count: floats, a multiple of 4) */
