@@ -138,6 +138,7 @@ _SIGS = {
     "flanhip_convolve_debug_partition": (None, [_i32]),
     "flanhip_audio_repitch_out_frames": (_i64, [_vp, _i64, _i64]),
     "flanhip_audio_repitch_plan": (_i64, [_i64, _f32, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "flanhip_audio_repitch_runs": (_i64, [_i64, _f32, _vp, _i64, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i32), C.POINTER(_i64)]),
     "flanhip_audio_repitch_workspace_bytes": (C.c_size_t, [_i64, _f32, _vp, _i64, _i64, _i32]),
     "flanhip_audio_repitch": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _i64, _i64, _i32, _vp, _vp]),
     "flanhip_audio_repitch_dev": (C.c_int, [_vp, _i64, _i64, _f32, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
@@ -211,6 +212,7 @@ _SIGS = {
     "flanhip_wavetable_resample_dev": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "flanhip_wavetable_resample": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
     "flanhip_wavetable_synth_plan": (_i64, [_i64, _f32, _i32, _i64, _vp, _i64, _i64] + [_vp] * 10),
+    "flanhip_wavetable_synth_runs": (_i64, [_i64, _f32, _i32, _i64, _vp, _i64, _i64, _i64] + [_vp] * 7 + [C.POINTER(_i32), C.POINTER(_i64)]),
     "flanhip_wavetable_synth_workspace_bytes": (C.c_size_t, [_i64, _i64, _f32, _i32, _i64, _vp, _i64]),
     "flanhip_wavetable_synth_dev": (C.c_int, [_vp, _i64, _i64, _i32, _f32, _i64, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
     "flanhip_wavetable_synth": (C.c_int, [_vp, _i64, _i64, _i32, _f32, _i64, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp]),
@@ -900,6 +902,29 @@ def audio_repitch_plan(num_frames, sample_rate, inv_factors, granularity_frames,
     inv = np.ascontiguousarray(inv_factors, np.float32)
     return _block_plan(_PLAN_FIELDS + [("wanted", np.int32)], lambda capacity, pointers, total: lib.flanhip_audio_repitch_plan(
         num_frames, sample_rate, _ptr(inv), inv.size, granularity_frames, quality, capacity, *pointers, total), "out_frames")
+
+
+def _run_table(fields, call):
+    """A host planner's run table, in the two calls of _block_plan: call( capacity, pointers, channels_per_group, groups ) makes the C call
+    and gives the number of runs or an error code.  A dict of one array per ( name, dtype ) of `fields`, channels_per_group and groups."""
+    cpw, groups = _i32(0), _i64(0)
+    runs = call(0, [None] * len(fields), C.byref(cpw), C.byref(groups))
+    if runs < 0:
+        check(int(runs))
+    t = {name: np.empty(runs, dtype) for name, dtype in fields}
+    got = call(runs, [_ptr(t[name]) for name, _ in fields], C.byref(cpw), C.byref(groups))
+    assert got == runs
+    t["channels_per_group"], t["groups"] = int(cpw.value), int(groups.value)
+    return t
+
+
+def audio_repitch_runs(num_frames, sample_rate, inv_factors, granularity_frames, num_channels, quality=REPITCH_SINC):
+    """The runs the sinc launch cuts the plan into: a dict of per-run arrays (first_block, num_blocks, win_start, win_len; win_len 0: the
+    taps come from global memory), channels_per_group and groups."""
+    inv = np.ascontiguousarray(inv_factors, np.float32)
+    fields = [("first_block", np.int64), ("num_blocks", np.int32), ("win_start", np.int64), ("win_len", np.int32)]
+    return _run_table(fields, lambda capacity, pointers, cpw, groups: lib.flanhip_audio_repitch_runs(
+        num_frames, sample_rate, _ptr(inv), inv.size, granularity_frames, quality, num_channels, capacity, *pointers, cpw, groups))
 
 
 def audio_repitch_workspace_bytes(num_frames, sample_rate, inv_factors, granularity_frames, quality=REPITCH_SINC):
@@ -1598,6 +1623,16 @@ def wavetable_synth_plan(out_frames, sample_rate, wavelength, granularity_frames
     fields = _PLAN_FIELDS + [("num_out", np.int32), ("wanted", np.int32), ("in_start", np.int64)]
     return _block_plan(fields, lambda capacity, pointers, total: lib.flanhip_wavetable_synth_plan(
         out_frames, sample_rate, wavelength, granularity_frames, _ptr(f), f.size, capacity, *pointers), "unused")
+
+
+def wavetable_synth_runs(out_frames, sample_rate, wavelength, granularity_frames, freq, num_channels):
+    """The runs the synthesis launch cuts the plan into: a dict of per-run arrays (first_out, num_out, first_block, num_blocks, j0, win_start,
+    win_len), channels_per_group and groups."""
+    f = np.ascontiguousarray(freq, np.float32).reshape(-1)
+    fields = [("first_out", np.int64), ("num_out", np.int32), ("first_block", np.int64), ("num_blocks", np.int32), ("j0", np.int64),
+              ("win_start", np.int64), ("win_len", np.int32)]
+    return _run_table(fields, lambda capacity, pointers, cpw, groups: lib.flanhip_wavetable_synth_runs(
+        out_frames, sample_rate, wavelength, granularity_frames, _ptr(f), f.size, num_channels, capacity, *pointers, cpw, groups))
 
 
 def wavetable_synth_workspace_bytes(ch, out_frames, sample_rate, wavelength, granularity_frames, freq):

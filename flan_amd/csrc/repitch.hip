@@ -225,6 +225,12 @@ int rp_prepare( int64_t ch, int64_t n, float sr, const float * inv, int64_t coun
 	return FLANHIP_OK;
 	}
 
+// channels per workgroup and channel groups of the sinc launch
+int rp_channel_groups( const RpPlan & plan, const std::vector<RpRun> & runs, int64_t g, int64_t ch, int64_t * groups )
+	{
+	return wdl_channel_groups( int64_t( plan.blocks.size() ) * g, runs.size(), ch, groups );
+	}
+
 int launch_repitch( const float * d_x, int64_t ch, int64_t n, int64_t g, int quality, const RpPlan & plan, const std::vector<RpRun> & runs,
 	float * d_out, void * d_ws, hipStream_t s )
 	{
@@ -251,8 +257,8 @@ int launch_repitch( const float * d_x, int64_t ch, int64_t n, int64_t g, int qua
 		}
 	const double * d_win = nullptr;
 	if( int rc = wdl_window<RP_TAPS>( "repitch", d_ws, l, runs, s, &d_win ) ) return rc;
-	const int cpw = wdl_channels_per_group( num_blocks * g, runs.size(), ch );
-	const int64_t groups = ( ch + cpw - 1 ) / cpw;
+	int64_t groups = 0;
+	const int cpw = rp_channel_groups( plan, runs, g, ch, &groups );
 	return launch_kernel( "repitch", k_repitch_sinc, int64_t( runs.size() ) * groups, RP_THREADS, 0, s, d_x, ch, n, g, plan.out_frames, d_blocks,
 		(const RpRun*) ( ws + l.run_off ), d_win, groups, cpw, d_out );
 	}
@@ -283,6 +289,31 @@ int64_t flanhip_audio_repitch_plan( int64_t num_frames, float sample_rate, const
 	if( out_frames ) *out_frames = rp_out_frames( inv_factors, count, granularity_frames );
 	return wdl_export_plan( plan.blocks, num_blocks, capacity, offsets, fracpos, ratio, filtpos, oversize, ideal, first_out,
 		[&]( int64_t i, const RpBlock & b ) { if( wanted ) wanted[i] = b.wanted; } );
+	}
+
+int64_t flanhip_audio_repitch_runs( int64_t num_frames, float sample_rate, const float * inv_factors, int64_t count, int64_t granularity_frames,
+	int quality, int64_t num_channels, int64_t capacity, int64_t * first_block, int32_t * num_blocks, int64_t * win_start, int32_t * win_len,
+	int32_t * channels_per_group, int64_t * groups )
+	{
+	static const float dummy = 0.0f;
+	if( int rc = rp_check( &dummy, num_channels, num_frames, sample_rate, inv_factors, count, granularity_frames, quality, &dummy ) ) return rc;
+	RpPlan plan;
+	std::vector<RpRun> runs;
+	if( int rc = rp_prepare( num_channels, num_frames, sample_rate, inv_factors, count, granularity_frames, quality, &plan, &runs ) ) return rc;
+	int64_t grp = 0;
+	const int cpw = runs.empty() ? 0 : rp_channel_groups( plan, runs, granularity_frames, num_channels, &grp );     // (no runs: the point kernel has no groups)
+	if( channels_per_group ) *channels_per_group = cpw;
+	if( groups ) *groups = grp;
+	const int64_t fill = std::min<int64_t>( std::max<int64_t>( capacity, 0 ), int64_t( runs.size() ) );
+	for( int64_t i = 0; i < fill; ++i )
+		{
+		const RpRun & r = runs[size_t( i )];
+		if( first_block ) first_block[i] = r.first_block;
+		if( num_blocks ) num_blocks[i] = r.num_blocks;
+		if( win_start ) win_start[i] = r.win_start;
+		if( win_len ) win_len[i] = r.win_len;
+		}
+	return int64_t( runs.size() );
 	}
 
 size_t flanhip_audio_repitch_workspace_bytes( int64_t num_frames, float sample_rate, const float * inv_factors, int64_t count,

@@ -570,8 +570,8 @@ int launch_wt_synth( const float * d_table, int64_t ch, int64_t row_stride, cons
 	FLANHIP_CHECK( hipStreamSynchronize( s ) );                                  // the host arrays may go once the copies have read them
 	const double * d_win = nullptr;
 	if( int rc = wdl_window<WT_TAPS>( "wavetable_synth", d_ws, l.wdl, runs, s, &d_win ) ) return rc;
-	const int cpw = wdl_channels_per_group( out_frames, runs.size(), ch );
-	const int64_t groups = ( ch + cpw - 1 ) / cpw;
+	int64_t groups = 0;
+	const int cpw = wdl_channel_groups( out_frames, runs.size(), ch, &groups );
 	const WtBlock * d_blocks = (const WtBlock*) ( ws + l.wdl.block_off );
 	const WtRun * d_runs = (const WtRun*) ( ws + l.wdl.run_off );
 	const float * d_index = (const float*) ( ws + l.index_off );
@@ -843,6 +843,36 @@ int64_t flanhip_wavetable_synth_plan( int64_t out_frames, float sample_rate, int
 	WtPlan plan;
 	if( int rc = wt_synth_plan( out_frames, wt_rate_out( sample_rate, wavelength ), granularity_frames, freq, freq_count, &plan ) ) return rc;
 	return wt_plan_copy( plan, capacity, offsets, fracpos, ratio, filtpos, oversize, ideal, first_out, num_out, wanted, in_start );
+	}
+
+int64_t flanhip_wavetable_synth_runs( int64_t out_frames, float sample_rate, int32_t wavelength, int64_t granularity_frames, const float * freq,
+	int64_t freq_count, int64_t num_channels, int64_t capacity, int64_t * first_out, int32_t * num_out, int64_t * first_block, int32_t * num_blocks,
+	int64_t * j0, int64_t * win_start, int32_t * win_len, int32_t * channels_per_group, int64_t * groups )
+	{
+	if( int rc = wt_synth_check( out_frames, sample_rate, wavelength, granularity_frames, freq, freq_count ) ) return rc;
+	FLANHIP_REQUIRE( num_channels > 0, FLANHIP_ERR_INVALID_ARG, "non-positive size" );
+	FLANHIP_REQUIRE( num_channels <= ( 1 << 16 ), FLANHIP_ERR_UNSUPPORTED, "table out of range" );
+	WtPlan plan;
+	std::vector<WtRun> runs;
+	if( int rc = wt_synth_plan( out_frames, wt_rate_out( sample_rate, wavelength ), granularity_frames, freq, freq_count, &plan ) ) return rc;
+	wt_runs( plan, &runs );
+	int64_t grp = 0;
+	const int cpw = wdl_channel_groups( out_frames, runs.size(), num_channels, &grp );
+	if( channels_per_group ) *channels_per_group = cpw;
+	if( groups ) *groups = grp;
+	const int64_t fill = std::min<int64_t>( std::max<int64_t>( capacity, 0 ), int64_t( runs.size() ) );
+	for( int64_t i = 0; i < fill; ++i )
+		{
+		const WtRun & r = runs[size_t( i )];
+		if( first_out ) first_out[i] = r.first_out;
+		if( num_out ) num_out[i] = r.num_out;
+		if( first_block ) first_block[i] = r.first_block;
+		if( num_blocks ) num_blocks[i] = r.num_blocks;
+		if( j0 ) j0[i] = r.j0;
+		if( win_start ) win_start[i] = r.win_start;
+		if( win_len ) win_len[i] = r.win_len;
+		}
+	return int64_t( runs.size() );
 	}
 
 size_t flanhip_wavetable_synth_workspace_bytes( int64_t num_channels, int64_t out_frames, float sample_rate, int32_t wavelength, int64_t granularity_frames,

@@ -101,6 +101,14 @@ inline int wdl_channels_per_group( int64_t outputs, size_t num_runs, int64_t ch 
 	return int( std::clamp<int64_t>( 512 / per_run, 1, ch ) );
 	}
 
+// the same and the channel groups a launch then has: its grid is runs x *groups
+inline int wdl_channel_groups( int64_t outputs, size_t num_runs, int64_t ch, int64_t * groups )
+	{
+	const int cpw = wdl_channels_per_group( outputs, num_runs, ch );
+	*groups = ( ch + cpw - 1 ) / cpw;
+	return cpw;
+	}
+
 // the workspace of a call: the window factors, then the block records, then the run records
 struct WdlLayout { size_t win_off, block_off, run_off, total; };
 template<int TAPS>

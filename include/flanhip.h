@@ -489,6 +489,15 @@ int64_t flanhip_audio_repitch_out_frames(const float * inv_factors, int64_t coun
 int64_t flanhip_audio_repitch_plan(int64_t num_frames, float sample_rate, const float * inv_factors, int64_t count, int64_t granularity_frames,
                                    int quality, int64_t capacity, int64_t * offsets, double * fracpos, double * ratio, double * filtpos,
                                    int32_t * oversize, int32_t * ideal, int64_t * first_out, int32_t * wanted, int64_t * out_frames);
+/* How the SINC launch cuts that plan into runs (host arithmetic, no device; the launch's own planner, for tests that must know which path
+ * a shape takes): a run is consecutive blocks that one workgroup computes from one coefficient table.  Returns the number of runs (0 for
+ * UNINTERPOLATED, which has none) or a negative FLANHIP_ERR_* as the plan does, and fills the first `capacity` records of every array that is
+ * not null: the run's first block and block count, and the stream window it stages in LDS, [win_start, win_start + win_len); win_len 0
+ * means the window is too long to stage and every tap is read from global memory.  *channels_per_group / *groups (nullable): the channels
+ * one workgroup walks and the groups per run for num_channels channels (the grid is runs x groups); both 0 where there are no runs. */
+int64_t flanhip_audio_repitch_runs(int64_t num_frames, float sample_rate, const float * inv_factors, int64_t count, int64_t granularity_frames,
+                                   int quality, int64_t num_channels, int64_t capacity, int64_t * first_block, int32_t * num_blocks,
+                                   int64_t * win_start, int32_t * win_len, int32_t * channels_per_group, int64_t * groups);
 /* bytes of device workspace flanhip_audio_repitch_dev needs (host arithmetic: it runs the plan; 0 for arguments it refuses): the window
  * factors (64 x 2080 doubles), 56 bytes per block and 40 per run */
 size_t flanhip_audio_repitch_workspace_bytes(int64_t num_frames, float sample_rate, const float * inv_factors, int64_t count,
@@ -1203,6 +1212,17 @@ int flanhip_wavetable_resample(const float * audio, int64_t num_channels, int64_
 int64_t flanhip_wavetable_synth_plan(int64_t out_frames, float sample_rate, int32_t wavelength, int64_t granularity_frames, const float * freq,
                                      int64_t freq_count, int64_t capacity, int64_t * offsets, double * fracpos, double * ratio, double * filtpos,
                                      int32_t * oversize, int32_t * ideal, int64_t * first_out, int32_t * num_out, int32_t * wanted, int64_t * in_start);
+/* How the synthesis launch cuts that plan into runs (host arithmetic, no device; the launch's own planner, for tests that must know which
+ * path a shape takes): a run is consecutive output frames that one workgroup computes from one coefficient table and one staged stream
+ * window.  Returns the number of runs or a negative FLANHIP_ERR_* as the plan does (num_channels <= 0: FLANHIP_ERR_INVALID_ARG), and fills the
+ * first `capacity` records of every array that is not null: the run's first output frame and frame count, the block of its first frame
+ * and how many blocks its frames lie in, j0 (the run's first frame is output j0 of that block: above 0 only where a block was cut into
+ * pieces), and the staged window [win_start, win_start + win_len), which holds every tap of the run.  *channels_per_group / *groups
+ * (nullable): the channels one workgroup walks and the groups per run for num_channels channels (the grid is runs x groups). */
+int64_t flanhip_wavetable_synth_runs(int64_t out_frames, float sample_rate, int32_t wavelength, int64_t granularity_frames, const float * freq,
+                                     int64_t freq_count, int64_t num_channels, int64_t capacity, int64_t * first_out, int32_t * num_out,
+                                     int64_t * first_block, int32_t * num_blocks, int64_t * j0, int64_t * win_start, int32_t * win_len,
+                                     int32_t * channels_per_group, int64_t * groups);
 /* Wavetable::synthesize (:266-334).  table: float[ch][slots W]; freq: as above (HOST); index: float[ch][num_blocks] (HOST), the table
  * index of every ( channel, block ) -- ratio_to_table_index of the ratio Function at the block's first frame, within [0, slots - 1] --;
  * out: float[ch][out_frames], every element written.  Input sample t, appended by the block q with in_start[q] <= t < in_start[q] + wanted[q], is

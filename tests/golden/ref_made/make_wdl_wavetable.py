@@ -2,9 +2,11 @@
 """Vectors of Wavetable::synthesize made by the reference's own WDL_Resampler (src/WDL/resample.cpp, compiled in place into a temporary
 directory together with wdl_wavetable_driver.cpp, which runs the block loop of Wavetable.cpp:293-330 around it).
 
-    FLAN_REFERENCE_SRC=<the reference's src directory> python tests/golden/ref_made/make_wdl_wavetable.py
+    FLAN_REFERENCE_SRC=<the reference's src directory> python tests/golden/ref_made/make_wdl_wavetable.py [runs]
 
-wdl_wavetable.npz holds, per case k of `names`: table_k float32 [ch][slots * W], freq_k float32 [frames] and index_k float32 [ch][frames]
+Without an argument it writes wdl_wavetable.npz from CASES; with `runs`, wdl_wavetable_runs.npz from RUN_CASES, the shapes that hold the run
+planner of the synthesis launch (blocks cut into pieces, channel groups: DESIGN.md 4.23).  Either file holds, per case k of `names`:
+table_k float32 [ch][slots * W], freq_k float32 [frames] and index_k float32 [ch][frames]
 (the frequency and the table index at every output frame: a block reads those of its first frame), meta_k = (sample rate, W, g, output
 frames, smooth, blocks), out_k float32 [ch][frames], wanted_k and delivered_k int32 [blocks].  The table indices come from
 tests/wavetable_reference.table_index over starts_k (one row per channel, padded with -1) and ratio_k float32 [frames]."""
@@ -54,6 +56,22 @@ CASES = [
 ]
 
 
+# The cases of the run planner: W = 64, smooth, the ratio swept 0 -> 1, random tables of 3 slots.  ( name, channels, g, frames, freq curve ).
+# What each shape must reach is asserted from the exported run table by tests/test_gpu_wavetable.py (RUN_PATHS).
+RUN_W, RUN_SLOTS = 64, 3
+RUN_CASES = [
+    ("piece_window", 2, 480, 1500, const(9803.7)),                # ratio 13.07, not ideal (9800 Hz is, through the GCD): every full block's window is past the staging buffer
+    ("piece_ratio32", 1, 480, 1200, const(24000.0)),              # ratio 32 (ideal, low-pass), the largest below the refusal: 3 pieces a block
+    ("piece_outputs_and_window", 2, 4800, 6000, const(2227.2)),   # ratio 2.9696: 2047 steps span 6078 or 6079 samples, so one block is cut at 2048 outputs and by the window
+    ("groups", 7, 100, 1200, sweep(225.0, 2475.0)),               # a table per block: 4 channels per workgroup, groups of 4 and 3
+]
+
+
+def run_starts(ch):
+    """3 starts per channel, different in every channel, inside the 1000 source frames"""
+    return [[0, 300 + 20 * c, 700 + 30 * c] for c in range(ch)]
+
+
 def make_table(W, seed):
     """5 slots of smooth random waveforms; the slots a channel does not fill stay 0, as resample_waveforms leaves them"""
     rng = np.random.default_rng(seed)
@@ -82,29 +100,39 @@ def build(tmp):
 
 
 def main():
-    out = {"names": np.array([c[0] for c in CASES])}
+    runs = sys.argv[1:] == ["runs"]
+    assert runs or not sys.argv[1:], "usage: make_wdl_wavetable.py [runs]"
+    if runs:
+        cases = [(name, RUN_W, g, frames, fcurve, sweep(0.0, 1.0), True, run_starts(ch)) for name, ch, g, frames, fcurve in RUN_CASES]
+    else:
+        cases = [c + (STARTS,) for c in CASES]
+    out = {"names": np.array([c[0] for c in cases])}
     with tempfile.TemporaryDirectory() as tmp:
         L = build(tmp)
-        for k, (name, W, g, frames, fcurve, rcurve, smooth) in enumerate(CASES):
-            table = make_table(W, 2000 + k)
+        for k, (name, W, g, frames, fcurve, rcurve, smooth, case_starts) in enumerate(cases):
+            if runs:
+                table = (0.5 * np.random.default_rng(2100 + k).standard_normal((len(case_starts), RUN_SLOTS * W))).astype(F32)
+            else:
+                table = make_table(W, 2000 + k)
             ch, slots = table.shape[0], table.shape[1] // W
             freq, ratio = fcurve(frames), rcurve(frames)
-            index = np.array([[R.table_index(s, SOURCE_FRAMES, r) for r in ratio] for s in STARTS], F32)
+            index = np.array([[R.table_index(s, SOURCE_FRAMES, r) for r in ratio] for s in case_starts], F32)
             y = np.zeros((ch, frames), F32)
             cap = 1 << 16
             wanted, delivered = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
             blocks = int(L.wdl_wavetable(table.reshape(-1), ch, slots, W, SR, frames, g, freq, index.reshape(-1), int(smooth), y.reshape(-1),
                                          wanted, delivered, cap))
             assert 0 < blocks <= cap
+            assert int(delivered[:blocks].sum()) == frames, "the reference's resampler did not deliver every frame"
             starts = np.full((ch, slots), -1, np.int32)
-            for c, s in enumerate(STARTS):
+            for c, s in enumerate(case_starts):
                 starts[c, :len(s)] = s
             out["table_%d" % k], out["freq_%d" % k], out["ratio_%d" % k], out["index_%d" % k], out["out_%d" % k] = table, freq, ratio, index, y
             out["starts_%d" % k] = starts
             out["wanted_%d" % k], out["delivered_%d" % k] = wanted[:blocks].copy(), delivered[:blocks].copy()
             out["meta_%d" % k] = np.array([SR, W, g, frames, int(smooth), blocks], np.float64)
             print("%-16s W=%d g=%d frames=%d -> %d blocks, delivered %d ... %d" % (name, W, g, frames, blocks, delivered[:blocks].min(), delivered[:blocks].max()))
-    path = os.path.join(HERE, "wdl_wavetable.npz")
+    path = os.path.join(HERE, "wdl_wavetable_runs.npz" if runs else "wdl_wavetable.npz")
     np.savez_compressed(path, **out)
     print(path, os.path.getsize(path), "bytes")
 

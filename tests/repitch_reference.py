@@ -15,6 +15,7 @@ F32 = np.float32
 SINC, LINEAR, UNINTERPOLATED = 0, 1, 2
 SINC_SIZE, SINC_OVERSIZE = 64, 32                       # SetMode( true, 0, true, 64 ): 64 taps, 32 slices unless the rates are "ideal"
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_made", "wdl_repitch.npz")
+GOLDEN_RUNS = os.path.join(os.path.dirname(GOLDEN), "wdl_repitch_runs.npz")       # the cases that hold the run planner
 
 
 def invert(factors):
@@ -171,9 +172,32 @@ def errors(y, ref):
     return float(np.sqrt(np.sum(d * d) / np.sum(ref * ref))), float(np.max(np.abs(d)) / scale)
 
 
-def load_cases():
-    """the reference-made fixture as a list of dicts: name, x, inv, sr, g, quality, out, wanted, delivered"""
-    z = np.load(GOLDEN)
+def random_case(seed):
+    """the random shapes the planner tests and the device tests share: ( x float32 [ch][n], sr, inv, g, quality )"""
+    rng = np.random.default_rng(seed)
+    n = int(rng.integers(1, 5001))
+    ch = int(rng.integers(1, 4))
+    g = int(rng.choice([1, 7, 48, 100, 480, 6000])) if n <= 1000 else int(rng.choice([48, 100, 480, 6000]))
+    count = factor_count(n, g)
+    kind = int(rng.integers(0, 4))
+    t = np.arange(count) / max(count - 1, 1)
+    if kind == 0:
+        v = np.full(count, rng.choice([0.25, 0.5, 0.75, 1.0, 1.25, 2.0, 3.0, 0.9, 1.7]))
+    elif kind == 1:
+        lo, hi = sorted(rng.uniform(0.3, 3.0, 2))
+        v = lo + (hi - lo) * t
+    elif kind == 2:
+        v = 1.0 + 0.6 * np.sin(2 * np.pi * rng.uniform(0.5, 4.0) * t)
+    else:
+        v = rng.choice([0.5, 1.0, 1.5, 2.0], count)
+    quality = UNINTERPOLATED if seed % 5 == 4 else SINC
+    x = (0.5 * rng.standard_normal((ch, n))).astype(F32)
+    return x, 48000.0, invert(v.astype(F32)), g, quality
+
+
+def load_cases(path=GOLDEN):
+    """a reference-made fixture as a list of dicts: name, x, inv, sr, g, quality, out, wanted, delivered"""
+    z = np.load(path)
     cases = []
     for k, name in enumerate(z["names"]):
         sr, g, quality, nout, blocks = z["meta_%d" % k]

@@ -1,6 +1,9 @@
 """flan::Wavetable on the MI355X (flan_amd/csrc/wavetable.hip): the table construction against the fp64 truth, the synthesis against the
 vectors the reference's own WDL_Resampler made (tests/golden/ref_made/wdl_wavetable.npz) and against the Python restatement
 (tests/wavetable_reference.py), the in-place edits against their fp64 forms.  DESIGN.md 4.23 lists the measured values.
+The run-planner cases (wdl_wavetable_runs.npz) each assert, from the exported run table (flanhip_wavetable_synth_runs), that they take the
+path they are named for -- a block cut into pieces by the staged window, by the output cap, by both; several channels per workgroup in more
+than one group -- and are held to bit identity like the others.
 
 Resample: rotations equal the truth's exactly (test_wavetable_reference.py holds the decision margins that allow it); the relative-max error
 of a waveform is at most 4 x the single-precision stand-in's on the same waveform, with a floor of 4 fp32 ulp (2^-22).
@@ -24,6 +27,9 @@ REL_MAX_BOUND = 0.0
 
 CASES = R.load_cases()
 IDS = [c["name"] for c in CASES]
+RUN_CASES = R.load_cases(R.GOLDEN_RUNS)
+RUN_IDS = [c["name"] for c in RUN_CASES]
+RUN_OUTPUTS = 2048                                                 # wavetable.hip's output frames per run
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -135,31 +141,9 @@ def test_synth_against_the_reference_made_output(c):
     assert rel_rms <= REL_RMS_BOUND and rel_max <= REL_MAX_BOUND, (rel_rms, rel_max)
 
 
-def random_case(seed):
-    rng = np.random.default_rng(seed)
-    W = int(rng.choice([64, 128]))
-    ch = int(rng.integers(1, 4))
-    g = int(rng.choice([1, 7, 48, 480]))
-    frames = int(rng.integers(1, 3001)) if g > 1 else int(rng.integers(1, 400))
-    slots = int(rng.integers(2, 6))
-    in_freq = 48000.0 / W
-    kind = int(rng.integers(0, 3))
-    t = np.arange(frames) / max(frames - 1, 1)
-    if kind == 0:
-        freq = np.full(frames, in_freq * rng.choice([0.25, 0.5, 1.0, 2.0, 3.0, 0.9, 1.7, 0.133]))
-    elif kind == 1:
-        lo, hi = sorted(rng.uniform(0.2, 6.0, 2))
-        freq = in_freq * (lo + (hi - lo) * t)
-    else:
-        freq = in_freq * (1.0 + 0.6 * np.sin(2 * np.pi * rng.uniform(0.5, 4.0) * t))
-    table = (0.5 * rng.standard_normal((ch, slots * W))).astype(F32)
-    ratio = rng.uniform(0.0, 1.0, frames) if seed % 2 else t
-    return table, W, slots, frames, g, freq.astype(F32), ratio.astype(F32), bool(seed % 3)
-
-
 @pytest.mark.parametrize("seed", range(20))
 def test_synth_random_shapes_against_the_restatement(seed):
-    table, W, slots, frames, g, freq, ratio, smooth = random_case(seed)
+    table, W, slots, frames, g, freq, ratio, smooth = R.random_synth_case(seed)         # (shared with the planner tests of test_wavetable_capi.py)
     blocks = R.synth_plan(frames, 48000.0, W, g, freq)
     first = np.array([b["first_out"] for b in blocks])
     index = np.ascontiguousarray(np.tile((ratio[first] * F32(slots - 1)).astype(F32), (table.shape[0], 1)))
@@ -198,6 +182,105 @@ def test_synth_host_and_device_forms_are_bit_identical():
         fa.wavetable_synth_dev(d_table, ch, slots, c["W"], c["sr"], c["out_frames"], c["g"], c["freq"], idx, c["smooth"], d_out, d_ws)
         torch.cuda.synchronize()
         assert np.array_equal(y_host.view(np.uint32), d_out.cpu().numpy().view(np.uint32)), name
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the run planner's paths (wdl_wavetable_runs.npz)
+
+def tables(c):
+    """( the block plan, the run table ) of a case as the launch computes them"""
+    args = (c["out_frames"], c["sr"], c["W"], c["g"], c["freq"])
+    return fa.wavetable_synth_plan(*args), fa.wavetable_synth_runs(*args, c["table"].shape[0])
+
+
+def pieces(r, b):
+    """the runs that block b was cut into: their indices, none if the block lies whole in a run"""
+    ks = [k for k in range(r["first_out"].size) if r["first_block"][k] == b and r["num_blocks"][k] == 1]
+    return ks if len(ks) > 1 else []
+
+
+def path_pieces(c, ideal, ratio, per_block):
+    p, r = tables(c)
+    assert np.all(p["ideal"] == ideal) and ratio(p["ratio"])
+    full = [b for b in range(p["num_out"].size) if p["num_out"][b] >= c["g"]]
+    assert len(full) >= 2
+    for b in full:                                                           # every full block is cut, by the window (no piece reaches the output cap)
+        ks = pieces(r, b)
+        assert per_block(len(ks)), (b, ks)
+        assert [int(r["j0"][k]) for k in ks] == list(np.cumsum([0] + [int(r["num_out"][k]) for k in ks[:-1]])) and r["j0"][ks[1]] > 0
+        assert all(r["num_out"][k] < RUN_OUTPUTS for k in ks)
+
+
+def path_outputs_and_window(c):
+    p, r = tables(c)
+    assert np.all(p["ideal"] == 0)
+    ks = pieces(r, 0)
+    assert len(ks) >= 3
+    inner = [int(r["num_out"][k]) for k in ks[:-1]]                           # every piece but the block's last was closed by a limit
+    assert RUN_OUTPUTS in inner and any(v < RUN_OUTPUTS for v in inner), inner           # the output cap, and the window before the cap
+
+
+def path_groups(c):
+    p, r = tables(c)
+    assert c["table"].shape[0] == 7 and (r["channels_per_group"], r["groups"]) == (4, 2)        # groups of 4 and 3 channels
+    assert r["first_out"].size >= p["num_out"].size - 2                      # a table per block
+
+
+RUN_PATHS = {
+    "piece_window": lambda c: path_pieces(c, 0, lambda ratio: np.all((ratio > 13.0) & (ratio < 13.1)), lambda pieces: pieces >= 2),
+    "piece_ratio32": lambda c: path_pieces(c, 1, lambda ratio: np.all(ratio == 32.0), lambda pieces: pieces == 3),
+    "piece_outputs_and_window": path_outputs_and_window,
+    "groups": path_groups,
+}
+
+_device_outputs = {}
+
+
+def device_output(c):
+    """a run-planner case's output in device form, into an output pre-filled with NaN over a workspace pre-filled with 0xFF; computed once"""
+    if c["name"] not in _device_outputs:
+        dev = torch.device("cuda", 0)
+        plan = fa.wavetable_synth_plan(c["out_frames"], c["sr"], c["W"], c["g"], c["freq"])
+        ch, slots = c["table"].shape[0], c["table"].shape[1] // c["W"]
+        d_table = torch.from_numpy(c["table"]).to(dev)
+        d_out = torch.full((ch, c["out_frames"]), float("nan"), dtype=torch.float32, device=dev)
+        d_ws = torch.full((fa.wavetable_synth_workspace_bytes(ch, c["out_frames"], c["sr"], c["W"], c["g"], c["freq"]),), 0xFF, dtype=torch.uint8, device=dev)
+        fa.wavetable_synth_dev(d_table, ch, slots, c["W"], c["sr"], c["out_frames"], c["g"], c["freq"], block_index(c, plan), c["smooth"], d_out, d_ws)
+        torch.cuda.synchronize()
+        _device_outputs[c["name"]] = d_out.cpu().numpy()
+    return _device_outputs[c["name"]]
+
+
+def test_every_run_case_has_its_path():
+    assert sorted(RUN_PATHS) == sorted(RUN_IDS)
+
+
+@pytest.mark.parametrize("c", RUN_CASES, ids=RUN_IDS)
+def test_run_case_takes_the_path_it_is_named_for(c):
+    RUN_PATHS[c["name"]](c)
+
+
+@pytest.mark.parametrize("c", RUN_CASES, ids=RUN_IDS)
+def test_run_case_against_the_reference_made_output(c):
+    y = device_output(c)
+    assert y.shape == c["out"].shape and not np.any(np.isnan(y))
+    rel_rms, rel_max = R.errors(y, c["out"])
+    differ = int(np.sum(y.view(np.uint32) != c["out"].view(np.uint32)))
+    print("%s: rel_rms=%.3e rel_max=%.3e, %d of %d samples differ" % (c["name"], rel_rms, rel_max, differ, y.size))
+    assert rel_rms <= REL_RMS_BOUND and rel_max <= REL_MAX_BOUND, (rel_rms, rel_max)
+
+
+@pytest.mark.parametrize("c", RUN_CASES, ids=RUN_IDS)
+def test_run_case_channels_runs_and_forms_are_bit_identical(c):
+    y = device_output(c)
+    bits = y.view(np.uint32)
+    plan = fa.wavetable_synth_plan(c["out_frames"], c["sr"], c["W"], c["g"], c["freq"])
+    idx = block_index(c, plan)
+    for k in range(c["table"].shape[0]):                                     # a channel does not depend on the group it is walked in
+        mono = fa.wavetable_synth(c["table"][k:k + 1], c["W"], c["sr"], c["out_frames"], c["g"], c["freq"], idx[k:k + 1], c["smooth"])
+        assert np.array_equal(bits[k], mono[0].view(np.uint32)), (c["name"], k)
+    assert np.array_equal(bits, run(c).view(np.uint32)), c["name"]           # the host form
+    assert np.array_equal(bits, run(c).view(np.uint32)), c["name"]           # and again
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -10,6 +10,8 @@ import repitch_reference as R
 
 CASES = R.load_cases()
 IDS = [c["name"] for c in CASES]
+RUN_CASES = R.load_cases(R.GOLDEN_RUNS)                     # the run planner's cases (wdl_repitch_runs.npz): held to the same here
+RUN_IDS = [c["name"] for c in RUN_CASES]
 _restated = {}
 
 
@@ -26,7 +28,7 @@ def test_the_fixture_holds_the_cases_the_design_lists():
     assert {c["x"].shape[1] for c in CASES} >= {1, 20, 1000}
 
 
-@pytest.mark.parametrize("case", CASES, ids=IDS)
+@pytest.mark.parametrize("case", CASES + RUN_CASES, ids=IDS + RUN_IDS)
 def test_plan_is_the_references(case):
     n = case["x"].shape[1]
     blocks = R.plan(n, case["sr"], case["inv"], case["g"], case["quality"])            # (asserts the three invariants)
@@ -37,7 +39,7 @@ def test_plan_is_the_references(case):
     assert [b["first_out"] for b in blocks] == [case["g"] * i for i in range(len(blocks))]
 
 
-@pytest.mark.parametrize("case", CASES, ids=IDS)
+@pytest.mark.parametrize("case", CASES + RUN_CASES, ids=IDS + RUN_IDS)
 def test_samples_are_bit_identical(case):
     y = restated(case)
     assert y.shape == case["out"].shape

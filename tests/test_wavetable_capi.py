@@ -1,5 +1,7 @@
 """flan::Wavetable's C ABI (include/flanhip.h, flan_amd/csrc/wavetable.hip) without a device: symbols, the host-only entry points (snap,
-starts, table index, every field of the synthesis plan) against the restatement bit for bit, refusals."""
+starts, table index, every field of the synthesis plan) against the restatement bit for bit, refusals, and the invariants of the runs the
+synthesis launch cuts that plan into (the exported run table, over the fixture cases, the random seeds of the device tests and the
+run-planner cases of wdl_wavetable_runs.npz)."""
 import ctypes
 import os
 
@@ -22,10 +24,13 @@ F32 = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["flanhip_wavetable_snap", "flanhip_wavetable_starts", "flanhip_wavetable_table_index", "flanhip_wavetable_slots",
            "flanhip_wavetable_resample_workspace_bytes", "flanhip_wavetable_resample_dev", "flanhip_wavetable_resample",
-           "flanhip_wavetable_synth_plan", "flanhip_wavetable_synth_workspace_bytes", "flanhip_wavetable_synth_dev", "flanhip_wavetable_synth",
+           "flanhip_wavetable_synth_plan", "flanhip_wavetable_synth_runs", "flanhip_wavetable_synth_workspace_bytes", "flanhip_wavetable_synth_dev", "flanhip_wavetable_synth",
            "flanhip_wavetable_edit_dev", "flanhip_wavetable_edit"]
 CASES = R.load_cases()
 IDS = [c["name"] for c in CASES]
+RUN_CASES = R.load_cases(R.GOLDEN_RUNS)
+RUN_IDS = [c["name"] for c in RUN_CASES]
+WINDOW_FLOATS, RUN_OUTPUTS = 6144, 2048                            # the limits wavetable.hip cuts its runs by
 PLAN_KEYS = ("offset", "fracpos", "ratio", "filtpos", "oversize", "ideal", "first_out", "num_out", "wanted", "in_start")
 
 
@@ -45,7 +50,7 @@ def test_wavetable_symbols_are_exported_and_bound():
         assert hasattr(lib, name), name
         assert name in fa.EXPORTS, name
         assert name + "(" in header, name
-    for name in ("wavetable_snap", "wavetable_starts", "wavetable_table_index", "wavetable_resample", "wavetable_resample_dev", "wavetable_synth_plan",
+    for name in ("wavetable_snap", "wavetable_starts", "wavetable_table_index", "wavetable_resample", "wavetable_resample_dev", "wavetable_synth_plan", "wavetable_synth_runs",
                  "wavetable_synth", "wavetable_synth_dev", "wavetable_edit", "wavetable_edit_dev"):
         assert callable(getattr(fa, name))
 
@@ -111,7 +116,7 @@ def test_table_index_equals_the_restatement():
         assert got[~finite].tolist() == [0.0, len(starts) - 1, 0.0, len(starts) - 1]          # NaN is 0; what no Frame holds saturates
 
 
-@pytest.mark.parametrize("c", CASES, ids=IDS)
+@pytest.mark.parametrize("c", CASES + RUN_CASES, ids=IDS + RUN_IDS)
 def test_synth_plan_equals_the_restatement_and_the_reference(c):
     plan = fa.wavetable_synth_plan(c["out_frames"], c["sr"], c["W"], c["g"], c["freq"])
     want = R.synth_plan(c["out_frames"], c["sr"], c["W"], c["g"], c["freq"])
@@ -221,3 +226,91 @@ def test_valid_calls_without_a_device_say_so():
     with pytest.raises(fa.FlanHipError) as e:
         fa.wavetable_edit(c["table"], c["W"], fa.WT_NORMALIZE)
     assert e.value.code == fa.ERR_NO_DEVICE
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the runs of the synthesis launch (flanhip_wavetable_synth_runs: the launch's own planner, exported)
+
+def planner_shapes():
+    """( id, ch, out_frames, sr, W, g, freq ) of every fixture case, every random seed of the device tests and every run-planner case"""
+    shapes = [(c["name"], c["table"].shape[0], c["out_frames"], c["sr"], c["W"], c["g"], c["freq"]) for c in CASES + RUN_CASES]
+    for seed in range(20):
+        table, W, slots, frames, g, freq, ratio, smooth = R.random_synth_case(seed)
+        shapes.append(("seed%d" % seed, table.shape[0], frames, 48000.0, W, g, freq))
+    return shapes
+
+
+SHAPES = planner_shapes()
+
+
+def block_positions(plan, b):
+    """srcpos of every output of block b: the reference's chain of additions from the block's fracpos"""
+    pos, out = float(plan["fracpos"][b]), []
+    for _ in range(int(plan["num_out"][b])):
+        out.append(pos)
+        pos += float(plan["ratio"][b])
+    return out
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=[s[0] for s in SHAPES])
+def test_runs_tile_the_output_within_their_limits(shape):
+    _, ch, frames, sr, W, g, freq = shape
+    plan = fa.wavetable_synth_plan(frames, sr, W, g, freq)
+    r = fa.wavetable_synth_runs(frames, sr, W, g, freq, ch)
+    first_out, num_out = r["first_out"], r["num_out"].astype(np.int64)
+    assert np.all(plan["num_out"] >= 1)                                             # no block without output (DESIGN.md 4.23 says why)
+    # the runs' output frames tile [0, out_frames) once, in order
+    assert first_out.size >= 1 and first_out[0] == 0 and np.all(num_out >= 1)
+    assert np.array_equal(first_out[1:], first_out[:-1] + num_out[:-1]) and first_out[-1] + num_out[-1] == frames
+    assert np.all(num_out <= RUN_OUTPUTS)
+    assert np.all(r["win_len"] > 0) and np.all(r["win_len"] <= WINDOW_FLOATS)       # always staged: the kernel gives the row form an empty row
+    block_of = np.repeat(np.arange(plan["num_out"].size), plan["num_out"])          # the block of every output frame
+    block_end = plan["first_out"] + plan["num_out"]
+    for k in range(first_out.size):
+        a, z = int(first_out[k]), int(first_out[k] + num_out[k]) - 1                # the run's first and last frame
+        ba, bz = int(block_of[a]), int(block_of[z])
+        assert ba == r["first_block"][k] and bz < r["first_block"][k] + r["num_blocks"][k], k
+        assert a - int(plan["first_out"][ba]) == r["j0"][k], k
+        if r["j0"][k] > 0 or z + 1 != block_end[bz]:
+            assert ba == bz, k                                                      # a piece of a cut block: that block alone
+        with_output = [b for b in range(ba, bz + 1) if plan["num_out"][b] > 0]
+        for key in ("filtpos", "oversize", "ideal"):
+            assert all(plan[key][b] == plan[key][ba] for b in with_output), (k, key)       # one coefficient table per run
+        lo, hi = int(r["win_start"][k]), int(r["win_start"][k]) + int(r["win_len"][k])
+        for b in with_output:                                                       # the 64 taps of the first and last output of every block's share
+            pos = block_positions(plan, b)
+            j_first = a - int(plan["first_out"][b]) if b == ba else 0
+            j_last = z - int(plan["first_out"][b]) if b == bz else len(pos) - 1
+            for j in (j_first, j_last):
+                s0 = int(plan["offset"][b]) + int(pos[j])
+                assert lo <= s0 and s0 + R.TAPS <= hi, (k, b, j, lo, hi, s0)
+    cpw, groups = r["channels_per_group"], r["groups"]
+    assert cpw >= 1 and groups * cpw >= ch > (groups - 1) * cpw
+
+
+def test_channel_groups_cover_every_channel_count():
+    c = RUN_CASES[RUN_IDS.index("groups")]
+    for ch in range(1, 40):
+        r = fa.wavetable_synth_runs(c["out_frames"], c["sr"], c["W"], c["g"], c["freq"], ch)
+        cpw, groups = r["channels_per_group"], r["groups"]
+        assert 1 <= cpw <= ch and groups * cpw >= ch > (groups - 1) * cpw, (ch, cpw, groups)
+
+
+def test_runs_refusals_and_counting():
+    L = fa.lib
+    f = np.array([9803.7], F32)
+    none7 = [None] * 7
+    runs = lambda frames, g, fp, ch, cpw=None, groups=None: L.flanhip_wavetable_synth_runs(frames, 48000.0, 64, g, fp, 1, ch, 0, *none7, cpw, groups)     # noqa: E731
+    cpw, groups = ctypes.c_int(-1), ctypes.c_int64(-1)
+    assert runs(1500, 480, p(f), 2, ctypes.byref(cpw), ctypes.byref(groups)) == 7
+    assert (cpw.value, groups.value) == (2, 1)
+    assert runs(1500, 480, p(f), 2) == 7                                     # everything nullable
+    win_len = np.full(2, -1, np.int32)                                       # a capacity below the run count fills that many records
+    assert L.flanhip_wavetable_synth_runs(1500, 48000.0, 64, 480, p(f), 1, 2, 2, None, None, None, None, None, None, p(win_len), None, None) == 7
+    assert np.all(win_len > 0) and np.all(win_len <= WINDOW_FLOATS)
+    assert runs(1500, 480, p(f), 0) == fa.ERR_INVALID_ARG
+    assert runs(1500, 480, None, 2) == fa.ERR_INVALID_ARG
+    assert runs(1500, 0, p(f), 2) == fa.ERR_INVALID_ARG
+    assert runs(0, 480, p(f), 2) == fa.ERR_INVALID_ARG
+    high = np.array([750.0 * 40], F32)
+    assert runs(1500, 480, p(high), 2) == fa.ERR_UNSUPPORTED                 # the plan's own refusal

@@ -13,9 +13,11 @@ import wavetable_reference as R
 F32 = np.float32
 CASES = R.load_cases()
 IDS = [c["name"] for c in CASES]
+RUN_CASES = R.load_cases(R.GOLDEN_RUNS)                     # the run planner's cases (wdl_wavetable_runs.npz): held to the same here
+RUN_IDS = [c["name"] for c in RUN_CASES]
 
 
-@pytest.mark.parametrize("c", CASES, ids=IDS)
+@pytest.mark.parametrize("c", CASES + RUN_CASES, ids=IDS + RUN_IDS)
 def test_the_restatement_equals_the_reference_made_output(c):
     blocks = R.synth_plan(c["out_frames"], c["sr"], c["W"], c["g"], c["freq"])
     assert len(blocks) == c["blocks"]

@@ -16,6 +16,7 @@ TAPS, PRELUDE = 64, 31
 SNAP_NONE, SNAP_ZERO, SNAP_LEVEL = 0, 1, 2
 PITCH_NONE, PITCH_LOCAL, PITCH_GLOBAL = 0, 1, 2
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_made", "wdl_wavetable.npz")
+GOLDEN_RUNS = os.path.join(os.path.dirname(GOLDEN), "wdl_wavetable_runs.npz")     # the cases that hold the run planner
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -258,9 +259,32 @@ def errors(y, ref):
     return float(np.sqrt(np.sum(d * d) / np.sum(ref * ref))), float(np.max(np.abs(d)) / scale)
 
 
-def load_cases():
-    """the reference-made fixture as a list of dicts"""
-    z = np.load(GOLDEN)
+def random_synth_case(seed):
+    """the random shapes the planner tests and the device tests share: ( table, W, slots, frames, g, freq, ratio, smooth )"""
+    rng = np.random.default_rng(seed)
+    W = int(rng.choice([64, 128]))
+    ch = int(rng.integers(1, 4))
+    g = int(rng.choice([1, 7, 48, 480]))
+    frames = int(rng.integers(1, 3001)) if g > 1 else int(rng.integers(1, 400))
+    slots = int(rng.integers(2, 6))
+    in_freq = 48000.0 / W
+    kind = int(rng.integers(0, 3))
+    t = np.arange(frames) / max(frames - 1, 1)
+    if kind == 0:
+        freq = np.full(frames, in_freq * rng.choice([0.25, 0.5, 1.0, 2.0, 3.0, 0.9, 1.7, 0.133]))
+    elif kind == 1:
+        lo, hi = sorted(rng.uniform(0.2, 6.0, 2))
+        freq = in_freq * (lo + (hi - lo) * t)
+    else:
+        freq = in_freq * (1.0 + 0.6 * np.sin(2 * np.pi * rng.uniform(0.5, 4.0) * t))
+    table = (0.5 * rng.standard_normal((ch, slots * W))).astype(F32)
+    ratio = rng.uniform(0.0, 1.0, frames) if seed % 2 else t
+    return table, W, slots, frames, g, freq.astype(F32), ratio.astype(F32), bool(seed % 3)
+
+
+def load_cases(path=GOLDEN):
+    """a reference-made fixture as a list of dicts"""
+    z = np.load(path)
     cases = []
     for k, name in enumerate(z["names"]):
         sr, W, g, nout, smooth, blocks = z["meta_%d" % k]
